@@ -1,10 +1,15 @@
 #!/usr/bin/env python3
 """bench.py -- benchmark of the MI355X ray-trace/shade path (BASELINE.json metric: Mray/s, ms/frame).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--full] [--dump-outputs DIR]
 
 The LAST line on stdout is ONE compact JSON object (a fixed set of keys, < 8 KB: tests/test_bench_helpers.py); everything else
 the run measured goes to bench_detail.json next to this script and, as one line, to stderr.
+
+N = 1, plain run: set up, W warm-up frames (and >= 30 ms of untimed frames for the clocks), ONE timed loop of exactly K frames,
+the line.  `--dump-outputs DIR` writes the frame of the loop's last step to DIR/image.npy.  `--full` adds everything else after
+the headline: the loop repeated, the oracle's parity check, kernel times and roofline, the side rows, the other configurations
+of BASELINE.json and the CPU baseline (the line's `parity_check`, `roofline`, `cpu_baseline`, ... are null without it).
 
 N = 1 -- workload = BASELINE.json configs[1] ("C2"): 1280x720, 32 spheres + 1 checkered plane, FlatRenderer,
 pixel-centre rays (S=0), synthetic scene of SURVEY.md 8(d).  One *step* = one frame through the C-ABI
@@ -669,13 +674,68 @@ def run_single(args, local_rank):
     if resolved != 0:
         raise RuntimeError(f"{resolved} rays were settled without a world query although the dome shortcut is off")
     n_wg = st.grid
-    # the headline: K frames back to back -- the K-step loop REPEATED (20 launches of 15 us are a 0.3 ms timed region);
-    # `value` / `ms_per_step` are the MEDIAN repeat, min and max in the detail file.  Before the first timed loop the
-    # same launches run untimed for >= 30 ms (clocks), and the loop is repeated until >= 20 ms have been timed (at least
-    # --repeats times): K stays what --steps says for every loop
+    # the headline: ONE timed loop of exactly K = --steps frames back to back.  Before it the same launches run untimed for
+    # >= 30 ms (the GPU's clocks ramp over the first milliseconds of work: part of the warm-up)
     ds.set_count_rays(False)
     ds.set_timing(False)
     pre_n, pre_ms = pre_roll(loop, args.pre_roll_ms)
+    elapsed = timed_loop(ds, loop, args.steps, None, False, events=False)[0]
+    ms_per_step = elapsed / args.steps * 1e3
+    dumped = dump_outputs(args.dump_outputs, loop.image()) if args.dump_outputs else None  # the timed loop's last frame
+    result = {
+        "metric": "Mray/s (primary+shadow; rays handed to a world query) at 1280x720 per GPU, C2: 32 spheres + 1 plane, FlatRenderer",
+        "value": rays_per_step * args.steps / elapsed / 1e6,
+        "unit": "Mray/s",
+        "n_gpus": 1,
+        "steps": args.steps,
+        "warmup": args.warmup,
+        "ms_per_step": ms_per_step,
+        "pre_roll": {"launches": pre_n, "ms": pre_ms, "note": "untimed launches of the same kernel before the timed loop (clock ramp)"},
+        "hip_force_dev_kernarg": os.environ.get("HIP_FORCE_DEV_KERNARG"),
+        "code_hash": loaded_code_hash(),
+        "higher_is_better": True,
+        "scaling": "weak",
+        "vs_baseline": None,
+        "dtype": "f64",
+        "data": "synthetic",
+        "config": {"workload": f"C2 flat {W}x{H}, 32 spheres + 1 plane, S=0, every primary ray traced (dome shortcut off), fp32 RGB resident in HBM",
+                   "width": W, "height": H, "n_shapes": flat.n_shapes, "renderer": "FlatRenderer"},
+        "ray_shape_tests_per_s": rays_per_step * flat.n_shapes * args.steps / elapsed,
+        "rays_per_step": rays_per_step,
+        "value_note": "every ray counted in `value` was generated and handed to a world query (dome shortcut off for the headline "
+                      "loop: pt_set_dome_shortcut(0)); the library's default frame is frame_with_dome_shortcut (--full)",
+        "dumped_outputs": dumped,
+    }
+    if args.full:
+        full_rows(args, result, ds, loop, flat, cam, par, local_rank, rays_per_step, n_wg)
+    ds.close()
+    if args.full:
+        if not args.no_extras:
+            result["extra"] = extra_rows(local_rank)
+            result["boundary"] = boundary_rows(flat, local_rank, rays_per_step)
+        if not args.no_cpu_baseline:
+            result["cpu_baseline"] = cpu_baseline(flat)
+    emit(result, compact_single(result))
+
+
+def dump_outputs(out_dir, frame):
+    """--dump-outputs DIR: what the timed path computed in its last step, as a caller of it receives it -- the [H, W, 3] fp32 RGB
+    frame (11 MB at 1280x720, written whole) -> DIR/image.npy.  -> {name: shape}."""
+    os.makedirs(out_dir, exist_ok=True)
+    img = frame.detach().cpu().numpy()
+    if img.dtype != np.float32:
+        raise RuntimeError(f"bench.py --dump-outputs: the frame is {img.dtype}, expected float32")
+    np.save(os.path.join(out_dir, "image.npy"), img)
+    return {"image": list(img.shape)}
+
+
+def full_rows(args, result, ds, loop, flat, cam, par, local_rank, rays_per_step, n_wg):
+    """--full: everything beyond the headline, measured on the same scene handle and frame loop after it -- the K-step loop
+    REPEATED (median, min, max), the same loop at 10 x K, the oracle's parity check of the frame, per-launch and bracketed
+    kernel times, the dome-shortcut side row, the roofline and the rows with frames in flight.  Adds them to `result`."""
+    # the K-step loop REPEATED (20 launches of 15 us are a 0.3 ms timed region): until >= 20 ms have been timed, at least
+    # --repeats times; K stays what --steps says for every loop
+    pre_n, pre_ms = result["pre_roll"]["launches"], result["pre_roll"]["ms"]
     est_loop_s = max(1e-6, pre_ms * 1e-3 / max(1, pre_n) * args.steps)
     repeats = max(1, args.repeats, min(400, int(np.ceil(args.min_timed_ms * 1e-3 / est_loop_s))))
     elapsed_all = [timed_loop(ds, loop, args.steps, None, False, events=False)[0] for _ in range(repeats)]
@@ -800,42 +860,22 @@ def run_single(args, local_rank):
     roofline["hbm"] = {"achieved": alg_bytes / avg_kernel_s / 1e9, "peak": PEAK_HBM_GBS, "unit": "GB/s",
                        "frac": alg_bytes / avg_kernel_s / 1e9 / PEAK_HBM_GBS, "algorithmic_bytes_per_launch": alg_bytes,
                        "note": "12 B per pixel written + the scene once per workgroup: not the bound"}
-    result = {
-        "metric": "Mray/s (primary+shadow; rays handed to a world query) at 1280x720 per GPU, C2: 32 spheres + 1 plane, FlatRenderer",
-        "value": rays_per_step * args.steps / elapsed / 1e6,
-        "unit": "Mray/s",
-        "n_gpus": 1,
-        "steps": args.steps,
-        "warmup": args.warmup,
-        "ms_per_step": ms_per_step,
+    result.update({
         "repeats": {"n": repeats, "ms_per_step_median": ms_per_step, "ms_per_step_min": min(elapsed_all) / args.steps * 1e3,
                     "ms_per_step_max": max(elapsed_all) / args.steps * 1e3,
                     "ms_per_step_first_5": [e / args.steps * 1e3 for e in elapsed_all[:5]],
                     "ms_per_step_last_5": [e / args.steps * 1e3 for e in elapsed_all[-5:]],
                     "timed_ms_total": sum(elapsed_all) * 1e3,
-                    "pre_roll": {"launches": pre_n, "ms": pre_ms, "note": "untimed launches of the same kernel before the first timed loop (clock ramp)"},
-                    "note": "the K-step timed loop run `n` times back to back (until >= 20 ms are timed); value and ms_per_step are the median repeat"},
+                    "note": "the K-step timed loop run `n` more times back to back after the headline's one (until >= 20 ms are "
+                            "timed); `value` and `ms_per_step` are the headline loop's"},
         "same_loop_at_10x_steps": {"steps": k10, "ms_per_step": el10 / k10 * 1e3,
                                    "fixed_cost_per_timed_region_us": (elapsed - el10 / 10.0) / 0.9 * 1e6,
                                    "note": "the identical timed loop with 10 x K steps: ms_per_step(K) - ms_per_step(10 K) is the timed region's "
                                            "fixed cost (first launch in, last synchronisation out) spread over K steps, not kernel time"},
-        "hip_force_dev_kernarg": os.environ.get("HIP_FORCE_DEV_KERNARG"),
-        "code_hash": loaded_code_hash(),
         "parity_check": parity,
-        "higher_is_better": True,
-        "scaling": "weak",
-        "vs_baseline": None,
-        "dtype": "f64",
-        "data": "synthetic",
-        "config": {"workload": f"C2 flat {W}x{H}, 32 spheres + 1 plane, S=0, every primary ray traced (dome shortcut off), fp32 RGB resident in HBM",
-                   "width": W, "height": H, "n_shapes": flat.n_shapes, "renderer": "FlatRenderer"},
-        "ray_shape_tests_per_s": rays_per_step * flat.n_shapes * args.steps / elapsed,
-        "rays_per_step": rays_per_step,
-        "value_note": "every ray counted in `value` was generated and handed to a world query (dome shortcut off for the headline "
-                      "loop: pt_set_dome_shortcut(0)); the library's default frame is frame_with_dome_shortcut",
         "frame_with_dome_shortcut": dome_row,
         "roofline": roofline,
-    }
+    })
     if not parity["bit_identical"]:  # a fast frame that is not the reference's frame is not a result
         result["error"] = f"parity_check failed: the timed frame differs from the oracle's in {parity.get('pixels_differing', '?')} pixels"
         result["value_unchecked"], result["value"] = result["value"], None
@@ -846,13 +886,6 @@ def run_single(args, local_rank):
     if not args.no_in_flight:  # measured by THIS run: a few hundred frames, behind the headline loops
         result["frames_in_flight"] = in_flight_rows(flat, cam, par, args.in_flight_steps, local_rank, rays_per_step, pmc if fresh(pmc) else None,
                                                     n_simd, clock_hz)
-    ds.close()
-    if not args.no_extras:
-        result["extra"] = extra_rows(local_rank)
-        result["boundary"] = boundary_rows(flat, local_rank, rays_per_step)
-    if not args.no_cpu_baseline:
-        result["cpu_baseline"] = cpu_baseline(flat)
-    emit(result, compact_single(result))
 
 
 # ---------------------------------------------------------------------------------------------------------------------------
@@ -1639,7 +1672,17 @@ def main():
     ap.add_argument("--in-flight-steps", type=int, default=100,
                     help="N=1: frames per in-flight row (few against the headline's launches: rocprofv3's average of the headline "
                          "kernel over the whole command stays that of launches run back to back)")
+    ap.add_argument("--full", action="store_true",
+                    help="N=1: besides the headline also measure and check everything else (repeats, oracle parity, kernel times, "
+                         "roofline, dome-shortcut and in-flight rows, the other configurations, the CPU baseline); the --no-* and "
+                         "--headline-only options trim this")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="N=1: write the frame the last timed step computed to DIR/image.npy (float32 [H, W, 3])")
     args = ap.parse_args()
+    if args.steps is not None and args.steps < 1:
+        ap.error("--steps must be >= 1")
+    if args.dump_outputs and args.gpus > 1:
+        ap.error("--dump-outputs is available with --gpus 1 only")
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         return launch_ranks(args, sys.argv[1:])

@@ -578,6 +578,26 @@ def g10_postprocess():
     save("g10_postprocess", **out)
 
 
+IMAGETRACER_CAMERAS = ("perspective", "orthogonal")
+
+
+def g11_imagetracer():
+    """The reference's ImageTracer with a plain function of the ray (no renderer): the frames
+    tests/test_tracer_host.py's host loop must reproduce, 6x4, aspect 1.5, PCG(11, 3), S = 0 and 2."""
+    def func(ray):
+        p = ray.at(1.25)
+        return Color(p.x * 0.5 + 1.0, abs(p.y), p.z * p.z)
+
+    out = {}
+    for name in IMAGETRACER_CAMERAS:
+        for S in (0, 2):
+            camera = (PerspectiveCamera(aspect_ratio=1.5, transformation=rotation_z(20.0) * translation(Vec(-1.0, 0.5, 0.2)))
+                      if name == "perspective" else OrthogonalCamera(aspect_ratio=1.5))
+            img = HdrImage(6, 4)
+            ImageTracer(img, camera, samples_per_side=S, pcg=PCG(11, 3)).fire_all_rays(func)
+            out[f"{name}_s{S}"] = pixels_array(img)
+    save("g11_imagetracer", **out)
+
 
 if __name__ == "__main__":
     argv = sys.argv[1:]
@@ -588,7 +608,7 @@ if __name__ == "__main__":
         del argv[at:at + 2]
     table = {"g1": g1_pcg, "g2": g2_xform, "g3": g3_shapes, "g4": g4_camera, "g6": g6_g7_scatter_onb,
              "g8": g8_pigments, "g9": g9_furnace, "g5": g5_frames, "g10": g10_postprocess, "g5c4": g5_c4,
-             "g5cli": g5_cli, "g5seq": g5_seq, "g5sample": g5_sample}
+             "g5cli": g5_cli, "g5seq": g5_seq, "g5sample": g5_sample, "g11": g11_imagetracer}
     if argv:
         parses = sum(1 for k in argv if k in ("g5", "g5cli", "g5seq", "g5sample"))
         if parses > 1:
@@ -598,6 +618,6 @@ if __name__ == "__main__":
     else:
         import subprocess
 
-        for k in ["g1", "g2", "g3", "g4", "g6", "g8", "g9", "g5", "g10", "g5cli", "g5c4", "g5seq", "g5sample"]:  # (g10 reads g5's frames)
+        for k in ["g1", "g2", "g3", "g4", "g6", "g8", "g9", "g5", "g10", "g5cli", "g5c4", "g5seq", "g5sample", "g11"]:  # (g10 reads g5's frames)
             subprocess.run([sys.executable, os.path.abspath(__file__), "--out", OUT_DIR, k], check=True,
                            env=dict(os.environ, PYTHONDONTWRITEBYTECODE="1"))

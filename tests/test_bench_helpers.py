@@ -223,3 +223,18 @@ def test_a_phase_that_overruns_ends_the_job_with_the_line_measured_so_far(tmp_pa
     with pytest.raises(Left):
         dog3.bail("phase 'x': the ranks' agreement failed")
     assert left == [1, 0, 0] and capsys.readouterr().out == ""
+
+
+def test_dump_outputs_writes_the_timed_frame_as_float32(tmp_path):
+    """--dump-outputs DIR: the frame the last timed step left in HBM, as a caller receives it -> DIR/image.npy (fp32, whole)."""
+    import numpy as np
+    import pytest
+    import torch
+
+    b = _bench()
+    frame = torch.linspace(-1.0, 2.0, 4 * 5 * 3, dtype=torch.float32).reshape(4, 5, 3)
+    got = b.dump_outputs(str(tmp_path / "out"), frame)
+    arr = np.load(tmp_path / "out" / "image.npy")
+    assert got == {"image": [4, 5, 3]} and arr.dtype == np.float32 and arr.tobytes() == frame.numpy().tobytes()
+    with pytest.raises(RuntimeError):
+        b.dump_outputs(str(tmp_path / "f64"), frame.double())  # not the headline's fp32 output format: refused, not converted

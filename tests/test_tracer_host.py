@@ -116,6 +116,31 @@ def test_renderer_never_falls_back_to_the_host_loop():
         GpuImageTracer(hm.HdrImage(2, 2), hm.OrthogonalCamera()).fire_all_rays(hm.FlatRenderer(w))
 
 
+@pytest.mark.parametrize("S", [0, 2])
+@pytest.mark.parametrize("camera", ["perspective", "orthogonal"])
+def test_host_loop_equals_the_reference_imagetracers_recorded_frames(camera, S):
+    """The host loop with this repository's classes against the frames the reference's ``ImageTracer`` computed for the same
+    cameras, generator and function of the ray (tests/golden/g11_imagetracer.npz, tests/golden/make_golden.py g11): the same
+    rays in the same order, pixel for pixel."""
+    import numpy as np
+
+    want = np.load(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "g11_imagetracer.npz"))[f"{camera}_s{S}"]
+    cam = (hm.PerspectiveCamera(aspect_ratio=1.5, transformation=hm.rotation_z(20.0) * hm.translation(hm.Vec(-1.0, 0.5, 0.2)))
+           if camera == "perspective" else hm.OrthogonalCamera(aspect_ratio=1.5))
+
+    def func(ray):
+        p = ray.at(1.25)
+        return hm.Color(p.x * 0.5 + 1.0, abs(p.y), p.z * p.z)
+
+    image = hm.HdrImage(6, 4)
+    calls = []
+    GpuImageTracer(image, cam, samples_per_side=S, pcg=hm.PCG(11, 3)).fire_all_rays(func, callback=lambda col, row: calls.append((col, row)))
+    assert calls == [(0, 0)]
+    got = np.array([[[image.get_pixel(col, row).r, image.get_pixel(col, row).g, image.get_pixel(col, row).b]
+                     for col in range(image.width)] for row in range(image.height)])
+    assert got.shape == want.shape and got.tobytes() == want.tobytes()
+
+
 # ---- against the reference's own classes (build container only; the reference never travels) --------------------
 REF_SRC = "/root/reference/src"
 

@@ -2,8 +2,8 @@
 # The ONE parametrised runner for a GPU box (gpurun -- 'bash tools/gpu_run.sh STEP [STEP ...]'): each step writes its log under
 # gpurun_out/<tag>/ and the steps are chained with && semantics (set -e: a failed or killed GPU step starts no further one).
 #   tests[:EXPR]      python -m pytest tests -m gpu -x -q [-k EXPR]
-#   bench             the driver's command: python bench.py (N = 1), line -> bench.json, detail -> bench_detail.json
-#   bench20           python bench.py --steps 20 --warmup 5 (the driver's K)
+#   bench             python bench.py --full (N = 1: the headline and every side row), line -> bench.json, detail -> bench_detail.json
+#   bench20           python bench.py --steps 20 --warmup 5 (a plain run: the headline alone)
 #   prof[:MODE]       tools/prof_bench.sh <tag> [trace-only | c2-only]: kernel trace + PMC passes -> pmc_*.json
 #   gloo2[:FAIL]      PT_DIST_BACKEND=gloo python bench.py --gpus 2 --steps 4 --warmup 2 (two ranks share the card);
 #                     FAIL = "timed sparse:raise" | "timed sparse:hang" rehearses the fallback paths (PT_BENCH_FAIL)
@@ -30,7 +30,7 @@ for step in "$@"; do
       else timeout -k 10 1100 python3 -m pytest tests -m gpu -x -q > $OUT/tests.log 2>&1 || { tail -30 $OUT/tests.log; exit 1; }; fi
       tail -3 $OUT/tests.log ;;
     bench)
-      timeout -k 10 600 python3 bench.py > $OUT/bench.json 2> $OUT/bench.err || { tail -5 $OUT/bench.err; exit 1; }
+      timeout -k 10 600 python3 bench.py --full > $OUT/bench.json 2> $OUT/bench.err || { tail -5 $OUT/bench.err; exit 1; }
       cp bench_detail.json $OUT/bench_detail.json; tail -c 4200 $OUT/bench.json ;;
     bench20)
       timeout -k 10 600 python3 bench.py --steps 20 --warmup 5 > $OUT/bench20.json 2> $OUT/bench20.err || { tail -5 $OUT/bench20.err; exit 1; }

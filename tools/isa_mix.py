@@ -82,7 +82,8 @@ def classify(mn):
                 lo, hi = cyc if isinstance(cyc, tuple) else (cyc, cyc)
                 return "valu", cls, (lo, hi), ctr
         return "valu", "unknown:" + mn, (2, 16), None
-    if mn.startswith(("s_load", "s_buffer_load", "s_store", "s_buffer_store", "s_dcache", "s_memtime", "s_memrealtime", "s_atc_probe")):
+    # (scalar memory: the kernels hold scalar LOADS only -- the project writes memory with vector instructions alone)
+    if mn.startswith(("s_load", "s_buffer_load", "s_memtime", "s_memrealtime", "s_atc_probe")):
         return "smem", "smem", (0, 0), None
     if mn.startswith(("s_cbranch", "s_branch", "s_setpc", "s_swappc", "s_call")):
         return "branch", "branch", (0, 0), None
