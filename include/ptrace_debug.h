@@ -85,7 +85,8 @@ int pt_debug_plan(const pt_scene_desc *desc, const pt_camera *cam, const pt_para
 int pt_debug_plan_scene(pt_scene *scene, const pt_camera *cam, const pt_params *params, pt_plan_info *out);
 /* One of the debug / measurement switches (csrc/pt_plan.h: PT_TUNING_TABLE; by field name or by its PTRACE_* environment
  * name).  The table is read from the environment when the library first needs it; this changes it afterwards, also between
- * scenes of one process.  None changes a pixel.  Returns PT_ERR_INVALID for an unknown name. */
+ * scenes of one process.  None changes a pixel.  Returns PT_ERR_INVALID for an unknown name.  grid_density
+ * (PTRACE_GRID_DENSITY, cells per sphere of the uniform grid) is taken here too, in whole numbers. */
 int pt_debug_set_tuning(const char *name, long long value);
 int pt_debug_get_tuning(const char *name, long long *value);
 

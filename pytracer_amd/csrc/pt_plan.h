@@ -10,8 +10,8 @@
 // in ONE table (PtTuning: read from the environment once, settable through pt_debug_set_tuning -- also between scenes of
 // one process, which the function-local statics could not).
 //
-// Nothing here changes a pixel: every kernel a plan can name renders the same image (tests/test_gpu_parity.py runs the
-// forced variants against the oracle).
+// Nothing here changes a pixel: every kernel a plan can name renders the same image (tests/variant_catalog.py holds a case
+// for each name and each switch of the table; tests/test_gpu_variants.py renders them against the oracle).
 #pragma once
 #include <algorithm>
 #include <cstdio>

@@ -1975,6 +1975,11 @@ extern "C" int pt_debug_plan_scene(pt_scene *s, const pt_camera *cam, const pt_p
 }
 
 extern "C" int pt_debug_set_tuning(const char *name, long long value) {
+  if (name && (strcmp(name, "grid_density") == 0 || strcmp(name, "PTRACE_GRID_DENSITY") == 0)) {  // (cells per sphere: whole numbers here)
+    if (value <= 0) return fail(PT_ERR_INVALID, "grid_density must be positive");
+    pt_tuning().grid_density = (double)value;
+    return PT_OK;
+  }
   if (!name || !pt_tuning_set(pt_tuning(), name, value)) return fail(PT_ERR_INVALID, "unknown tuning switch %s", name ? name : "(null)");
   return PT_OK;
 }
@@ -1989,6 +1994,10 @@ extern "C" int pt_debug_get_tuning(const char *name, long long *value) {
   }
   PT_TUNING_TABLE(X)
 #undef X
+  if (strcmp(name, "grid_density") == 0 || strcmp(name, "PTRACE_GRID_DENSITY") == 0) {
+    *value = (long long)t.grid_density;
+    return PT_OK;
+  }
   return fail(PT_ERR_INVALID, "unknown tuning switch %s", name);
 }
 
