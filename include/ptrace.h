@@ -244,7 +244,11 @@ int pt_image_average_luminosity(int device, const void *img_dev, int fmt, int wi
                                 double *out, void *stream);
 /* normalize_image (x * scale, scale = factor / luminosity; hdrimages.py:130-140), optionally clamp_image
  * (x / (1 + x); :142-146), optionally written back in place, optionally the LDR bytes of write_ldr_image
- * (int(255 * pow(x, 1/gamma)); :160-166) into rgb8_dev (W*H*3 bytes, row 0 on top; may be NULL). */
+ * (int(255 * pow(x, 1/gamma)); :160-166) into rgb8_dev (W*H*3 bytes, row 0 on top; may be NULL).
+ * Values beyond the byte range saturate (255 * pow(..) >= 255 -> 255, <= 0 -> 0, NaN -> 0): the product is clamped as a
+ * double before it is converted.  The reference's int() has no such case: PIL rejects them.
+ * The arithmetic is fp64 for both formats; on PT_OUT_F32 the write-back rounds to float while the bytes of the same call
+ * come from the unrounded fp64 value.  gamma <= 0 with rgb8_dev: PT_ERR_INVALID, the image untouched. */
 int pt_image_tonemap(int device, void *img_dev, int fmt, int width, int height, double scale, int clamp,
                      double gamma, unsigned char *rgb8_dev, int write_back, void *stream);
 /* ---- a rank's shard in sparse form, for the gather of a sharded frame (the reference has no multi-GPU

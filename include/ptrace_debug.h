@@ -15,7 +15,8 @@ extern "C" {
 #endif
 
 /* Elementwise device primitives (op 0 sqrt, 1 x/y, 2 sin, 3 cos, 4 atan2(x, y), 5 acos, 6 floor, 7 x*y+x unfused,
- * 8/9 PCG outputs / floats, 10 pcg_advance == n steps): IEEE exactness and ulp distance to libm. */
+ * 8/9 PCG outputs / floats, 10 pcg_advance == n steps, 11 sincos mismatches, 12 log10, 13 pow(x, y)): IEEE exactness and
+ * ulp distance to libm. */
 int pt_debug_probe(int op, const double *x, const double *y, double *out, int n);
 
 /* keep[i] (World.shapes index): does the conservative cull of the primary rays through the image rectangle

@@ -839,8 +839,11 @@ void pto_tonemap(double *img, long long n, double scale, int clamp, double gamma
     if (clamp) x = x / (1 + x);
     if (write_back) img[i] = x;
     if (rgb8) {
-      int b = (int)(255 * pow(x, 1 / gamma));
-      rgb8[i] = (unsigned char)(b < 0 ? 0 : (b > 255 ? 255 : b));
+      /* beyond the byte range (int)v is undefined in C: saturate as a double first, NaN -> 0.  The reference's int() has
+       * no such case (PIL rejects those values); in range nothing changes. */
+      const double v = 255 * pow(x, 1 / gamma);
+      const double c = v >= 255.0 ? 255.0 : (v > 0.0 ? v : 0.0);
+      rgb8[i] = (unsigned char)(int)c;
     }
   }
 }

@@ -64,6 +64,9 @@ __global__ void pt_post_sum_kernel(const double *partials, int n, double *out) {
 }
 
 // normalize + clamp (+ LDR bytes): x' = x*scale; x'' = x'/(1+x'); byte = int(255 * pow(x'', 1/gamma))
+// All of it in fp64 whatever the image's type: on an fp32 image the write-back rounds x'' to float, the byte is that of the
+// UNROUNDED fp64 x'' (one fused pass and the two-step write-back-then-bytes may so differ by a step on fp32, never on fp64).
+// 255 * pow(..) beyond the byte range saturates as a double BEFORE the conversion (NaN -> 0): (int)v is undefined there.
 __global__ void pt_post_tonemap_kernel(void *img, int f32, long long n, double scale, int do_clamp, double inv_gamma,
                                        unsigned char *rgb8, int write_back) {
   for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long long)gridDim.x * blockDim.x) {
@@ -76,10 +79,11 @@ __global__ void pt_post_tonemap_kernel(void *img, int f32, long long n, double s
         ((double *)img)[i] = x;
     }
     if (rgb8) {
-      const double v = 255 * pow(x, inv_gamma);
-      int b = (int)v;  // int() truncates toward zero
-      b = b < 0 ? 0 : (b > 255 ? 255 : b);
-      rgb8[i] = (unsigned char)b;
+      // gamma 1.0: x itself.  ocml's pow(x, 1.0) is within its ulp or so of x but not always x, which on a truncation
+      // step (x = k/255) costs a whole byte; the reference's x ** 1.0 (libm) is x.  (inv_gamma is uniform: no divergence)
+      const double v = 255 * (inv_gamma == 1.0 ? x : pow(x, inv_gamma));
+      const double c = v >= 255.0 ? 255.0 : (v > 0.0 ? v : 0.0);  // (NaN fails both compares: 0)
+      rgb8[i] = (unsigned char)(int)c;  // int() truncates toward zero
     }
   }
 }

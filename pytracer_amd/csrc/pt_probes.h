@@ -154,6 +154,8 @@ __global__ void pt_probe_kernel(int op, const double *x, const double *y, double
       r = (double)bad;
       break;
     }
+    case 12: r = log10(x[i]); break;      // pt_post_loglum_kernel's term
+    case 13: r = pow(x[i], y[i]); break;  // pt_post_tonemap_kernel's pow(x, 1/gamma)
     default: break;
   }
   out[i] = r;
