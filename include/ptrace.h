@@ -156,6 +156,7 @@ typedef struct pt_stats {
 #define PT_KERNEL_PATH 4         /* path tracer, one queue over all pixels                                        */
 #define PT_KERNEL_PATH_REGIONS 5 /* path tracer in two passes: tile classification, then work units over regions */
 #define PT_KERNEL_PATH_TREE 6    /* ... num_of_rays > 1: second pass with one pixel per wave, a node's children on lanes */
+#define PT_KERNEL_HITS 7         /* pt_render_hits: 8x8 tiles with culled shape lists, first-hit records instead of colours */
 
 typedef struct pt_scene pt_scene; /* opaque: device-resident scene + workspace */
 
@@ -213,6 +214,38 @@ int pt_render_device(pt_scene *scene, const pt_camera *cam, const pt_params *p, 
                      size_t out_bytes, void *stream);
 /* Statistics of the last completed pt_render / synchronised pt_render_device on this scene. */
 int pt_get_stats(pt_scene *scene, pt_stats *out);
+/* ---- hit-record frames (ABI 1.6) ---------------------------------------------------------------------
+ * What World.ray_intersection (world.py:51-69) returns for EVERY primary ray ImageTracer.fire_all_rays fires
+ * (imagetracer.py:60-110), left in HBM or copied to the host: the first half of any renderer a user writes
+ * (`hit = self.world.ray_intersection(ray)`, render.py:52, 65, 103, 158), and the usual auxiliary buffers
+ * (depth, normal, uv, object id).  `channels` is an OR of: */
+#define PT_HIT_T       1   /* 1 plane : HitRecord.t (hitrecord.py:44)                 (+inf where nothing was hit) */
+#define PT_HIT_POINT   2   /* 3 planes: HitRecord.world_point (hitrecord.py:41)                                    */
+#define PT_HIT_NORMAL  4   /* 3 planes: HitRecord.normal as World.ray_intersection leaves it (world.py:66-68)      */
+#define PT_HIT_UV      8   /* 2 planes: HitRecord.surface_point (hitrecord.py:43; shapes.py:36-42, 183-184)        */
+#define PT_HIT_RAY    16   /* 6 planes: origin, dir of the primary ray (imagetracer.py:48-58)                      */
+#define PT_HIT_ALL    31
+/* The shape plane (int32, index into World.shapes, -1 = no hit) is always written, first.
+ * Layout: planar, every plane [nsamp][rows_for_rank][W] with nsamp = max(S, 1)^2 and sample k = sub_row * S + sub_col
+ * (the order of imagetracer.py:86-87); the shape plane as int32, padded to a multiple of 8 bytes, then the selected
+ * fp64 planes in the order of the bits above, components x, y, z (u, v).  On a miss the shape is -1, t is +inf,
+ * every other selected value 0.0; the RAY planes are written for every sample.  A channel that is not selected
+ * costs no stores (and UV, for spheres, no atan2 / acos).
+ * Of pt_params the call reads width, height, samples_per_side, the partition (row_block, n_ranks, rank) and pcg_mode
+ * with its seeds (PT_PCG_SEQ: jitter_state / jitter_seq, the stream of the reference's ImageTracer.pcg, each sample
+ * drawing exactly its two jitter numbers; PT_PCG_PIXEL / PT_PCG_SAMPLE: the first two numbers of the pixel's /
+ * sample's generator of path_state / path_seq); renderer, the path tracer's fields and out_format are ignored.
+ * pt_get_stats afterwards: n_rays = n_pixels * nsamp, n_rays_resolved = 0 (a record needs its point: every ray is
+ * traced), kernel = PT_KERNEL_HITS.  Unknown channel bits: PT_ERR_INVALID (pt_hits_bytes: 0). */
+size_t pt_hits_bytes(const pt_params *p, int channels);
+/* Byte offset of a plane in that buffer: `channel` one of PT_HIT_* (0: the shape plane), `component` 0 .. planes - 1.
+ * < 0: the channel is not selected (or no such channel / component). */
+long long pt_hits_plane_offset(const pt_params *p, int channels, int channel, int component);
+/* As pt_render / pt_render_device: kernel + D2H into a HOST buffer; or into a DEVICE buffer on `stream`. */
+int pt_render_hits(pt_scene *scene, const pt_camera *cam, const pt_params *p, int channels, void *out_host,
+                   size_t out_bytes);
+int pt_render_hits_device(pt_scene *scene, const pt_camera *cam, const pt_params *p, int channels, void *out_dev,
+                          size_t out_bytes, void *stream);
 /* Enable (1) / disable (0) the in-kernel ray counter (default on). */
 int pt_set_count_rays(pt_scene *scene, int enable);
 /* Measurement switch: 0 = primary rays are always generated and traced, also where the image can only show
@@ -281,9 +314,9 @@ int pt_last_error(char *buf, size_t n);
  * (pytracer_amd.prefer_device_kernargs(), the `render` command and bench.py do).  A value set after the runtime came up
  * is reported here but has no effect. */
 int pt_device_kernargs(void);
-/* Library/ABI version: (major<<16)|minor; this header describes 1.5.  The minor grows whenever a struct here grows or an
+/* Library/ABI version: (major<<16)|minor; this header describes 1.6.  The minor grows whenever a struct here grows or an
  * entry point is added (1.2: pt_stats gained `kernel` and `_reserved` -- 56 bytes, which pt_get_stats writes in full --,
- * pt_scene_clone, pt_image_sparse_*; 1.3: PT_PCG_SEQ on the device for OnOff / Flat / PointLight; 1.4: pt_device_kernargs, no load-time setenv; 1.5: pt_device_alloc / _free / _download, pt_stream_create / _sync / _destroy): a caller built
+ * pt_scene_clone, pt_image_sparse_*; 1.3: PT_PCG_SEQ on the device for OnOff / Flat / PointLight; 1.4: pt_device_kernargs, no load-time setenv; 1.5: pt_device_alloc / _free / _download, pt_stream_create / _sync / _destroy; 1.6: pt_hits_bytes, pt_hits_plane_offset, pt_render_hits, pt_render_hits_device): a caller built
  * against an older header must check pt_version() before it hands pt_get_stats its smaller struct. */
 int pt_version(void);
 

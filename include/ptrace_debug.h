@@ -84,6 +84,12 @@ int pt_debug_plan(const pt_scene_desc *desc, const pt_camera *cam, const pt_para
                   pt_plan_info *out);
 /* The plan a handle's next frame follows (its own n_cu and switches). */
 int pt_debug_plan_scene(pt_scene *scene, const pt_camera *cam, const pt_params *params, pt_plan_info *out);
+/* ... and what pt_render_hits / pt_render_hits_device will launch (csrc/pt_hits_plan.h): pre_kernel, main_kernel, grid, lds_main,
+ * hier, ortho and kernel (PT_KERNEL_HITS) are filled, the path tracer's fields stay 0.  The culling mode follows the scene
+ * facts the 8x8 tile kernel's follows: plain, cell lists for worlds of more than 256 shapes, the beam of an orthogonal camera;
+ * the switch cull = 0 names the form without culling. */
+int pt_debug_plan_hits(const pt_scene_desc *desc, const pt_camera *cam, const pt_params *params, int channels, int n_cu,
+                       pt_plan_info *out);
 /* One of the debug / measurement switches (csrc/pt_plan.h: PT_TUNING_TABLE; by field name or by its PTRACE_* environment
  * name).  The table is read from the environment when the library first needs it; this changes it afterwards, also between
  * scenes of one process.  None changes a pixel.  Returns PT_ERR_INVALID for an unknown name.  grid_density

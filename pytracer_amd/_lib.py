@@ -16,19 +16,20 @@ EXPORTS = ("pt_device_count", "pt_scene_upload", "pt_scene_clone", "pt_scene_fre
            "pt_version", "pt_profile_begin", "pt_profile_end", "pt_set_timing", "pt_image_pack_pfm",
            "pt_image_average_luminosity", "pt_image_tonemap", "pt_host_alloc", "pt_host_free", "pt_set_dome_shortcut", "pt_device_info",
            "pt_image_sparse_fixed_bytes", "pt_image_sparse_encode", "pt_image_sparse_decode", "pt_image_sparse_decode_many", "pt_device_kernargs",
-           "pt_device_alloc", "pt_device_free", "pt_device_download", "pt_stream_create", "pt_stream_sync", "pt_stream_destroy")
+           "pt_device_alloc", "pt_device_free", "pt_device_download", "pt_stream_create", "pt_stream_sync", "pt_stream_destroy",
+           "pt_hits_bytes", "pt_hits_plane_offset", "pt_render_hits", "pt_render_hits_device")
 
 
 # every symbol include/ptrace_debug.h declares for ordinary builds (diagnostics: not part of the boundary)
 DEBUG_EXPORTS = ("pt_debug_probe", "pt_debug_cull_probe", "pt_debug_hit_probe", "pt_debug_lanes_probe",
                  "pt_debug_camera_probe", "pt_debug_scatter_probe", "pt_debug_read_queue", "pt_debug_plan", "pt_debug_plan_scene",
-                 "pt_debug_set_tuning", "pt_debug_get_tuning", "pt_debug_handed_over")
+                 "pt_debug_set_tuning", "pt_debug_get_tuning", "pt_debug_handed_over", "pt_debug_plan_hits")
 
 
 # include/ptrace.h: pt_version() = major << 16 | minor; abi.Stats mirrors the 56-byte pt_stats of minor >= 2, the tracer's
 # default alignment needs the PT_PCG_SEQ of minor >= 3, device.device_kernargs() the entry point of minor 4
-# ... devmem.DeviceBuffer / Stream the entry points of minor 5
-ABI_MAJOR, ABI_MINOR_NEEDED = 1, 5
+# ... devmem.DeviceBuffer / Stream the entry points of minor 5, hits.HitFrame those of minor 6
+ABI_MAJOR, ABI_MINOR_NEEDED = 1, 6
 
 
 class PtraceError(RuntimeError):
@@ -165,6 +166,14 @@ def lib():
         L.pt_stream_sync.argtypes = [C.c_int, C.c_void_p]
         L.pt_stream_destroy.restype = C.c_int
         L.pt_stream_destroy.argtypes = [C.c_int, C.c_void_p]
+        L.pt_hits_bytes.restype = C.c_size_t
+        L.pt_hits_bytes.argtypes = [P(abi.Params), C.c_int]
+        L.pt_hits_plane_offset.restype = C.c_longlong
+        L.pt_hits_plane_offset.argtypes = [P(abi.Params), C.c_int, C.c_int, C.c_int]
+        L.pt_render_hits.restype = C.c_int
+        L.pt_render_hits.argtypes = [C.c_void_p, P(abi.Camera), P(abi.Params), C.c_int, C.c_void_p, C.c_size_t]
+        L.pt_render_hits_device.restype = C.c_int
+        L.pt_render_hits_device.argtypes = [C.c_void_p, P(abi.Camera), P(abi.Params), C.c_int, C.c_void_p, C.c_size_t, C.c_void_p]
         # diagnostics (include/ptrace_debug.h): bound when the build carries them -- a renderer never needs one
         if hasattr(L, "pt_debug_cull_probe"):
             L.pt_debug_cull_probe.restype = C.c_int
@@ -193,6 +202,9 @@ def lib():
             L.pt_debug_set_tuning.argtypes = [C.c_char_p, C.c_longlong]
             L.pt_debug_get_tuning.restype = C.c_int
             L.pt_debug_get_tuning.argtypes = [C.c_char_p, P(C.c_longlong)]
+        if hasattr(L, "pt_debug_plan_hits"):
+            L.pt_debug_plan_hits.restype = C.c_int
+            L.pt_debug_plan_hits.argtypes = [P(abi.SceneDesc), P(abi.Camera), P(abi.Params), C.c_int, C.c_int, P(abi.PlanInfo)]
         if hasattr(L, "pt_debug_handed_over"):
             L.pt_debug_handed_over.restype = C.c_int
             L.pt_debug_handed_over.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]

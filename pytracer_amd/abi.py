@@ -22,6 +22,12 @@ OUT_F64, OUT_F32 = 0, 1
 
 PT_OK = 0
 KERNEL_NONE, KERNEL_SIMPLE, KERNEL_TILE, KERNEL_TILE4, KERNEL_PATH, KERNEL_PATH_REGIONS, KERNEL_PATH_TREE = range(7)
+KERNEL_HITS = 7
+# hit-record frames (ptrace.h, ABI 1.6): channel bits, their planes, the names the CLI and hit shaders use
+HIT_T, HIT_POINT, HIT_NORMAL, HIT_UV, HIT_RAY = 1, 2, 4, 8, 16
+HIT_ALL = 31
+HIT_PLANES = {HIT_T: 1, HIT_POINT: 3, HIT_NORMAL: 3, HIT_UV: 2, HIT_RAY: 6}
+HIT_NAMES = {"t": HIT_T, "point": HIT_POINT, "normal": HIT_NORMAL, "uv": HIT_UV, "ray": HIT_RAY, "all": HIT_ALL}
 ERROR_NAMES = {
     -1: "PT_ERR_INVALID",
     -2: "PT_ERR_HIP",
@@ -360,6 +366,49 @@ def copy_params(p: Params, **changes) -> Params:
     for k, v in changes.items():
         setattr(q, k, v)
     return q
+
+
+def hit_channels(channels) -> int:
+    """``PT_HIT_*`` bits from an int, a name (``"normal"``, ``"all"``), a comma-separated string or an iterable of names."""
+    if isinstance(channels, int):
+        bits = channels
+    else:
+        names = channels.split(",") if isinstance(channels, str) else list(channels)
+        bits = 0
+        for name in names:
+            key = str(name).strip().lower()
+            if key not in HIT_NAMES:
+                raise ValueError(f"unknown hit channel {name!r} (have: {', '.join(HIT_NAMES)})")
+            bits |= HIT_NAMES[key]
+    if bits < 0 or bits & ~HIT_ALL:
+        raise ValueError(f"unknown hit channel bits {bits:#x}")
+    return bits
+
+
+def hits_plane_values(p: Params) -> int:
+    """Values per plane of a hit-record frame: ``nsamp * rows_for_rank * W``."""
+    S = int(p.samples_per_side)
+    return (S * S if S > 0 else 1) * len(rows_for_rank(p.height, p.row_block, p.n_ranks, p.rank)) * int(p.width)
+
+
+def hits_bytes(p: Params, channels: int) -> int:
+    """Mirror of ``pt_hits_bytes``: the int32 shape plane padded to 8 bytes, then the selected fp64 planes."""
+    channels = hit_channels(channels)
+    n = hits_plane_values(p)
+    planes = sum(k for bit, k in HIT_PLANES.items() if channels & bit)
+    return ((n * 4 + 7) & ~7) + n * 8 * planes
+
+
+def hits_plane_offset(p: Params, channels: int, channel: int, component: int = 0) -> int:
+    """Mirror of ``pt_hits_plane_offset`` (bytes; ``channel`` 0: the shape plane; < 0: not selected)."""
+    channels = hit_channels(channels)
+    if channel == 0:
+        return 0 if component == 0 else -1
+    if channel not in HIT_PLANES or not channels & channel or not 0 <= component < HIT_PLANES[channel]:
+        return -1
+    n = hits_plane_values(p)
+    before = sum(k for bit, k in HIT_PLANES.items() if bit < channel and channels & bit)
+    return ((n * 4 + 7) & ~7) + n * 8 * (before + component)
 
 
 def rows_for_rank(height: int, row_block: int, n_ranks: int, rank: int) -> List[int]:

@@ -181,4 +181,54 @@ def render(width, height, algorithm, pfm_output, png_output, num_of_rays, max_de
     tracer.close()
 
 
+HIT_CHANNEL_NAMES = ["t", "point", "normal", "uv", "ray", "all"]
+
+
+@click.command("hits")
+@click.option("--width", type=int, default=640, help="Width of the frame")
+@click.option("--height", type=int, default=480, help="Height of the frame")
+@click.option("--channels", type=str, default="all",
+              help="Comma-separated planes to write besides shape_index: " + ", ".join(HIT_CHANNEL_NAMES))
+@click.option("--output", type=str, default="frame.npz", help="Name of the .npz file to create")
+@click.option("--samples-per-pixel", type=int, default=0,
+              help="Samples per pixel (a perfect square; 0: one ray through the pixel centre, no jitter).")
+@click.option("--declare-float", "-d", type=str, multiple=True, help="Declare a variable: --declare-float=VAR:VALUE")
+@click.option("--device", type=int, default=0, help="GPU to render on")
+@click.option("--pcg-mode", type=click.Choice(["auto", "seq", "pixel", "sample"]), default="auto",
+              help="Jitter streams (auto = seq: the reference's own stream PCG(42, 54)).")
+@click.argument("input_scene_name", type=str, default="builtin:demo")
+def hits(width, height, channels, output, samples_per_pixel, declare_float, device, pcg_mode, input_scene_name):
+    """First-hit buffers of a scene: what World.ray_intersection returns for every primary ray, as an .npz of planes
+    [samples, H, W(, components)] -- shape_index (int32, -1 = no hit) and the selected channels."""
+    from . import abi
+
+    try:
+        side = isqrt(samples_per_pixel) if samples_per_pixel >= 0 else -1
+        if side * side != samples_per_pixel:
+            raise UsageError(f"--samples-per-pixel {samples_per_pixel}: must be a perfect square (0, 1, 4, 9, ...)")
+        try:
+            bits = abi.hit_channels(channels)
+        except ValueError as e:
+            raise UsageError(f"--channels: {e}") from None
+        world, camera, _ = _load_scene(input_scene_name, parse_float_overrides(declare_float), width, height)
+    except UsageError as e:
+        click.echo(f"pytracer_amd hits: {e}", err=True)
+        sys.exit(2)
+    import numpy as np
+
+    from . import _lib, prefer_device_kernargs
+
+    prefer_device_kernargs()
+    _lib.standalone()  # (torch-free, like `render`)
+    tracer = GpuImageTracer(image=hm.HdrImage(width, height), camera=camera, samples_per_side=side, device=device,
+                            pcg_mode=pcg_mode)
+    frame = tracer.fire_all_hits(world, bits)
+    st = tracer.last_stats
+    np.savez(output, **frame.planes())
+    click.echo(f"{width}x{height} px, {frame.nsamp} sample(s) per pixel, {len(world.shapes)} shape(s): "
+               f"{st.kernel_ms:.3f} ms in kernels, {st.n_rays} rays; wrote {output} ({', '.join(frame.planes())})")
+    tracer.close()
+
+
 cli.add_command(render)
+cli.add_command(hits)

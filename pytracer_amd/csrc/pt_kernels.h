@@ -21,6 +21,8 @@
 //   pt_tile_kernel        the other OnOff / Flat / PointLight frames and the path tracer's FIRST pass: a wave owns an
 //                         8x8 tile, one pixel per lane, survivor masks in LDS replayed per jitter sample; strips and
 //                         blocks of tiles share a cull; cell lists (pt_cell_kernel) for worlds of > 256 shapes.
+//   pt_hits_kernel        hit-record frames (pt_render_hits): pt_tile_kernel's tiles, culling and query, the closest hit's
+//                         HitRecord stored as planes instead of a colour (pt_hits.h).
 //   pt_path_regions_kernel  the path tracer's second pass for num_of_rays = 1: work units of flagged pixels, a
 //                         pixel's samples spread over lanes, speculated generator states committed in order;
 //                         scattered rays walk per-lane candidate lists (world_query_lanes) or a uniform grid.
@@ -116,6 +118,7 @@ struct Hit {
 #include "pt_camera.h"
 #include "pt_simple.h"
 #include "pt_tile.h"
+#include "pt_hits.h"
 #include "pt_path.h"
 #include "pt_tree.h"
 #include "pt_probes.h"

@@ -21,14 +21,16 @@
 #include "pt_kernels.h"
 #include "pt_layout.h"
 #include "pt_plan.h"
+#include "pt_hits_plan.h"
 #include "pt_post.h"
 
 // major << 16 | minor.  The minor grows whenever a struct of include/ptrace.h grows or an entry point is added (minor 2:
 // pt_stats gained `kernel` + `_reserved`, pt_scene_clone / pt_image_sparse_* arrived; minor 3: PT_PCG_SEQ accepted for
 // OnOff / Flat / PointLight at any samples_per_side; minor 4: pt_device_kernargs, and the library no longer sets
-// HIP_FORCE_DEV_KERNARG when it is loaded; minor 5: pt_device_alloc / pt_device_free / pt_device_download / pt_stream_*);
+// HIP_FORCE_DEV_KERNARG when it is loaded; minor 5: pt_device_alloc / pt_device_free / pt_device_download / pt_stream_*;
+// minor 6: hit-record frames -- pt_hits_bytes / pt_hits_plane_offset / pt_render_hits / pt_render_hits_device);
 // a caller built against an older header checks pt_version() first.
-#define PT_VERSION ((1 << 16) | 5)
+#define PT_VERSION ((1 << 16) | 6)
 
 // (Kernel arguments in device memory -- HIP_FORCE_DEV_KERNARG=1, ~1 us per launch, profiles/r04_dev_kernarg.txt -- are the
 // CALLER's choice: the HIP runtime reads the variable when it initialises, and a library that edited the process environment
@@ -1049,10 +1051,15 @@ static int ensure(T **ptr, size_t *have, size_t need, hipStream_t st) {
 
 // launch() = plan (pt_plan.h: a pure function of the scene's facts, the camera, the parameters and the tuning table) +
 // enqueue (this function: buffers, the argument block, the launches the plan names -- no decision is taken here).
-static int launch(pt_scene *s, const pt_camera *cam, const pt_params *p, void *out_dev, hipStream_t st) {
+// hits_channels >= 0: a hit-record frame (pt_render_hits; pt_hits_plan.h) of those channels instead of the renderer's colours.
+static int launch(pt_scene *s, const pt_camera *cam, const pt_params *p, void *out_dev, hipStream_t st, int hits_channels = -1) {
   const PtTuning &tn = pt_tuning();
   PtPlan pl;
-  pt_make_plan(scene_facts(s), cam, p, tn, pl);
+  bool hits_cull = false;
+  if (hits_channels >= 0)
+    pt_make_hits_plan(scene_facts(s), cam, p, tn, pl, hits_cull);
+  else
+    pt_make_plan(scene_facts(s), cam, p, tn, pl);
 
   PtKArgs a;
   memset(&a, 0, sizeof a);
@@ -1275,7 +1282,26 @@ static int launch(pt_scene *s, const pt_camera *cam, const pt_params *p, void *o
     if (s->queue_parity == 0) s->queue_clean = false;
   }
 #endif
-  if (pl.tile4) {
+  if (hits_channels >= 0) {
+    // pt_hits_kernel<HIER, ORTHO, CULL> (pt_hits.h): the tile kernel's culling modes, or every shape through world_query
+    const size_t lds = hits_cull ? pl.lds_tile : 0;
+    s->stats.lds_bytes = (int)lds;
+    if (hits_cull && pl.hier) {
+      if (pl.cell_chunk_len > PT_CELL_CHUNK) return fail(PT_ERR_INVALID, "internal: cell chunk exceeds its LDS staging");
+      HIP_TRY(hipMemsetAsync(s->cell_count, 0, (size_t)pl.ncells * sizeof(int), st));
+      PT_LAUNCH(pt_cell_kernel, pl.cell_groups * pl.cell_chunks, 0, false, a, pl.cell_chunks, pl.cell_chunk_len);
+    }
+    if (!hits_cull && pl.ortho)
+      PT_LAUNCH((pt_hits_kernel<false, true, false>), pl.grid, lds, true, a, hits_channels);
+    else if (!hits_cull)
+      PT_LAUNCH((pt_hits_kernel<false, false, false>), pl.grid, lds, true, a, hits_channels);
+    else if (pl.tile_mode == PT_TILE_HIER)
+      PT_LAUNCH((pt_hits_kernel<true, false, true>), pl.grid, lds, true, a, hits_channels);
+    else if (pl.tile_mode == PT_TILE_ORTHO)
+      PT_LAUNCH((pt_hits_kernel<false, true, true>), pl.grid, lds, true, a, hits_channels);
+    else
+      PT_LAUNCH((pt_hits_kernel<false, false, true>), pl.grid, lds, true, a, hits_channels);
+  } else if (pl.tile4) {
     // small worlds: the shapes' records ride in LDS for shading (Flat; OnOff reads none of them)
     s->stats.lds_bytes = (int)pl.lds_main;
     const dim3 grid4(pl.grid4_x, pl.grid4_y, 1);
@@ -1537,6 +1563,117 @@ extern "C" int pt_render(pt_scene *s, const pt_camera *cam, const pt_params *p, 
   rc = launch(s, cam, p, s->out_dev, s->stream);
   if (rc) return rc;
   if (need > 0) {
+    HIP_TRY(hipMemcpyAsync(out_host, s->out_dev, need, hipMemcpyDeviceToHost, s->stream));
+    HIP_TRY(hipEventRecord(s->ev2, s->stream));
+    s->pending = true;
+    s->pending_copy = true;
+  }
+  HIP_TRY(hipStreamSynchronize(s->stream));
+  return fold_stats(s);
+}
+
+// ---- hit-record frames (include/ptrace.h, ABI 1.6) -------------------------------------------------------------------
+static int hits_planes_of(int channel) {
+  switch (channel) {
+    case PT_HIT_T: return 1;
+    case PT_HIT_POINT: return 3;
+    case PT_HIT_NORMAL: return 3;
+    case PT_HIT_UV: return 2;
+    case PT_HIT_RAY: return 6;
+    default: return 0;
+  }
+}
+static bool hits_channels_ok(int channels) { return channels >= 0 && (channels & ~PT_HIT_ALL) == 0; }
+// values per plane: nsamp * rows_for_rank * W
+static long long hits_plane_values(const pt_params *p) {
+  if (!p || p->width <= 0 || p->samples_per_side < 0) return 0;
+  const long long S = p->samples_per_side;
+  return (S > 0 ? S * S : 1) * (long long)pt_rows_for_rank(p) * p->width;
+}
+// the fields a hit-record frame does not read, set to values every check accepts
+static pt_params hits_params(const pt_params *p) {
+  pt_params q = *p;
+  q.renderer = PT_RENDERER_FLAT;
+  q.out_format = PT_OUT_F64;
+  q.num_of_rays = 1;
+  q.max_depth = 0;
+  return q;
+}
+
+extern "C" size_t pt_hits_bytes(const pt_params *p, int channels) {
+  if (!p || !hits_channels_ok(channels)) return 0;
+  const long long n = hits_plane_values(p);
+  int planes = 0;
+  for (int bit = 1; bit <= PT_HIT_RAY; bit <<= 1)
+    if (channels & bit) planes += hits_planes_of(bit);
+  return (size_t)((n * 4 + 7) & ~7LL) + (size_t)n * 8 * (size_t)planes;
+}
+
+extern "C" long long pt_hits_plane_offset(const pt_params *p, int channels, int channel, int component) {
+  if (!p || !hits_channels_ok(channels)) return fail(PT_ERR_INVALID, "unknown hit channel bits %#x", channels);
+  if (channel == 0) return component == 0 ? 0 : PT_ERR_INVALID;
+  if (hits_planes_of(channel) == 0 || !(channels & channel) || component < 0 || component >= hits_planes_of(channel))
+    return PT_ERR_INVALID;
+  const long long n = hits_plane_values(p);
+  long long planes = 0;
+  for (int bit = 1; bit < channel; bit <<= 1)
+    if (channels & bit) planes += hits_planes_of(bit);
+  return ((n * 4 + 7) & ~7LL) + n * 8 * (planes + component);
+}
+
+static int hits_check(pt_scene *s, const pt_camera *cam, const pt_params *p, int channels, const void *out, size_t out_bytes,
+                      pt_params &q) {
+  if (!s || !cam || !p) return fail(PT_ERR_INVALID, "null argument");
+  if (!hits_channels_ok(channels)) return fail(PT_ERR_INVALID, "unknown hit channel bits %#x", channels);
+  q = hits_params(p);
+  int rc = check_params(s, cam, &q);
+  if (rc) return rc;
+  const size_t need = pt_hits_bytes(&q, channels);
+  if (out_bytes < need) return fail(PT_ERR_SIZE, "hit-record buffer too small: %zu < %zu bytes", out_bytes, need);
+  if (need > 0 && !out) return fail(PT_ERR_INVALID, "null output buffer");
+  return PT_OK;
+}
+
+extern "C" int pt_render_hits_device(pt_scene *s, const pt_camera *cam, const pt_params *p, int channels, void *out_dev,
+                                     size_t out_bytes, void *stream) {
+  pt_params q;
+  int rc = hits_check(s, cam, p, channels, out_dev, out_bytes, q);
+  if (rc) return rc;
+  HIP_TRY(hipSetDevice(s->device));
+  s->pending = false;  // (as pt_render_device: an unsynchronised earlier render loses its statistics)
+  hipStream_t st = stream ? (hipStream_t)stream : s->stream;
+  rc = launch(s, cam, &q, out_dev, st, channels);
+  if (rc) return rc;
+  if (s->stats.n_pixels > 0) {
+    s->pending = true;
+    s->pending_copy = false;
+  }
+  if (!stream) return pt_sync(s);
+  return PT_OK;
+}
+
+extern "C" int pt_render_hits(pt_scene *s, const pt_camera *cam, const pt_params *p, int channels, void *out_host,
+                              size_t out_bytes) {
+  pt_params q;
+  int rc = hits_check(s, cam, p, channels, out_host, out_bytes, q);
+  if (rc) return rc;
+  const size_t need = pt_hits_bytes(&q, channels);
+  HIP_TRY(hipSetDevice(s->device));
+  if (s->pending) {
+    rc = fold_stats(s);
+    if (rc) return rc;
+  }
+  if (need > s->out_dev_bytes) {
+    if (s->out_dev) HIP_TRY(hipFree(s->out_dev));
+    s->out_dev = nullptr;
+    s->out_dev_bytes = 0;
+    HIP_TRY(hipMalloc(&s->out_dev, need));
+    s->out_dev_bytes = need;
+  }
+  rc = launch(s, cam, &q, s->out_dev, s->stream, channels);
+  if (rc) return rc;
+  if (need > 0) {
+    // (the padding behind the shape plane is the only part no lane writes: the copy carries whatever the buffer held)
     HIP_TRY(hipMemcpyAsync(out_host, s->out_dev, need, hipMemcpyDeviceToHost, s->stream));
     HIP_TRY(hipEventRecord(s->ev2, s->stream));
     s->pending = true;
@@ -1960,6 +2097,32 @@ extern "C" int pt_debug_plan(const pt_scene_desc *desc, const pt_camera *cam, co
   PtPlan pl;
   pt_make_plan(f, cam, p, pt_tuning(), pl);
   plan_info(pl, f, p, out);
+  return PT_OK;
+}
+
+extern "C" int pt_debug_plan_hits(const pt_scene_desc *desc, const pt_camera *cam, const pt_params *p, int channels, int n_cu,
+                                  pt_plan_info *out) {
+  if (!out || !p) return fail(PT_ERR_INVALID, "null argument");
+  if (!hits_channels_ok(channels)) return fail(PT_ERR_INVALID, "unknown hit channel bits %#x", channels);
+  int rc = check_desc(desc);
+  if (rc) return rc;
+  pt_scene tmp;  // (a bag of facts here: no HIP call touches it)
+  HostTables h;
+  analyse_scene(desc, pt_tuning(), &tmp, h);
+  tmp.n_cu = n_cu > 0 ? n_cu : 256;
+  const pt_params q = hits_params(p);
+  rc = check_params(&tmp, cam, &q);
+  if (rc) return rc;
+  const PtSceneFacts f = scene_facts(&tmp);
+  PtPlan pl;
+  bool cull = false;
+  pt_make_hits_plan(f, cam, &q, pt_tuning(), pl, cull);
+  plan_info(pl, f, &q, out);
+  pt_hits_kernel_name(pl, cull, 0, out->pre_kernel, sizeof out->pre_kernel);
+  out->first_kernel[0] = out->alt_kernel[0] = 0;
+  pt_hits_kernel_name(pl, cull, 2, out->main_kernel, sizeof out->main_kernel);
+  out->hier = cull && pl.hier;
+  out->lds_main = cull ? (long long)pl.lds_tile : 0;
   return PT_OK;
 }
 

@@ -128,6 +128,32 @@ class DeviceScene:
         _lib.check(_lib.lib().pt_render_device(self._h, C.byref(cam), C.byref(params), C.c_void_p(dev_ptr),
                                                nbytes, C.c_void_p(stream) if stream else None))
 
+    def render_hits(self, cam: abi.Camera, params: abi.Params, channels=abi.HIT_ALL, pinned: bool = False):
+        """The hit-record frame of ``params`` (``pt_render_hits``: kernel + device->host copy) -> :class:`pytracer_amd.hits.HitFrame`,
+        numpy views over ONE host buffer (page-locked with ``pinned=True``, as :meth:`render`)."""
+        from .hits import HitFrame
+
+        channels = abi.hit_channels(channels)
+        nbytes = int(_lib.lib().pt_hits_bytes(C.byref(params), channels))
+        buf = pinned_empty((nbytes,), np.uint8) if pinned else np.empty((nbytes,), dtype=np.uint8)
+        _lib.check(_lib.lib().pt_render_hits(self._h, C.byref(cam), C.byref(params), channels, buf.ctypes.data_as(C.c_void_p), nbytes))
+        return HitFrame(buf, params, channels)
+
+    def render_hits_into(self, cam: abi.Camera, params: abi.Params, channels, dev_ptr, nbytes: Optional[int] = None,
+                         stream=None) -> None:
+        """The same frame into caller-owned device memory of ``pt_hits_bytes`` bytes on ``stream`` (``pt_render_hits_device``;
+        ``None`` = the library's stream, synchronous).  ``dev_ptr``: a device address, or a
+        :class:`pytracer_amd.devmem.DeviceBuffer` -- which then remembers ``stream``, so that its ``numpy()`` waits for this
+        frame; ``stream``: a ``hipStream_t`` value or a :class:`pytracer_amd.devmem.Stream`.
+        ``HitFrame(buffer.numpy(), params, channels)`` views a download."""
+        handle = getattr(stream, "handle", stream)
+        if getattr(dev_ptr, "is_device_buffer", False):
+            nbytes = dev_ptr.nbytes if nbytes is None else nbytes
+            dev_ptr.rendered_on(stream)
+            dev_ptr = dev_ptr.data_ptr()
+        _lib.check(_lib.lib().pt_render_hits_device(self._h, C.byref(cam), C.byref(params), abi.hit_channels(channels),
+                                                    C.c_void_p(dev_ptr), int(nbytes), C.c_void_p(handle) if handle else None))
+
     def cull_probe(self, cam: abi.Camera, width: int, height: int, x0: int, x1: int, row0: int, row1: int,
                    pixel=None) -> np.ndarray:
         """Diagnostics: which shapes (by ``World.shapes`` index) the conservative cull of the primary rays through
@@ -212,6 +238,15 @@ def plan(flat, cam: abi.Camera, params: abi.Params, n_cu: int = 256, dome_shortc
     info = abi.PlanInfo()
     desc = flat.desc()
     _lib.check(_lib.lib().pt_debug_plan(C.byref(desc), C.byref(cam), C.byref(params), int(n_cu), 1 if dome_shortcut else 0, C.byref(info)))
+    return info
+
+
+def plan_hits(flat, cam: abi.Camera, params: abi.Params, channels=abi.HIT_ALL, n_cu: int = 256) -> abi.PlanInfo:
+    """What ``pt_render_hits`` would launch (``pt_debug_plan_hits``, csrc/pt_hits_plan.h).  Touches no device."""
+    info = abi.PlanInfo()
+    desc = flat.desc()
+    _lib.check(_lib.lib().pt_debug_plan_hits(C.byref(desc), C.byref(cam), C.byref(params), abi.hit_channels(channels), int(n_cu),
+                                             C.byref(info)))
     return info
 
 

@@ -53,16 +53,28 @@ class DeviceBuffer:
         p = C.c_void_p()
         _lib.check(_lib.lib().pt_device_alloc(self.device, self.nbytes, C.byref(p)))
         self._ptr: Optional[int] = p.value
+        self.last_stream = None  # the stream the buffer was last rendered on (see rendered_on)
 
     def data_ptr(self) -> int:
         if self._ptr is None and self.nbytes:
             raise RuntimeError("DeviceBuffer used after free()")
         return self._ptr or 0
 
+    def rendered_on(self, stream) -> "DeviceBuffer":
+        """Note the stream (a :class:`Stream`, a raw ``hipStream_t`` value, or ``None`` for a synchronous call with nothing in
+        flight) a render into this buffer was enqueued on: ``numpy()`` then orders its download behind it by default."""
+        self.last_stream = stream
+        return self
+
     def numpy(self, stream: Optional[Stream] = None) -> np.ndarray:
+        """Copy to the host, ordered behind ``stream`` -- by default the stream the buffer was last rendered on
+        (``rendered_on``), so that a frame still in flight on a caller's stream is complete when this returns."""
+        if stream is None:
+            stream = self.last_stream
+        handle = getattr(stream, "handle", stream)  # (a closed Stream has handle None: nothing of it is in flight)
         out = np.empty(self.shape, dtype=self.dtype)
         _lib.check(_lib.lib().pt_device_download(self.device, out.ctypes.data_as(C.c_void_p), C.c_void_p(self.data_ptr()), self.nbytes,
-                                                 C.c_void_p(stream.handle) if stream is not None else None))
+                                                 C.c_void_p(handle) if handle else None))
         return out
 
     def free(self) -> None:

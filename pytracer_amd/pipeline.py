@@ -42,6 +42,8 @@ class FramePipeline:
         slot = self._next
         self._next = (slot + 1) % len(self.scenes)
         self.scenes[slot].render_into(cam, params, out.data_ptr(), nbytes, self.streams[slot].handle)
+        if getattr(out, "is_device_buffer", False):
+            out.rendered_on(self.streams[slot])  # (its numpy() then waits for this frame by default)
         self._busy[slot] = out
         return slot
 

@@ -11,6 +11,15 @@ What ``func`` may be:
   is rendered on the MI355X.  A renderer whose world the device cannot express (unknown shape / BRDF /
   pigment class, non-affine matrix) raises ``UnsupportedSceneError``: a renderer never silently runs
   anywhere else.
+* a *hit shader* -- an object (usually a callable) that is none of the four renderers and has a ``world`` attribute and a method
+  ``shade_hits(frame) -> [nsamp, H, W, 3]`` (:mod:`pytracer_amd.shaders` has two worked examples): nearly every renderer a
+  user writes starts with ``hit = self.world.ray_intersection(ray)`` and shades from the ``HitRecord``.  That first half --
+  the culled first-hit query over the frame -- runs on the device (``fire_all_hits``: a
+  :class:`pytracer_amd.hits.HitFrame`, the records of every sample of every pixel); ``shade_hits`` is called ONCE with it,
+  and the tracer reduces its samples as imagetracer.py:83-101 does (from 0.0, sample after sample in order, then times
+  ``1 / S**2``).  ``func.hit_channels`` (optional) names the channels it reads.  ``last_path = "device-hits"``.  A world the
+  device cannot express raises ``UnsupportedSceneError``, or with ``fallback="host"`` the shader's own ``__call__`` runs
+  through the host loop below.
 * any other callable ``Ray -> Color`` (the lambdas of the reference's own ``TestImageTracer``,
   test_all.py:576-604): there is nothing to put on a GPU, the contract is "call ``func`` once per
   sample, in the reference's order, and store what it returns".  That per-pixel loop runs on the host
@@ -119,7 +128,7 @@ class GpuImageTracer:
         self.resident = bool(resident)
         self.fallback = fallback
         self.device_image = None   # resident=True: the last frame, in HBM
-        self.last_path = None      # "device" | "host": where the last frame was computed
+        self.last_path = None      # "device" | "device-hits" | "host": where the last frame was computed
         self.image = image
         self.camera = camera
         self.samples_per_side = samples_per_side
@@ -158,6 +167,16 @@ class GpuImageTracer:
                 self.last_path = "device"
             except flatten.UnsupportedSceneError:
                 # (raised while flattening: before anything was rendered or written)
+                if self.fallback != "host" or not callable(func):
+                    raise
+                self.device_image = None
+                self._host_loop(func, callback, callback_time_s, callback_kwargs)
+                self.last_path = "host"
+        elif _is_hit_shader(func):
+            try:
+                self._hit_shader_frame(func, callback, callback_kwargs)
+                self.last_path = "device-hits"
+            except flatten.UnsupportedSceneError:
                 if self.fallback != "host" or not callable(func):
                     raise
                 self.device_image = None
@@ -204,6 +223,67 @@ class GpuImageTracer:
         if self._scene is None:
             self._scene = DeviceScene(flat, self.device)
         return self._scene
+
+    # -- hit-record frames: World.ray_intersection for every primary ray, on the device ---------------------------------
+    def _hits_mode(self) -> int:
+        mode = _PCG_MODES[self.pcg_mode]
+        return abi.PCG_SEQ if mode is None else mode  # "auto": a primary ray draws exactly its two jitter numbers, so "seq" is exact
+
+    def _hits_params(self) -> abi.Params:
+        mode = self._hits_mode()
+        state, seq = flatten.recover_seeds(self.pcg, mode != abi.PCG_SEQ)
+        return abi.make_params(int(self.image.width), int(self.image.height), abi.RENDERER_FLAT,
+                               samples_per_side=int(self.samples_per_side), pcg_mode=mode, jitter_state=state, jitter_seq=seq,
+                               path_state=state, path_seq=seq)
+
+    def _render_hit_frame(self, world, channels: int):
+        """The hit-record frame of this tracer's camera, ``samples_per_side`` and ``pcg`` AS IT STANDS (nothing is advanced
+        here).  The one seam of the hit-shader route: a subclass that overrides it supplies the frame some other way."""
+        params = self._hits_params()
+        cam = flatten.flatten_camera(self.camera)
+        scene = self._device_scene(world)
+        frame = scene.render_hits(cam, params, channels)
+        self.last_stats = scene.stats()
+        self.last_bands = 1
+        return frame
+
+    def _advance_behind_hits(self) -> None:
+        """Behind a ``"seq"`` frame ``tracer.pcg`` stands where the reference's loop leaves it (imagetracer.py:84-101)."""
+        S = int(self.samples_per_side)
+        if self._hits_mode() == abi.PCG_SEQ and S > 0 and hasattr(self.pcg, "state") and hasattr(self.pcg, "inc"):
+            self.pcg.state = pcg_advance(int(self.pcg.state), int(self.pcg.inc),
+                                         2 * int(self.image.width) * int(self.image.height) * S ** 2)
+
+    def fire_all_hits(self, world, channels=abi.HIT_ALL):
+        """``world.ray_intersection(ray)`` for every primary ray ``fire_all_rays`` would fire (every sample of every pixel,
+        jittered from ``self.pcg`` under ``pcg_mode``; ``"auto"`` means ``"seq"``) -> :class:`pytracer_amd.hits.HitFrame`
+        with the selected ``channels`` (``PT_HIT_*`` bits or names: ``"normal,t"``)."""
+        frame = self._render_hit_frame(world, abi.hit_channels(channels))
+        self._advance_behind_hits()
+        self.last_path = "device-hits"
+        return frame
+
+    def _hit_shader_frame(self, func, callback, callback_kwargs) -> None:
+        if callback:
+            callback(col=0, row=0, **callback_kwargs)
+        w, h, S = int(self.image.width), int(self.image.height), int(self.samples_per_side)
+        nsamp = S * S if S > 0 else 1
+        frame = self._render_hit_frame(func.world, abi.hit_channels(getattr(func, "hit_channels", abi.HIT_ALL)))
+        vals = np.asarray(func.shade_hits(frame), dtype=np.float64)
+        if S == 0 and vals.shape == (h, w, 3):
+            vals = vals[None]
+        if vals.shape != (nsamp, h, w, 3):
+            raise ValueError(f"shade_hits must return [nsamp, H, W, 3] = {(nsamp, h, w, 3)}, not {vals.shape}")
+        if S > 0:  # imagetracer.py:83-101: from 0.0, one fp64 addition per sample in k order, then Color * (1 / S**2)
+            cum = np.zeros((h, w, 3), dtype=np.float64)
+            for k in range(nsamp):
+                cum = cum + vals[k]
+            out = cum * (1 / S ** 2)
+        else:
+            out = np.array(vals[0], dtype=np.float64)
+        self._advance_behind_hits()
+        self.device_image = None
+        _fill_image(self.image, out, self.lazy_pixels)
 
     def _device_frame(self, func, callback, callback_time_s, callback_kwargs) -> None:
         last_call_time = perf_counter()
@@ -293,6 +373,12 @@ class GpuImageTracer:
         if self._scene is not None:
             self._scene.close()
             self._scene = None
+
+
+def _is_hit_shader(func) -> bool:
+    """None of the four renderers, with a ``world`` and a ``shade_hits(frame)`` method (usually also a callable
+    ``Ray -> Color``, which ``fallback="host"`` needs; the device route itself never calls it)."""
+    return not flatten.is_device_renderer(func) and hasattr(func, "world") and callable(getattr(func, "shade_hits", None))
 
 
 def _fill_image(image, arr: np.ndarray, lazy: bool = False) -> None:
