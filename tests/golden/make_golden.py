@@ -599,6 +599,65 @@ def g11_imagetracer():
     save("g11_imagetracer", **out)
 
 
+def g12_families():
+    """tests/scene_families.py's recipe built from the REFERENCE's classes (the kit below), one world per family: Flat,
+    PointLight and PathTracer frames of 32x20 rendered by the reference, and for the mirrored and the sheared family a block
+    of ``World.ray_intersection`` hit records like g3's.  One file per family: g12_family_<family>.npz."""
+    from types import SimpleNamespace
+
+    from tests import scene_families as sf
+
+    def image(w, h, rgb):
+        img = HdrImage(w, h)
+        img.pixels = [Color(*c) for c in rgb]
+        return img
+
+    kit = SimpleNamespace(
+        Vec=Vec, Point=Point, Color=Color, translation=translation, scaling=scaling, rotation_x=rotation_x,
+        rotation_y=rotation_y, rotation_z=rotation_z, UniformPigment=UniformPigment, CheckeredPigment=CheckeredPigment,
+        ImagePigment=ImagePigment, DiffuseBRDF=DiffuseBRDF, SpecularBRDF=SpecularBRDF, Material=Material, Sphere=Sphere,
+        Plane=Plane, PointLight=PointLight, World=World, PerspectiveCamera=PerspectiveCamera,
+        OrthogonalCamera=OrthogonalCamera, image=image)
+    w, h = sf.GOLDEN_SIZE
+    for family in sf.FAMILIES:
+        seed = sf.GOLDEN_SEEDS[family]
+        world, camera, _, _ = sf.family_world(family, seed, kit)
+        scene = flatten.flatten_world(world)
+        cam = flatten.flatten_camera(camera)
+        bg, amb = Color(0.1, 0.2, 0.3), Color(0.05, 0.05, 0.1)
+        mode = abi.PCG_PIXEL if seed % 2 else abi.PCG_SAMPLE
+        frames = [
+            (lambda: FlatRenderer(world, background_color=bg), 0, abi.PCG_PIXEL, 42, 54),
+            (lambda: PointLightRenderer(world, background_color=bg, ambient_color=amb), 2, abi.PCG_SEQ, 42, 54),
+            (lambda: PathTracer(world, background_color=bg, pcg=PCG(45 + seed, 54), russian_roulette_limit=seed % 3,
+                                num_of_rays=1 + seed % 3, max_depth=1 + seed % 4), 1, mode, 45 + seed, 54),
+        ]
+        out = {}
+        for k, (make, S, md, s0, q0) in enumerate(frames):
+            par = flatten.renderer_params(make(), w, h, samples_per_side=S, tracer_pcg=PCG(42, 54), pcg_mode=md)
+            if md != abi.PCG_SEQ:
+                par.path_state, par.path_seq = s0, q0
+            out[f"f{k}_pixels"] = render_ref(world, camera, make(), w, h, S, md, s0, q0)
+            out.update({f"f{k}_{name}": v for name, v in params_dict(par).items()})
+        if family in ("mirrored", "sheared"):
+            g = PCG(12, seed)
+            r = g.random_float
+            index_of = {id(s.material): i for i, s in enumerate(world.shapes)}
+            rays, recs = [], []
+            for k in range(300):
+                o = (-3.0 + 4.0 * r(), 4.0 * (r() - 0.5), 2.5 * r())
+                d = (0.2 + r(), 1.6 * (r() - 0.5), 1.2 * (r() - 0.6))
+                tmin = 1e-5 if k % 2 == 0 else 1e-3
+                rays.append(list(o) + list(d) + [tmin, INF])
+                hr = world.ray_intersection(Ray(origin=Point(*o), dir=Vec(*d), tmin=tmin, tmax=INF))
+                recs.append([0.0] * 11 if hr is None else
+                            [1.0, hr.t, hr.world_point.x, hr.world_point.y, hr.world_point.z, hr.normal.x, hr.normal.y,
+                             hr.normal.z, hr.surface_point.u, hr.surface_point.v, float(index_of[id(hr.material)])])
+            out.update(rays=np.array(rays), per_world=np.array(recs))
+        save(f"g12_family_{family}", n_frames=np.array(len(frames)), seed=np.array(seed), **out, **scene.to_dict(),
+             **abi.camera_to_dict(cam))
+
+
 if __name__ == "__main__":
     argv = sys.argv[1:]
     if "--out" in argv:
@@ -608,7 +667,7 @@ if __name__ == "__main__":
         del argv[at:at + 2]
     table = {"g1": g1_pcg, "g2": g2_xform, "g3": g3_shapes, "g4": g4_camera, "g6": g6_g7_scatter_onb,
              "g8": g8_pigments, "g9": g9_furnace, "g5": g5_frames, "g10": g10_postprocess, "g5c4": g5_c4,
-             "g5cli": g5_cli, "g5seq": g5_seq, "g5sample": g5_sample, "g11": g11_imagetracer}
+             "g5cli": g5_cli, "g5seq": g5_seq, "g5sample": g5_sample, "g11": g11_imagetracer, "g12": g12_families}
     if argv:
         parses = sum(1 for k in argv if k in ("g5", "g5cli", "g5seq", "g5sample"))
         if parses > 1:
@@ -618,6 +677,6 @@ if __name__ == "__main__":
     else:
         import subprocess
 
-        for k in ["g1", "g2", "g3", "g4", "g6", "g8", "g9", "g5", "g10", "g5cli", "g5c4", "g5seq", "g5sample", "g11"]:  # (g10 reads g5's frames)
+        for k in ["g1", "g2", "g3", "g4", "g6", "g8", "g9", "g5", "g10", "g5cli", "g5c4", "g5seq", "g5sample", "g11", "g12"]:  # (g10 reads g5's frames)
             subprocess.run([sys.executable, os.path.abspath(__file__), "--out", OUT_DIR, k], check=True,
                            env=dict(os.environ, PYTHONDONTWRITEBYTECODE="1"))

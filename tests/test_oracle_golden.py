@@ -199,6 +199,54 @@ def test_frame_golden(oracle, name):
     assert n_rays >= par.width * par.height * max(1, par.samples_per_side) ** 2
 
 
+# ---- G12: the scene families (tests/scene_families.py) built from the reference's classes -------------------------------
+def _family_fixture(family):
+    from tests import scene_families as sf
+
+    d = util.load("g12_family_" + family)
+    return sf, d, abi.FlatScene.from_dict(d), abi.camera_from_dict(d)
+
+
+@pytest.mark.parametrize("family", ["mirrored", "sheared", "camera", "pigments", "lights", "mixed"])
+def test_family_golden(oracle, family):
+    """Mirrored, sheared and scaled-camera worlds, patterned pigments on every shape, many lights: the oracle equals the
+    reference's own frames bit for bit, and the host-side recipe flattens to the very scene the reference's objects gave."""
+    from pytracer_amd import flatten
+
+    sf, d, scene, cam = _family_fixture(family)
+    assert family in sf.FAMILIES and int(d["seed"]) == sf.GOLDEN_SEEDS[family]
+    world, camera, _, _ = sf.family_world(family, int(d["seed"]))
+    assert flatten.flatten_world(world).same_bits(scene), "hostmodel and the reference's classes flatten differently"
+    mine = flatten.flatten_camera(camera)
+    assert bytes(mine) == bytes(cam)
+    renderers = set()
+    for k in range(int(d["n_frames"])):
+        par = util.params_from({key[len(f"f{k}_"):]: d[key] for key in d.files if key.startswith(f"f{k}_par_")})
+        pixels = d[f"f{k}_pixels"]
+        assert (par.width, par.height) == sf.GOLDEN_SIZE
+        out, n_rays = oracle.render(scene, cam, par, n_threads=0, sqr_mode=oracle.SQR_POW)
+        assert util.bits_equal(out, pixels), f"{family} frame {k} (renderer {par.renderer}): max rel err {util.rel_err(out, pixels).max()}"
+        assert len(np.unique(pixels.reshape(-1, 3), axis=0)) > 8 and n_rays >= par.width * par.height
+        renderers.add(par.renderer)
+    assert renderers == {abi.RENDERER_FLAT, abi.RENDERER_POINTLIGHT, abi.RENDERER_PATHTRACER}
+
+
+@pytest.mark.parametrize("family", ["mirrored", "sheared"])
+def test_family_hit_records_golden(oracle, family):
+    _, d, scene, _ = _family_fixture(family)
+    n_hits, shapes, flipped = 0, set(), 0
+    det = [np.linalg.det(scene.m[:, i].reshape(3, 4)[:, :3]) for i in range(scene.n_shapes)]
+    for ray, exp in zip(d["rays"], d["per_world"]):
+        got = oracle.world_intersect(scene, ray)
+        assert (got is not None) == bool(exp[0])
+        if got is not None:
+            assert util.bits_equal(got[:9], exp[1:10]) and int(got[9]) == int(exp[10])
+            n_hits += 1
+            shapes.add(int(got[9]))
+            flipped += det[int(got[9])] < 0
+    assert n_hits > 200 and len(shapes) >= 10 and (family != "mirrored" or flipped > 50)
+
+
 def test_checksums_match_baseline_md():
     # BASELINE.md §2 checksums, measured by the survey on the reference
     for name, expect in (("g5_demo_onoff_160x120", 44139.0), ("g5_demo_flat_160x120", 19389.899999998433),

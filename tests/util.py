@@ -1,9 +1,11 @@
 """Helpers shared by the tests: golden-fixture loading and tolerance checks."""
+import ctypes as C
 import os
 
 import numpy as np
 
 from pytracer_amd import abi
+from pytracer_amd.hits import HitFrame
 
 GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
 
@@ -56,3 +58,46 @@ def bits_equal_rows(a, b) -> np.ndarray:
     b = np.ascontiguousarray(b, dtype=np.float64)
     a2, b2 = a.reshape(a.shape[0], -1), b.reshape(b.shape[0], -1)
     return (a2.view(np.uint64) == b2.view(np.uint64)).all(axis=1)
+
+
+def oracle_frame(orc, flat, cam, p, channels=abi.HIT_ALL):
+    """``world_intersect(tracer_fire_ray(...))`` for every sample of the rank's rows, the jitter from ``oracle.Pcg`` in the
+    reference's order (imagetracer.py:80-93): SEQ one generator over the whole image in row-major order, PIXEL / SAMPLE the
+    first two numbers of the pixel's / sample's generator (include/ptrace.h)."""
+    L = orc.lib()
+    frame = HitFrame(None, p, channels)
+    frame.shape_index[...] = -1
+    frame.t[...] = np.inf
+    S, W, H = p.samples_per_side, p.width, p.height
+    nsamp = frame.nsamp
+    desc = flat.desc()
+    ray, rec = np.zeros(8), np.zeros(10)
+    pr, po = ray.ctypes.data_as(C.POINTER(C.c_double)), rec.ctypes.data_as(C.POINTER(C.c_double))
+    mine = {g: l for l, g in enumerate(abi.rows_for_rank(H, p.row_block, p.n_ranks, p.rank))}
+    seq = orc.Pcg(p.jitter_state, p.jitter_seq) if p.pcg_mode == abi.PCG_SEQ else None
+    sidx, t, pt, nrm, uv, ro, rd = frame.shape_index, frame.t, frame.point, frame.normal, frame.uv, frame.ray_origin, frame.ray_dir
+    for row in range(H):
+        lrow = mine.get(row)
+        if lrow is None:
+            if seq is not None and S > 0:
+                for _ in range(2 * nsamp * W):
+                    seq.random()
+            continue
+        for col in range(W):
+            i = row * W + col
+            g = seq
+            if S > 0 and p.pcg_mode == abi.PCG_PIXEL:
+                g = orc.Pcg(p.path_state, p.path_seq + i)
+            for k in range(nsamp):
+                up = vp = 0.5
+                if S > 0:
+                    if p.pcg_mode == abi.PCG_SAMPLE:
+                        g = orc.Pcg(p.path_state, p.path_seq + i * nsamp + k)
+                    up = (k % S + g.random_float()) / S
+                    vp = (k // S + g.random_float()) / S
+                L.pto_tracer_fire_ray(C.byref(cam), W, H, col, row, up, vp, pr)
+                ro[k, lrow, col], rd[k, lrow, col] = ray[0:3], ray[3:6]
+                if L.pto_world_intersect(C.byref(desc), pr, po):
+                    sidx[k, lrow, col] = int(rec[9])
+                    t[k, lrow, col], pt[k, lrow, col], nrm[k, lrow, col], uv[k, lrow, col] = rec[0], rec[1:4], rec[4:7], rec[7:9]
+    return frame
