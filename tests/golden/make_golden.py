@@ -658,6 +658,67 @@ def g12_families():
              **abi.camera_to_dict(cam))
 
 
+def g13_planes():
+    """tests/plane_worlds.py's recipe built from the REFERENCE's classes, three worlds: 65 planes around the camera (closed),
+    60 spheres over an open fan of 5 planes under 9 lights, and the constructed world of the coincident pair.  Flat, PointLight
+    and PathTracer (N = 2, D = 2) frames of 24x16 rendered by the reference and 300 ``World.ray_intersection`` records each:
+    g13_planes_<name>.npz."""
+    from types import SimpleNamespace
+
+    from tests import plane_worlds as pw
+
+    def image(w, h, rgb):
+        img = HdrImage(w, h)
+        img.pixels = [Color(*c) for c in rgb]
+        return img
+
+    kit = SimpleNamespace(
+        Vec=Vec, Point=Point, Color=Color, translation=translation, scaling=scaling, rotation_x=rotation_x,
+        rotation_y=rotation_y, rotation_z=rotation_z, UniformPigment=UniformPigment, CheckeredPigment=CheckeredPigment,
+        ImagePigment=ImagePigment, DiffuseBRDF=DiffuseBRDF, SpecularBRDF=SpecularBRDF, Material=Material, Sphere=Sphere,
+        Plane=Plane, PointLight=PointLight, World=World, PerspectiveCamera=PerspectiveCamera,
+        OrthogonalCamera=OrthogonalCamera, image=image)
+    w, h = pw.GOLDEN_SIZE
+    for k_world, (name, case_id) in enumerate(pw.GOLDEN.items()):
+        if case_id is None:
+            world, _ = pw.constructed_world(kit)
+            camera = pw.constructed_cameras((w, h), kit)[0]
+        else:
+            case = pw.BY_ID[case_id]
+            world, _ = pw.case_world(case, kit)
+            camera = pw.case_cameras(case, (w, h), kit)[0]
+        scene = flatten.flatten_world(world)
+        cam = flatten.flatten_camera(camera)
+        bg, amb = Color(0.1, 0.2, 0.3), Color(0.05, 0.05, 0.1)
+        frames = [
+            (lambda: FlatRenderer(world, background_color=bg), 0, abi.PCG_PIXEL, 42, 54),
+            (lambda: PointLightRenderer(world, background_color=bg, ambient_color=amb), 2, abi.PCG_SEQ, 42, 54),
+            (lambda: PathTracer(world, background_color=bg, pcg=PCG(45, 54), russian_roulette_limit=1, num_of_rays=2, max_depth=2),
+             1, abi.PCG_SAMPLE if k_world % 2 else abi.PCG_PIXEL, 45, 54),
+        ]
+        out = {}
+        for k, (make, S, md, s0, q0) in enumerate(frames):
+            par = flatten.renderer_params(make(), w, h, samples_per_side=S, tracer_pcg=PCG(42, 54), pcg_mode=md)
+            if md != abi.PCG_SEQ:
+                par.path_state, par.path_seq = s0, q0
+            out[f"f{k}_pixels"] = render_ref(world, camera, make(), w, h, S, md, s0, q0)
+            out.update({f"f{k}_{key}": v for key, v in params_dict(par).items()})
+        r = PCG(13, k_world).random_float
+        index_of = {id(s.material): i for i, s in enumerate(world.shapes)}
+        rays, recs = [], []
+        for k in range(300):
+            o = (2.0 * (r() - 0.5), 2.0 * (r() - 0.5), 1.6 * (r() - 0.5))
+            d = (2.0 * (r() - 0.3), 2.0 * (r() - 0.5), 2.0 * (r() - 0.5))
+            tmin = 1e-5 if k % 2 == 0 else 1e-3
+            rays.append(list(o) + list(d) + [tmin, INF])
+            hr = world.ray_intersection(Ray(origin=Point(*o), dir=Vec(*d), tmin=tmin, tmax=INF))
+            recs.append([0.0] * 11 if hr is None else
+                        [1.0, hr.t, hr.world_point.x, hr.world_point.y, hr.world_point.z, hr.normal.x, hr.normal.y,
+                         hr.normal.z, hr.surface_point.u, hr.surface_point.v, float(index_of[id(hr.material)])])
+        save(f"g13_planes_{name}", n_frames=np.array(len(frames)), rays=np.array(rays), per_world=np.array(recs), **out,
+             **scene.to_dict(), **abi.camera_to_dict(cam))
+
+
 if __name__ == "__main__":
     argv = sys.argv[1:]
     if "--out" in argv:
@@ -667,7 +728,8 @@ if __name__ == "__main__":
         del argv[at:at + 2]
     table = {"g1": g1_pcg, "g2": g2_xform, "g3": g3_shapes, "g4": g4_camera, "g6": g6_g7_scatter_onb,
              "g8": g8_pigments, "g9": g9_furnace, "g5": g5_frames, "g10": g10_postprocess, "g5c4": g5_c4,
-             "g5cli": g5_cli, "g5seq": g5_seq, "g5sample": g5_sample, "g11": g11_imagetracer, "g12": g12_families}
+             "g5cli": g5_cli, "g5seq": g5_seq, "g5sample": g5_sample, "g11": g11_imagetracer, "g12": g12_families,
+             "g13": g13_planes}
     if argv:
         parses = sum(1 for k in argv if k in ("g5", "g5cli", "g5seq", "g5sample"))
         if parses > 1:
@@ -677,6 +739,6 @@ if __name__ == "__main__":
     else:
         import subprocess
 
-        for k in ["g1", "g2", "g3", "g4", "g6", "g8", "g9", "g5", "g10", "g5cli", "g5c4", "g5seq", "g5sample", "g11", "g12"]:  # (g10 reads g5's frames)
+        for k in ["g1", "g2", "g3", "g4", "g6", "g8", "g9", "g5", "g10", "g5cli", "g5c4", "g5seq", "g5sample", "g11", "g12", "g13"]:  # (g10 reads g5's frames)
             subprocess.run([sys.executable, os.path.abspath(__file__), "--out", OUT_DIR, k], check=True,
                            env=dict(os.environ, PYTHONDONTWRITEBYTECODE="1"))

@@ -247,6 +247,52 @@ def test_family_hit_records_golden(oracle, family):
     assert n_hits > 200 and len(shapes) >= 10 and (family != "mirrored" or flipped > 50)
 
 
+# ---- G13: plane-heavy worlds (tests/plane_worlds.py) built from the reference's classes -----------------------------------
+@pytest.mark.parametrize("name", ["closed", "fan", "coincident"])
+def test_plane_world_golden(oracle, name):
+    """65 planes and no sphere, 60 spheres over a fan of 5 planes under 9 lights, two coincident planes between spheres: the
+    oracle equals the reference's own frames and hit records bit for bit, and the host-side recipe flattens to the very
+    scene the reference's objects gave."""
+    from pytracer_amd import flatten
+    from tests import plane_worlds as pw
+
+    d = util.load("g13_planes_" + name)
+    scene, cam = abi.FlatScene.from_dict(d), abi.camera_from_dict(d)
+    if pw.GOLDEN[name] is None:
+        world, info = pw.constructed_world()
+        camera = pw.constructed_cameras(pw.GOLDEN_SIZE)[0]
+    else:
+        case = pw.BY_ID[pw.GOLDEN[name]]
+        world, _ = pw.case_world(case)
+        camera = pw.case_cameras(case, pw.GOLDEN_SIZE)[0]
+        assert (scene.n_shapes, int((scene.kind == abi.SHAPE_PLANE).sum())) == (case.n_shapes, case.n_planes)
+    assert flatten.flatten_world(world).same_bits(scene), "hostmodel and the reference's classes flatten differently"
+    assert bytes(flatten.flatten_camera(camera)) == bytes(cam)
+    renderers = set()
+    for k in range(int(d["n_frames"])):
+        par = util.params_from({key[len(f"f{k}_"):]: d[key] for key in d.files if key.startswith(f"f{k}_par_")})
+        pixels = d[f"f{k}_pixels"]
+        assert (par.width, par.height) == pw.GOLDEN_SIZE
+        out, n_rays = oracle.render(scene, cam, par, n_threads=0, sqr_mode=oracle.SQR_POW)
+        assert util.bits_equal(out, pixels), f"{name} frame {k} (renderer {par.renderer}): max rel err {util.rel_err(out, pixels).max()}"
+        assert len(np.unique(pixels.reshape(-1, 3), axis=0)) > 8 and n_rays >= par.width * par.height
+        renderers.add(par.renderer)
+    assert renderers == {abi.RENDERER_FLAT, abi.RENDERER_POINTLIGHT, abi.RENDERER_PATHTRACER}
+    n_hits, on_planes, shapes = 0, 0, set()
+    for ray, exp in zip(d["rays"], d["per_world"]):
+        got = oracle.world_intersect(scene, ray)
+        assert (got is not None) == bool(exp[0])
+        if got is not None:
+            assert util.bits_equal(got[:9], exp[1:10]) and int(got[9]) == int(exp[10])
+            n_hits += 1
+            shapes.add(int(got[9]))
+            on_planes += scene.kind[int(got[9])] == abi.SHAPE_PLANE
+    assert n_hits > 150 and on_planes > 100 and len(shapes) >= (3 if name == "fan" else 6), (n_hits, on_planes, len(shapes))
+    if name == "coincident":  # world.py's strict "<": the pair's first plane takes every ray that meets the pair
+        i, j = info["pair"]
+        assert i in shapes and j not in shapes
+
+
 def test_checksums_match_baseline_md():
     # BASELINE.md §2 checksums, measured by the survey on the reference
     for name, expect in (("g5_demo_onoff_160x120", 44139.0), ("g5_demo_flat_160x120", 19389.899999998433),
