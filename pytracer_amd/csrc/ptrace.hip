@@ -21,6 +21,7 @@
 #include "pt_kernels.h"
 #include "pt_layout.h"
 #include "pt_plan.h"
+#include "pt_scene_build.h"
 #include "pt_hits_plan.h"
 #include "pt_post.h"
 
@@ -55,51 +56,48 @@ static int fail(int code, const char *fmt, ...) {
                   __LINE__);                                                                 \
   } while (0)
 
-// A ball of the scattered-ray filter as the kernels want it: r'^2 / (1 - 8e-6) rounded up; where there is no usable bound
-// (r' not finite or >= 1e17, a centre that is not finite or beyond 1e17) the centre 0 and r'^2 = 1e38, which the filter's
-// arithmetic never rejects and never overflows on (pt_query.h: world_query_lanes).
-static void pt_ball_square(float *x, float *y, float *z, float *r, bool *ordinary) {
-  const bool ok = std::isfinite(*r) && *r >= 0.0f && *r < 1e17f && std::isfinite(*x) && std::isfinite(*y) && std::isfinite(*z) &&
-                  std::fabs(*x) < 1e17f && std::fabs(*y) < 1e17f && std::fabs(*z) < 1e17f;
-  *ordinary = ok;
-  if (ok) {
-    *r = std::nextafter((float)((double)*r * (double)*r * (1.0 + 8.1e-6)), INFINITY);
-  } else {
-    *x = *y = *z = 0.0f;
-    *r = 1e38f;
-  }
-}
-
-struct pt_scene {
-  int device = 0;
-  int n_shapes = 0, n_spheres = 0, n_lights = 0, n_textures = 0;
+// What pt_scene_upload makes of a scene and no launch changes: the tables in HBM and every scalar of the analysis.  One
+// block per uploaded scene, shared by all its handles (pt_scene_clone); the last handle to be freed frees it.
+struct PtSceneShared {
   PtShapeRec *recs = nullptr;
   PtShapeAux *aux = nullptr;
-  PtHoist *hoist = nullptr;
   PtDiagRec *diag = nullptr;
-  PtHoistDiag *hoist_diag = nullptr;
   float4 *bounds = nullptr;
   unsigned *grid_cells = nullptr, *grid_occ = nullptr;  // uniform grid for scattered / shadow rays (see PtKArgs)
   float4 *grid_balls = nullptr;
   unsigned short *grid_slots = nullptr;
   int *grid_always = nullptr;
-  int grid_n_always = 0, grid_n_cells = 0, grid_res[3] = {0, 0, 0};
-  float grid_far_eo = INFINITY;  // rays with 1e-6 * max|origin component| above this do not walk the grid (see world_query_lanes)
-  float grid_min[3] = {0, 0, 0}, grid_max[3] = {0, 0, 0}, grid_cell[3] = {0, 0, 0}, grid_inv[3] = {0, 0, 0};
   float *bsoa = nullptr;  // bounds as x[], y[], z[], r'[] (bs_stride floats each), then group and chunk balls
-  int bs_stride = 0, gs_stride = 0, cs_stride = 0, bs_levels = 0;
-  float bs_rmax[3] = {0.0f, 0.0f, 0.0f};
-  int n_diag = 0;
   PtLight *lights = nullptr;
   PtTex *tex = nullptr;
   double *tex_data = nullptr;
+  PtSceneScalars sc;
+  std::vector<PtDomeCand> dome_cands;
+  int n_cu = 256;
+  std::atomic<int> refs{1};
+};
+
+// the device's current copy of the cold half of an argument block (refresh_cold)
+struct ColdArgs {
+  PtKArgs *dev = nullptr;
+  PtKArgs last;  // what `dev` holds
+  bool valid = false;
+  hipStream_t stream = nullptr;
+};
+
+// a handle: the scene it renders, and everything a launch writes
+struct pt_scene {
+  int device = 0;
+  PtSceneShared *sh = nullptr;
+  PtHoist *hoist = nullptr;
+  PtHoistDiag *hoist_diag = nullptr;
   double *ws = nullptr;  // path-tracer frame stack, grown on demand
   size_t ws_bytes = 0;
   double *handover = nullptr;  // num_of_rays > 1: records of the pixels the one-queue kernel hands to the tree kernel
   size_t handover_doubles = 0;
   int4 *units_handed = nullptr;  // ... and their units
   size_t units_handed_n = 0;
-  void *out_dev = nullptr;  // staging for pt_render (host output)
+  unsigned char *out_dev = nullptr;  // staging for pt_render (host output)
   size_t out_dev_bytes = 0;
   unsigned long long *ray_counter = nullptr;   // totals: all rays, rays resolved by the dome shortcut
   unsigned long long *ray_partials = nullptr;  // the same two per workgroup
@@ -111,30 +109,17 @@ struct pt_scene {
   unsigned long long *queue_last = nullptr;  // the block the most recent frame used (debug read-back)
   int queue_parity = 0;
   bool queue_clean = false;
-  PtKArgs *args_dev = nullptr;          // device copy of the argument block (cold fields)
-  PtKArgs *args_dev2 = nullptr;         // ... of pt_path_flagged_kernel's, when a frame enqueues both second-pass kernels (PT_Q_CHOICE)
-  PtKArgs args2_last;
-  bool args2_valid = false;
-  hipStream_t args2_stream = nullptr;
+  ColdArgs args;                        // the argument block (cold fields)
+  ColdArgs args2;                       // ... pt_path_flagged_kernel's, when a frame enqueues both second-pass kernels (PT_Q_CHOICE)
   int last_handover_cap = 0;            // records the last num_of_rays > 1 frame's hand-over table held (pt_debug_handed_over)
   bool choice_pending = false;          // ray_counter_host[2] will hold the frame's PT_Q_CHOICE word once ev_count has passed
   unsigned char *region_keys = nullptr;  // path tracer region ordering
-  struct DomeCand {
-    int slot;
-    double invm[12];
-  };
-  std::vector<DomeCand> dome_cands;  // spheres that may serve as "the dome" of a view: uniform pigments, sane scale
-  int4 *units = nullptr;  // second pass: work units (pt_unit_scatter)
-  int units_cap = 0;
   unsigned long long *region_mask = nullptr;
-  int region_cap = 0;
+  int4 *units = nullptr;  // second pass: work units (pt_unit_scatter)
+  size_t region_keys_cap = 0, region_mask_cap = 0, units_cap = 0;
   unsigned int *cell_list = nullptr;  // large scenes: per-cell survivor lists (pt_cell_kernel)
   int *cell_count = nullptr;
-  size_t cell_list_cap = 0;
-  int cell_count_cap = 0;
-  PtKArgs args_last;                    // what args_dev holds
-  bool args_valid = false;
-  hipStream_t args_stream = nullptr;
+  size_t cell_list_cap = 0, cell_count_cap = 0;
   unsigned long long *ray_counter_host = nullptr;  // pinned
   hipStream_t stream = nullptr;
   hipStream_t last_stream = nullptr;  // stream of the most recent launch
@@ -142,7 +127,6 @@ struct pt_scene {
   hipEvent_t ev_count = nullptr;  // recorded behind the copy of the ray count into ray_counter_host
   bool count_pending = false;     // the last launch enqueued that copy: fold_stats waits for ev_count
   bool launched = false;          // last_stream names a stream this scene has work on
-  int vgprs_last = 0;             // registers per lane of the render kernel launched last
   std::vector<hipEvent_t> prof;  // 2 * capacity events while profiling
   int prof_used = 0;             // pairs recorded
   bool profiling = false;
@@ -155,11 +139,7 @@ struct pt_scene {
   bool hoist_valid = false;  // s->hoist holds the constants of hoist_cam
   pt_camera hoist_cam = {};
   hipStream_t hoist_stream = nullptr;  // the stream the constants were produced on
-  int n_cu = 256;
   pt_stats stats = {};
-  // handles made by pt_scene_clone share the scene's tables (everything pt_scene_upload wrote and no launch changes);
-  // the last handle of the family to be freed frees them
-  std::atomic<int> *family = nullptr;
 };
 
 extern "C" int pt_version(void) { return PT_VERSION; }
@@ -211,37 +191,16 @@ extern "C" size_t pt_output_bytes(const pt_params *p) {
   return (size_t)pt_rows_for_rank(p) * (size_t)p->width * 3 * (p->out_format == PT_OUT_F32 ? 4 : 8);
 }
 
-static int check_desc(const pt_scene_desc *d) {
-  if (!d) return fail(PT_ERR_INVALID, "null scene descriptor");
-  if (d->n_shapes < 0 || d->n_lights < 0 || d->n_textures < 0)
-    return fail(PT_ERR_INVALID, "negative count in scene descriptor");
-  if (d->n_shapes > 0 &&
-      (!d->kind || !d->invm || !d->m || !d->brdf_kind || !d->brdf_param || !d->pig_kind ||
-       !d->pig_c1 || !d->pig_c2 || !d->pig_steps || !d->pig_tex || !d->emi_kind || !d->emi_c1 ||
-       !d->emi_c2 || !d->emi_steps || !d->emi_tex))
-    return fail(PT_ERR_INVALID, "null array in scene descriptor");
-  if (d->n_lights > 0 && (!d->light_pos || !d->light_color || !d->light_radius))
-    return fail(PT_ERR_INVALID, "null light array in scene descriptor");
-  if (d->n_textures > 0 && (!d->tex_w || !d->tex_h || !d->tex_offset || !d->tex_data))
-    return fail(PT_ERR_INVALID, "null texture array in scene descriptor");
-  for (int i = 0; i < d->n_shapes; ++i) {
-    if (d->kind[i] != PT_SHAPE_SPHERE && d->kind[i] != PT_SHAPE_PLANE)
-      return fail(PT_ERR_INVALID, "shape %d: unknown kind %d", i, d->kind[i]);
-    if (d->brdf_kind[i] != PT_BRDF_DIFFUSE && d->brdf_kind[i] != PT_BRDF_SPECULAR)
-      return fail(PT_ERR_INVALID, "shape %d: unknown BRDF kind %d", i, d->brdf_kind[i]);
-    const int pk[2] = {d->pig_kind[i], d->emi_kind[i]};
-    const int pt[2] = {d->pig_tex[i], d->emi_tex[i]};
-    for (int k = 0; k < 2; ++k) {
-      if (pk[k] < PT_PIGMENT_UNIFORM || pk[k] > PT_PIGMENT_IMAGE)
-        return fail(PT_ERR_INVALID, "shape %d: unknown pigment kind %d", i, pk[k]);
-      if (pk[k] == PT_PIGMENT_IMAGE && (pt[k] < 0 || pt[k] >= d->n_textures))
-        return fail(PT_ERR_INVALID, "shape %d: texture index %d out of range", i, pt[k]);
-    }
-  }
-  for (int t = 0; t < d->n_textures; ++t)
-    if (d->tex_w[t] <= 0 || d->tex_h[t] <= 0 || d->tex_offset[t] < 0)
-      return fail(PT_ERR_INVALID, "texture %d: bad size/offset", t);
-  return PT_OK;
+static int check_desc(const pt_scene_desc *d) { return pt_check_desc(d, g_err, sizeof g_err); }
+
+// drop a handle's reference on the scene's block; the last one frees the tables (the device is current)
+static void shared_release(PtSceneShared *sh) {
+  if (!sh || sh->refs.fetch_sub(1) != 1) return;
+  for (void *p : {(void *)sh->recs, (void *)sh->aux, (void *)sh->diag, (void *)sh->bounds, (void *)sh->bsoa, (void *)sh->grid_cells,
+                  (void *)sh->grid_occ, (void *)sh->grid_balls, (void *)sh->grid_slots, (void *)sh->grid_always, (void *)sh->lights,
+                  (void *)sh->tex, (void *)sh->tex_data})
+    (void)hipFree(p);
+  delete sh;
 }
 
 extern "C" void pt_scene_free(pt_scene *s) {
@@ -249,45 +208,14 @@ extern "C" void pt_scene_free(pt_scene *s) {
   (void)hipSetDevice(s->device);
   if (s->stream) (void)hipStreamSynchronize(s->stream);
   if (s->launched && s->last_stream) (void)hipStreamSynchronize(s->last_stream);
-  // the tables the family shares: freed by its last handle (a scene that was never cloned is a family of one)
-  const bool last = !s->family || s->family->fetch_sub(1) == 1;
-  if (last) {
-    (void)hipFree(s->recs);
-    (void)hipFree(s->aux);
-    (void)hipFree(s->diag);
-    (void)hipFree(s->bounds);
-    (void)hipFree(s->bsoa);
-    (void)hipFree(s->grid_cells);
-    (void)hipFree(s->grid_occ);
-    (void)hipFree(s->grid_balls);
-    (void)hipFree(s->grid_slots);
-    (void)hipFree(s->grid_always);
-    (void)hipFree(s->lights);
-    (void)hipFree(s->tex);
-    (void)hipFree(s->tex_data);
-    delete s->family;
-  }
-  (void)hipFree(s->hoist);
-  (void)hipFree(s->hoist_diag);
-  (void)hipFree(s->ws);
-  (void)hipFree(s->handover);
-  (void)hipFree(s->units_handed);
-  (void)hipFree(s->out_dev);
-  (void)hipFree(s->ray_counter);
-  (void)hipFree(s->ray_partials);
-  (void)hipFree(s->queue);
-  (void)hipFree(s->args_dev);
-  (void)hipFree(s->args_dev2);
-  (void)hipFree(s->region_keys);
-  (void)hipFree(s->units);
-  (void)hipFree(s->region_mask);
-  (void)hipFree(s->cell_list);
-  (void)hipFree(s->cell_count);
+  shared_release(s->sh);
+  for (void *p : {(void *)s->hoist, (void *)s->hoist_diag, (void *)s->ws, (void *)s->handover, (void *)s->units_handed, (void *)s->out_dev,
+                  (void *)s->ray_counter, (void *)s->ray_partials, (void *)s->queue, (void *)s->args.dev, (void *)s->args2.dev,
+                  (void *)s->region_keys, (void *)s->units, (void *)s->region_mask, (void *)s->cell_list, (void *)s->cell_count})
+    (void)hipFree(p);
   if (s->ray_counter_host) (void)hipHostFree(s->ray_counter_host);
-  if (s->ev0) (void)hipEventDestroy(s->ev0);
-  if (s->ev1) (void)hipEventDestroy(s->ev1);
-  if (s->ev2) (void)hipEventDestroy(s->ev2);
-  if (s->ev_count) (void)hipEventDestroy(s->ev_count);
+  for (hipEvent_t e : {s->ev0, s->ev1, s->ev2, s->ev_count})
+    if (e) (void)hipEventDestroy(e);
   for (hipEvent_t e : s->prof) (void)hipEventDestroy(e);
   if (s->stream) (void)hipStreamDestroy(s->stream);
   delete s;
@@ -313,8 +241,8 @@ static int handle_state(pt_scene *s) {
   int rc;
   if ((rc = hip_or_free(hipMalloc((void **)&s->ray_counter, 2 * sizeof(unsigned long long)), "hipMalloc(counter)"))) return rc;
   if ((rc = hip_or_free(hipMalloc((void **)&s->queue, 2 * PT_QUEUE_WORDS * sizeof(unsigned long long)), "hipMalloc(queue)"))) return rc;
-  if ((rc = hip_or_free(hipMalloc((void **)&s->args_dev, sizeof(PtKArgs)), "hipMalloc(args)"))) return rc;
-  if ((rc = hip_or_free(hipMalloc((void **)&s->args_dev2, sizeof(PtKArgs)), "hipMalloc(args)"))) return rc;
+  if ((rc = hip_or_free(hipMalloc((void **)&s->args.dev, sizeof(PtKArgs)), "hipMalloc(args)"))) return rc;
+  if ((rc = hip_or_free(hipMalloc((void **)&s->args2.dev, sizeof(PtKArgs)), "hipMalloc(args)"))) return rc;
   if ((rc = hip_or_free(hipHostMalloc((void **)&s->ray_counter_host, 3 * sizeof(unsigned long long)), "hipHostMalloc"))) return rc;
   s->ray_counter_host[0] = s->ray_counter_host[1] = s->ray_counter_host[2] = 0;
   if ((rc = hip_or_free(hipStreamCreateWithFlags(&s->stream, hipStreamNonBlocking), "hipStreamCreate"))) return rc;
@@ -325,487 +253,7 @@ static int handle_state(pt_scene *s) {
   return PT_OK;
 }
 
-// What pt_scene_upload computes on the HOST before anything is uploaded: the records in slot order, the culling bounds, the
-// ball hierarchy, the uniform grid.  No HIP call: pt_debug_plan runs it for a scene DESCRIPTION on any machine (the scalars
-// land in `s`, used as a plain bag of facts there).
-struct HostTables {
-  std::vector<PtShapeRec> recs;
-  std::vector<PtShapeAux> aux;
-  std::vector<PtDiagRec> diag;
-  std::vector<float4> bounds;
-  std::vector<float> bsoa;
-  std::vector<PtLight> lights;
-  std::vector<PtTex> tex;
-  std::vector<double> tex_data;
-  bool has_grid = false;
-  std::vector<unsigned> grid_cells, grid_occ;
-  std::vector<unsigned short> grid_slots;
-  std::vector<float4> grid_balls;
-  std::vector<int> grid_always;
-};
-
-static void analyse_scene(const pt_scene_desc *d, const PtTuning &tn, pt_scene *s, HostTables &h) {
-  s->n_shapes = d->n_shapes;
-  s->n_lights = d->n_lights;
-  s->n_textures = d->n_textures;
-  const int n = d->n_shapes;
-
-  // group the records: scale+translate spheres, other spheres, planes — each group in World.shapes order
-  auto is_diag = [&](int i) {
-    if (d->kind[i] != PT_SHAPE_SPHERE) return false;
-    const int off[6] = {1, 2, 4, 6, 8, 9};
-    for (int k : off)
-      if (d->invm[(size_t)k * n + i] != 0.0) return false;
-    const int dia[3] = {0, 5, 10};
-    for (int k : dia) {
-      const double v = std::fabs(d->invm[(size_t)k * n + i]);
-      if (!(v >= 1e-100 && v <= 1e100)) return false;
-    }
-    for (int k : {3, 7, 11})
-      if (!std::isfinite(d->invm[(size_t)k * n + i])) return false;
-    return true;
-  };
-  std::vector<int> order;
-  order.reserve(n);
-  for (int i = 0; i < n; ++i)
-    if (is_diag(i)) order.push_back(i);
-  s->n_diag = (int)order.size();
-  for (int i = 0; i < n; ++i)
-    if (d->kind[i] == PT_SHAPE_SPHERE && !is_diag(i)) order.push_back(i);
-  s->n_spheres = (int)order.size();
-  for (int i = 0; i < n; ++i)
-    if (d->kind[i] != PT_SHAPE_SPHERE) order.push_back(i);
-  // Large scenes: within each sphere group the slots follow a Morton curve through the centres (the few
-  // spheres much larger than the rest first), so that 8 and 64 consecutive slots are close in space and
-  // a ball around them is tight (per-ray prefilter of scattered and shadow rays, world_query_lanes).
-  // Any slot order gives the same image: ties in t go to the lower World.shapes index (r.index).
-  s->bs_levels = s->n_spheres >= 128 ? 1 : 0;
-  if (s->bs_levels) {
-    auto centre = [&](int i, int k) { return d->m[(size_t)(3 + 4 * k) * n + i]; };
-    auto radius2 = [&](int i) {  // squared Frobenius norm of M's 3x3 block: a size, not a bound
-      double v = 0.0;
-      for (int r_ = 0; r_ < 3; ++r_)
-        for (int c_ = 0; c_ < 3; ++c_) v += d->m[(size_t)(r_ * 4 + c_) * n + i] * d->m[(size_t)(r_ * 4 + c_) * n + i];
-      return v;
-    };
-    std::vector<double> sizes;
-    for (int k = 0; k < s->n_spheres; ++k) sizes.push_back(radius2(order[k]));
-    std::vector<double> sorted_sizes = sizes;
-    std::nth_element(sorted_sizes.begin(), sorted_sizes.begin() + sorted_sizes.size() / 2, sorted_sizes.end());
-    const double big = 64.0 * sorted_sizes[sorted_sizes.size() / 2];  // 8x the median radius
-    double lo[3] = {INFINITY, INFINITY, INFINITY}, hi[3] = {-INFINITY, -INFINITY, -INFINITY};
-    for (int k = 0; k < s->n_spheres; ++k) {
-      if (!(sizes[k] <= big)) continue;
-      for (int c_ = 0; c_ < 3; ++c_) {
-        const double v = centre(order[k], c_);
-        if (std::isfinite(v)) {
-          lo[c_] = std::min(lo[c_], v);
-          hi[c_] = std::max(hi[c_], v);
-        }
-      }
-    }
-    auto morton = [&](int i) {
-      uint64_t code = 0;
-      uint32_t q[3];
-      for (int c_ = 0; c_ < 3; ++c_) {
-        const double v = centre(i, c_), span = hi[c_] - lo[c_];
-        double u = (span > 0.0 && std::isfinite(v)) ? (v - lo[c_]) / span : 0.0;
-        u = std::min(1.0, std::max(0.0, u));
-        q[c_] = (uint32_t)(u * 2097151.0);  // 21 bits
-      }
-      for (int b = 20; b >= 0; --b)
-        for (int c_ = 0; c_ < 3; ++c_) code = (code << 1) | ((q[c_] >> b) & 1u);
-      return code;
-    };
-    auto sort_range = [&](int a0, int a1) {
-      std::vector<std::pair<std::pair<int, uint64_t>, int>> keyed;  // ((small?, code), shape)
-      for (int k = a0; k < a1; ++k) {
-        const bool small_ = sizes[k] <= big;
-        // large spheres first, largest leading; then the Morton order of the rest
-        const uint64_t code = small_ ? morton(order[k]) : (uint64_t)(k - a0);
-        keyed.push_back({{small_ ? 1 : 0, code}, order[k]});
-      }
-      std::stable_sort(keyed.begin(), keyed.end(), [](const auto &x, const auto &y) { return x.first < y.first; });
-      for (int k = a0; k < a1; ++k) order[k] = keyed[k - a0].second;
-    };
-    sort_range(0, s->n_diag);
-    sort_range(s->n_diag, s->n_spheres);
-  }
-  std::vector<PtShapeRec> recs(n);
-  std::vector<PtShapeAux> aux(n);
-  for (int slot = 0; slot < n; ++slot) {
-    const int i = order[slot];
-    PtShapeRec &r = recs[slot];
-    PtShapeAux &x = aux[slot];
-    memset(&r, 0, sizeof r);
-    memset(&x, 0, sizeof x);
-    for (int k = 0; k < 12; ++k) {
-      r.invm[k] = d->invm[(size_t)k * n + i];
-      x.m[k] = d->m[(size_t)k * n + i];
-    }
-    r.kind = d->kind[i];
-    for (int k = 0; k < 3; ++k) {
-      x.pig_c1[k] = d->pig_c1[(size_t)k * n + i];
-      x.pig_c2[k] = d->pig_c2[(size_t)k * n + i];
-      x.emi_c1[k] = d->emi_c1[(size_t)k * n + i];
-      x.emi_c2[k] = d->emi_c2[(size_t)k * n + i];
-    }
-    x.pig_steps = d->pig_steps[i];
-    x.emi_steps = d->emi_steps[i];
-    x.brdf_param = d->brdf_param[i];
-    x.brdf_kind = d->brdf_kind[i];
-    x.pig_kind = d->pig_kind[i];
-    x.emi_kind = d->emi_kind[i];
-    x.pig_tex = d->pig_tex[i];
-    x.emi_tex = d->emi_tex[i];
-    x.needs_uv = (d->pig_kind[i] != PT_PIGMENT_UNIFORM || d->emi_kind[i] != PT_PIGMENT_UNIFORM) ? 1 : 0;
-    // both pigments uniform: color2 of the (uniform) BRDF pigment is never read, and the slot carries what FlatRenderer
-    // returns for the shape, pigment + emitted (render.py:65-74; the same fp64 addition the kernel would do per pixel)
-    if (!x.needs_uv)
-      for (int k = 0; k < 3; ++k) x.pig_c2[k] = x.pig_c1[k] + x.emi_c1[k];
-    r.index = i;
-    // |invm|_F^2 for the "camera inside this sphere" shortcut of the tile kernel; +inf disables it unless
-    // every singular value of invm's 3x3 block is within 1e-6 .. 1e6 (Gershgorin bounds of invm^T invm)
-    r.fro2 = INFINITY;
-    if (r.kind == PT_SHAPE_SPHERE) {
-      double A[3][3], fro2 = 0.0;
-      for (int p = 0; p < 3; ++p)
-        for (int q = 0; q < 3; ++q) {
-          A[p][q] = 0.0;
-          for (int k = 0; k < 3; ++k) A[p][q] += r.invm[k * 4 + p] * r.invm[k * 4 + q];
-        }
-      double lmin = INFINITY, lmax = 0.0;
-      for (int p = 0; p < 3; ++p) {
-        double off = 0.0;
-        for (int q = 0; q < 3; ++q)
-          if (q != p) off += std::fabs(A[p][q]);
-        lmin = std::min(lmin, A[p][p] - off);
-        lmax = std::max(lmax, A[p][p] + off);
-        fro2 += A[p][p];
-      }
-      if (std::isfinite(fro2) && lmin >= 1e-12 && lmax <= 1e12) r.fro2 = fro2 * (1.0 + 1e-9);
-    }
-  }
-  std::vector<PtLight> lights(d->n_lights);
-  for (int l = 0; l < d->n_lights; ++l) {
-    memset(&lights[l], 0, sizeof(PtLight));
-    for (int k = 0; k < 3; ++k) {
-      lights[l].pos[k] = d->light_pos[(size_t)k * d->n_lights + l];
-      lights[l].color[k] = d->light_color[(size_t)k * d->n_lights + l];
-    }
-    lights[l].radius = d->light_radius[l];
-  }
-  std::vector<PtTex> tex(d->n_textures);
-  size_t tex_doubles = 0;
-  for (int t = 0; t < d->n_textures; ++t) {
-    tex[t].w = d->tex_w[t];
-    tex[t].h = d->tex_h[t];
-    tex[t].offset = d->tex_offset[t];
-    tex_doubles = std::max(tex_doubles, (size_t)d->tex_offset[t] + (size_t)d->tex_w[t] * d->tex_h[t] * 3);
-  }
-  std::vector<double> tex_data(d->tex_data, d->tex_data + tex_doubles);
-
-  std::vector<PtDiagRec> diag(s->n_diag);
-  for (int slot = 0; slot < s->n_diag; ++slot) {
-    PtDiagRec &g = diag[slot];
-    memset(&g, 0, sizeof g);
-    const double *im = recs[slot].invm;
-    g.s[0] = im[0];
-    g.s[1] = im[5];
-    g.s[2] = im[10];
-    g.t[0] = im[3];
-    g.t[1] = im[7];
-    g.t[2] = im[11];
-    g.tnz = (im[3] != 0.0 ? 1 : 0) | (im[7] != 0.0 ? 2 : 0) | (im[11] != 0.0 ? 4 : 0);
-  }
-  // bounding spheres for tile culling: radius = a rigorous upper bound of the spectral norm of M's 3x3 block
-  struct Bound64 {
-    double cx, cy, cz, r;
-  };
-  std::vector<float4> bounds(n);
-  for (int slot = 0; slot < n; ++slot) {
-    Bound64 b;
-    const double *m = aux[slot].m;
-    b.cx = m[3];
-    b.cy = m[7];
-    b.cz = m[11];
-    b.r = -1.0;
-    if (recs[slot].kind == PT_SHAPE_SPHERE) {
-      double A[3][3];
-      for (int i = 0; i < 3; ++i)
-        for (int j = 0; j < 3; ++j) {
-          A[i][j] = 0.0;
-          for (int k = 0; k < 3; ++k) A[i][j] += m[k * 4 + i] * m[k * 4 + j];
-        }
-      // Gershgorin: lambda_max(M^T M) <= max_i sum_j |(M^T M)_ij|  (exact for scale/rotation blocks)
-      double lam = 0.0;
-      for (int i = 0; i < 3; ++i)
-        lam = std::max(lam, std::fabs(A[i][0]) + std::fabs(A[i][1]) + std::fabs(A[i][2]));
-      // The exact test uses invm, the bound uses m: check that m really inverts invm (the reference
-      // stores both, transformations.py:48-56) and widen the radius by the residual; else never cull.
-      const double *im = recs[slot].invm;
-      double resid = 0.0;
-      for (int i = 0; i < 3; ++i) {
-        for (int j = 0; j < 3; ++j) {
-          double e = (i == j) ? -1.0 : 0.0;
-          for (int k = 0; k < 3; ++k) e += im[i * 4 + k] * m[k * 4 + j];
-          resid = std::max(resid, std::fabs(e));
-        }
-        double e = im[i * 4 + 3];
-        for (int k = 0; k < 3; ++k) e += im[i * 4 + k] * m[k * 4 + 3];
-        resid = std::max(resid, std::fabs(e));
-      }
-      const double r = std::sqrt(lam) * (1.0 + 1e-9 + 16.0 * resid);
-      const bool finite = std::isfinite(r) && std::isfinite(b.cx) && std::isfinite(b.cy) &&
-                          std::isfinite(b.cz) && resid < 1e-6;
-      b.r = finite ? r : -1.0;
-    }
-    // to fp32: widen r by the rounding of the centre (<= 2^-24 relative per component) and of r itself
-    float4 f;
-    f.x = (float)b.cx;
-    f.y = (float)b.cy;
-    f.z = (float)b.cz;
-    const double cabs = std::max(std::fabs(b.cx), std::max(std::fabs(b.cy), std::fabs(b.cz)));
-    const double rw = b.r * (1.0 + 1e-6) + 2e-7 * cabs;
-    f.w = (b.r >= 0.0 && std::isfinite(rw) && rw < 1e37 && cabs < 1e37) ? (float)rw * (1.0f + 1e-6f) : -1.0f;
-    if (recs[slot].kind == PT_SHAPE_PLANE) {
-      // planes have no bounding sphere; their slot carries what plane_keeps() needs instead: the z row of
-      // invm (object-space d.z = row . d, o.z = row . o + invm[11]) rounded to fp32
-      const double *im = recs[slot].invm;
-      f.x = (float)im[8];
-      f.y = (float)im[9];
-      f.z = (float)im[10];
-      f.w = (float)im[11];
-    }
-    bounds[slot] = f;
-  }
-  // ... and as structure-of-arrays for the per-ray prefilter of scattered rays (world_query_lanes): two
-  // neighbouring spheres per packed fp32 instruction.  r' = r*(1 + 1e-5) + 1e-6*max|c| rounded up;
-  // +inf where there is no bound (the test then always keeps the shape).
-  s->bs_stride = (n + 8 + 7) / 8 * 8;  // 8 floats of slack: the prefilter reads eight at a time, 32-byte aligned
-  const int n_groups = (s->n_spheres + 7) / 8, n_chunks = (s->n_spheres + 63) / 64;
-  s->gs_stride = (n_chunks * 8 + 8 + 7) / 8 * 8;  // eight groups per chunk, read eight at a time
-  s->cs_stride = (n_chunks + 8 + 7) / 8 * 8;
-  std::vector<float> bsoa((size_t)4 * (s->bs_stride + s->gs_stride + s->cs_stride), 0.0f);
-  for (int slot = 0; slot < s->bs_stride; ++slot) {
-    float rk = INFINITY;
-    if (slot < n) {
-      const float4 f = bounds[slot];
-      bsoa[slot] = f.x;
-      bsoa[(size_t)s->bs_stride + slot] = f.y;
-      bsoa[(size_t)2 * s->bs_stride + slot] = f.z;
-      if (slot < s->n_spheres && f.w >= 0.0f) {
-        const double cabs = std::max(std::fabs((double)f.x), std::max(std::fabs((double)f.y), std::fabs((double)f.z)));
-        const double v = (double)f.w * (1.0 + 1e-5) + 1e-6 * cabs;
-        rk = std::nextafter((float)v, INFINITY);
-      }
-    }
-    bsoa[(size_t)3 * s->bs_stride + slot] = rk;
-  }
-  // a ball around the (already inflated) balls of slots [a0, a1): centre = middle of the centres' box,
-  // radius = max_i(|c_i - centre| + r'_i), rounded up; +inf as soon as one member has no bound
-  auto ball_around = [&](int a0, int a1, float *out4) {
-    double lo[3] = {INFINITY, INFINITY, INFINITY}, hi[3] = {-INFINITY, -INFINITY, -INFINITY};
-    bool bounded = a1 > a0;
-    for (int k = a0; k < a1; ++k) {
-      bounded = bounded && std::isfinite(bsoa[(size_t)3 * s->bs_stride + k]);
-      for (int c_ = 0; c_ < 3; ++c_) {
-        const double v = bsoa[(size_t)c_ * s->bs_stride + k];
-        lo[c_] = std::min(lo[c_], v);
-        hi[c_] = std::max(hi[c_], v);
-      }
-    }
-    out4[0] = out4[1] = out4[2] = 0.0f;
-    out4[3] = INFINITY;
-    if (!bounded) return;
-    float c[3];
-    for (int c_ = 0; c_ < 3; ++c_) c[c_] = (float)(0.5 * (lo[c_] + hi[c_]));
-    double rad = 0.0;
-    for (int k = a0; k < a1; ++k) {
-      double d2 = 0.0;
-      for (int c_ = 0; c_ < 3; ++c_) {
-        const double dv = (double)bsoa[(size_t)c_ * s->bs_stride + k] - (double)c[c_];
-        d2 += dv * dv;
-      }
-      rad = std::max(rad, std::sqrt(d2) * (1.0 + 1e-12) + (double)bsoa[(size_t)3 * s->bs_stride + k]);
-    }
-    const double cabs = std::max(std::fabs((double)c[0]), std::max(std::fabs((double)c[1]), std::fabs((double)c[2])));
-    const double v = rad * (1.0 + 1e-5) + 1e-6 * cabs;
-    if (!std::isfinite(v) || v > 1e37) return;
-    out4[0] = c[0];
-    out4[1] = c[1];
-    out4[2] = c[2];
-    out4[3] = std::nextafter((float)v, INFINITY);
-  };
-  {
-    float *gs = bsoa.data() + (size_t)4 * s->bs_stride, *cs = gs + (size_t)4 * s->gs_stride;
-    for (int k = 0; k < s->gs_stride; ++k) {
-      float b4[4] = {0.0f, 0.0f, 0.0f, INFINITY};
-      if (k < n_groups) ball_around(k * 8, std::min(k * 8 + 8, s->n_spheres), b4);
-      for (int c_ = 0; c_ < 4; ++c_) gs[(size_t)c_ * s->gs_stride + k] = b4[c_];
-    }
-    for (int k = 0; k < s->cs_stride; ++k) {
-      float b4[4] = {0.0f, 0.0f, 0.0f, INFINITY};
-      if (k < n_chunks) ball_around(k * 64, std::min(k * 64 + 64, s->n_spheres), b4);
-      for (int c_ = 0; c_ < 4; ++c_) cs[(size_t)c_ * s->cs_stride + k] = b4[c_];
-    }
-  }
-  for (int slot = 0; slot < s->n_spheres; ++slot)
-    if (aux[slot].needs_uv == 0 && std::isfinite(recs[slot].fro2)) {
-      pt_scene::DomeCand dc;
-      dc.slot = slot;
-      memcpy(dc.invm, recs[slot].invm, sizeof dc.invm);
-      s->dome_cands.push_back(dc);
-    }
-  h.recs = recs;
-  h.bounds = bounds;
-  // ---- uniform grid over the ordinary spheres (scenes of >= 128 spheres) ----
-  // A sphere is entered into every cell that the box around its ball (the r' of the per-ray prefilter, already
-  // inflated) overlaps after widening it by eps = 2e-3 cell + 1e-4 max|coordinate|.  The walk (world_query_lanes)
-  // runs a 3D-DDA in fp32 on the fp32 copy of the ray: that copy stays within ~1e-7 |coordinate| x a few of the
-  // true ray, and the accumulated rounding of the DDA's crossing parameters (<= 200 steps x 2^-24) can make it
-  // enter a face or skip a corner cell up to ~1.2e-5 x the grid's extent early or late; eps (>= 3e-5 extent, since
-  // a cell is >= 1/64 of it) covers both, so a point where the true ray meets a sphere always lies within eps of a
-  // visited cell, i.e. in a cell the sphere is entered in.  Spheres much larger than the rest (8x the median
-  // radius: a dome would be in every cell) or without a bound go to the "always" list.
-  if (tn.grid && s->bs_levels && s->n_spheres <= 65535) {
-    auto ball = [&](int k, int q) { return bsoa[(size_t)q * s->bs_stride + k]; };  // q: 0..2 centre, 3 radius r'
-    std::vector<float> radii;
-    for (int k = 0; k < s->n_spheres; ++k)
-      if (std::isfinite(ball(k, 3))) radii.push_back(ball(k, 3));
-    std::vector<int> always, inside;
-    float big = INFINITY;
-    if (!radii.empty()) {
-      std::nth_element(radii.begin(), radii.begin() + radii.size() / 2, radii.end());
-      big = 8.0f * radii[radii.size() / 2];
-    }
-    double lo[3] = {INFINITY, INFINITY, INFINITY}, hi[3] = {-INFINITY, -INFINITY, -INFINITY}, cmax = 0.0;
-    for (int k = 0; k < s->n_spheres; ++k) {
-      const float r = ball(k, 3);
-      if (!std::isfinite(r) || r > big) {
-        always.push_back(k);
-        continue;
-      }
-      inside.push_back(k);
-      for (int q = 0; q < 3; ++q) {
-        lo[q] = std::min(lo[q], (double)ball(k, q) - r);
-        hi[q] = std::max(hi[q], (double)ball(k, q) + r);
-      }
-    }
-    // (below ~1000 spheres the exhaustive packed prefilter and the cell walk cost the same -- measured on C4's 256 --
-    //  and the prefilter has the sparse path for the deep stragglers; the grid wins 2.5-3.3x at 10 000)
-    if ((int)inside.size() >= std::max(64, (int)tn.grid_min)) {
-      double ext[3], vol = 1.0;
-      for (int q = 0; q < 3; ++q) {
-        const double pad = 1e-3 * (hi[q] - lo[q]) + 1e-4 * (1.0 + std::max(std::fabs(lo[q]), std::fabs(hi[q])));
-        lo[q] -= pad;
-        hi[q] += pad;
-        ext[q] = hi[q] - lo[q];
-        vol *= ext[q];
-        cmax = std::max(cmax, std::max(std::fabs(lo[q]), std::fabs(hi[q])));
-      }
-      const double target = std::min<double>(32768.0, std::max<double>(64.0, tn.grid_density * (double)inside.size()));  // (cells per sphere)
-      const double side = std::cbrt(vol / target);
-      long long ncell = 1;
-      for (int q = 0; q < 3; ++q) {
-        s->grid_res[q] = (int)std::min(64.0, std::max(1.0, std::ceil(ext[q] / side)));
-        s->grid_min[q] = (float)lo[q];
-        s->grid_max[q] = (float)hi[q];
-        s->grid_cell[q] = (float)(ext[q] / s->grid_res[q]);
-        s->grid_inv[q] = (float)(s->grid_res[q] / ext[q]);
-        ncell *= s->grid_res[q];
-      }
-      std::vector<std::vector<unsigned short>> cells((size_t)ncell);
-      size_t items = 0;
-      bool ok = std::isfinite(vol) && vol > 0.0 && ncell <= 65535;  // (cell ids travel in 16 bits)
-      for (int k : inside) {
-        if (!ok) break;
-        int c0[3], c1[3];
-        for (int q = 0; q < 3; ++q) {
-          const double eps = 2e-3 * s->grid_cell[q] + 1e-4 * cmax, c = ball(k, q), r = ball(k, 3);
-          c0[q] = std::max(0, std::min(s->grid_res[q] - 1, (int)std::floor((c - r - eps - lo[q]) * s->grid_res[q] / ext[q])));
-          c1[q] = std::max(0, std::min(s->grid_res[q] - 1, (int)std::floor((c + r + eps - lo[q]) * s->grid_res[q] / ext[q])));
-        }
-        for (int z = c0[2]; z <= c1[2]; ++z)
-          for (int y = c0[1]; y <= c1[1]; ++y)
-            for (int x = c0[0]; x <= c1[0]; ++x) {
-              auto &cell = cells[((size_t)z * s->grid_res[1] + y) * s->grid_res[0] + x];
-              cell.push_back((unsigned short)k);
-              ++items;
-              ok = ok && cell.size() <= 255 && items <= ((size_t)1 << 23);
-            }
-      }
-      if (ok) {
-        std::vector<unsigned> words((size_t)ncell), occ((size_t)(ncell + 31) / 32 + 1, 0u);
-        std::vector<unsigned short> slots;
-        std::vector<float4> balls;
-        for (size_t cidx = 0; cidx < (size_t)ncell; ++cidx) {
-          words[cidx] = ((unsigned)slots.size() << 8) | (unsigned)cells[cidx].size();
-          if (!cells[cidx].empty()) occ[cidx >> 5] |= 1u << (cidx & 31);
-          for (unsigned short k : cells[cidx]) {
-            slots.push_back(k);
-            float4 b;
-            b.x = ball(k, 0);
-            b.y = ball(k, 1);
-            b.z = ball(k, 2);
-            b.w = ball(k, 3);
-            bool ordinary;
-            pt_ball_square(&b.x, &b.y, &b.z, &b.w, &ordinary);
-            balls.push_back(b);
-          }
-        }
-        h.grid_cells = words;
-        h.grid_occ = occ;
-        h.grid_slots = slots;
-        h.grid_balls = balls;
-        h.grid_always = always;
-        h.has_grid = true;
-        s->grid_n_always = (int)always.size();
-        // the margin a sphere is entered with, >= 1e-4 * cmax, covers the fp32 copy of a ray whose origin lies within
-        // ~100 x the grid's coordinates (1.2e-7 |o| <= a quarter of the margin); a ray from farther away takes the
-        // exhaustive filter instead of the walk
-        s->grid_far_eo = (float)(1e-4 * cmax);
-        s->grid_n_cells = (int)ncell;
-      }
-    }
-  }
-  // the filter compares squares (world_query_lanes): r' -> r'^2 rounded up, in all three tables
-  {
-    float *tab[3] = {bsoa.data(), bsoa.data() + (size_t)4 * s->bs_stride, bsoa.data() + (size_t)4 * (s->bs_stride + s->gs_stride)};
-    const int stride[3] = {s->bs_stride, s->gs_stride, s->cs_stride};
-    for (int lv = 0; lv < 3; ++lv) {
-      float rmax = 0.0f;
-      for (int k = 0; k < stride[lv]; ++k) {
-        float *x = tab[lv] + k, *y = x + stride[lv], *z = y + stride[lv], *r = z + stride[lv];
-        const float rp = *r;
-        bool ordinary;
-        pt_ball_square(x, y, z, r, &ordinary);
-        if (ordinary) rmax = std::max(rmax, rp);
-      }
-      s->bs_rmax[lv] = rmax;
-    }
-  }
-  h.bsoa = bsoa;
-  h.diag = diag;
-  h.aux = aux;
-  h.lights = lights;
-  h.tex = tex;
-  h.tex_data = tex_data;
-}
-
-static PtSceneFacts scene_facts(const pt_scene *s) {
-  PtSceneFacts f;
-  f.n_shapes = s->n_shapes;
-  f.n_spheres = s->n_spheres;
-  f.n_diag = s->n_diag;
-  f.n_lights = s->n_lights;
-  f.bs_levels = s->bs_levels;
-  f.has_grid = s->grid_n_cells > 0 ? 1 : 0;
-  f.grid_n_cells = s->grid_n_cells;
-  f.n_cu = s->n_cu;
-  f.dome_shortcut = s->dome_shortcut ? 1 : 0;
-  return f;
-}
+static PtSceneFacts scene_facts(const pt_scene *s) { return pt_scene_facts(s->sh->sc, s->sh->n_cu, s->dome_shortcut); }
 
 extern "C" int pt_scene_upload(const pt_scene_desc *d, int device, pt_scene **out) {
   if (!out) return fail(PT_ERR_INVALID, "null output handle");
@@ -819,10 +267,17 @@ extern "C" int pt_scene_upload(const pt_scene_desc *d, int device, pt_scene **ou
   HIP_TRY(hipSetDevice(device));
 
   pt_scene *s = new (std::nothrow) pt_scene();
-  if (!s) return fail(PT_ERR_NOMEM, "out of host memory");
+  PtSceneShared *sh = s ? new (std::nothrow) PtSceneShared() : nullptr;
+  if (!sh) {
+    delete s;
+    return fail(PT_ERR_NOMEM, "out of host memory");
+  }
   s->device = device;
-  HostTables h;
-  analyse_scene(d, pt_tuning(), s, h);
+  s->sh = sh;
+  PtSceneHost h;
+  pt_build_scene(d, pt_tuning(), h);
+  sh->sc = h.sc;
+  sh->dome_cands = h.dome_cands;
 #define UP(call)            \
   do {                      \
     rc = (call);            \
@@ -831,70 +286,53 @@ extern "C" int pt_scene_upload(const pt_scene_desc *d, int device, pt_scene **ou
       return rc;            \
     }                       \
   } while (0)
-  UP(upload(&s->recs, h.recs));
-  UP(upload(&s->bounds, h.bounds));
+  UP(upload(&sh->recs, h.recs));
+  UP(upload(&sh->bounds, h.bounds));
   if (h.has_grid) {
-    UP(upload(&s->grid_cells, h.grid_cells));
-    UP(upload(&s->grid_occ, h.grid_occ));
-    UP(upload(&s->grid_slots, h.grid_slots));
-    UP(upload(&s->grid_balls, h.grid_balls));
-    UP(upload(&s->grid_always, h.grid_always));
+    UP(upload(&sh->grid_cells, h.grid_cells));
+    UP(upload(&sh->grid_occ, h.grid_occ));
+    UP(upload(&sh->grid_slots, h.grid_slots));
+    UP(upload(&sh->grid_balls, h.grid_balls));
+    UP(upload(&sh->grid_always, h.grid_always));
   }
-  UP(upload(&s->bsoa, h.bsoa));
-  UP(upload(&s->diag, h.diag));
+  UP(upload(&sh->bsoa, h.bsoa));
+  UP(upload(&sh->diag, h.diag));
   {
-    std::vector<PtHoistDiag> hd(std::max(s->n_diag, 1));
+    std::vector<PtHoistDiag> hd(std::max(sh->sc.n_diag, 1));
     UP(upload(&s->hoist_diag, hd));
   }
-  UP(upload(&s->aux, h.aux));
-  UP(upload(&s->lights, h.lights));
-  UP(upload(&s->tex, h.tex));
-  UP(upload(&s->tex_data, h.tex_data));
+  UP(upload(&sh->aux, h.aux));
+  UP(upload(&sh->lights, h.lights));
+  UP(upload(&sh->tex, h.tex));
+  UP(upload(&sh->tex_data, h.tex_data));
   {
-    std::vector<PtHoist> hh(std::max(s->n_shapes, 1));
+    std::vector<PtHoist> hh(std::max(sh->sc.n_shapes, 1));
     UP(upload(&s->hoist, hh));
   }
 #undef UP
   if ((rc = handle_state(s))) return rc;
   hipDeviceProp_t prop;
-  if (hipGetDeviceProperties(&prop, device) == hipSuccess) s->n_cu = prop.multiProcessorCount;
-  s->family = new std::atomic<int>(1);
+  if (hipGetDeviceProperties(&prop, device) == hipSuccess) sh->n_cu = prop.multiProcessorCount;
   *out = s;
   return PT_OK;
 }
 
-// A second handle on the same scene: it shares the tables pt_scene_upload made (nothing a launch writes) and has its
-// own per-camera constants, queues, counters, workspace, stream and events -- so frames rendered through different
-// handles of a family may be in flight at the same time, each on its own stream (include/ptrace.h).
+// A second handle on the same scene: it takes a reference on the block pt_scene_upload made (nothing a launch writes) and
+// has its own per-camera constants, queues, counters, workspace, stream and events -- so frames rendered through different
+// handles of a scene may be in flight at the same time, each on its own stream (include/ptrace.h).
 extern "C" int pt_scene_clone(pt_scene *src, pt_scene **out) {
   if (!src || !out) return fail(PT_ERR_INVALID, "null argument");
   *out = nullptr;
   HIP_TRY(hipSetDevice(src->device));
   pt_scene *s = new pt_scene();
-  // what describes the scene
   s->device = src->device;
-  s->n_shapes = src->n_shapes; s->n_spheres = src->n_spheres; s->n_lights = src->n_lights; s->n_textures = src->n_textures;
-  s->recs = src->recs; s->aux = src->aux; s->diag = src->diag; s->bounds = src->bounds;
-  s->grid_cells = src->grid_cells; s->grid_occ = src->grid_occ; s->grid_balls = src->grid_balls; s->grid_slots = src->grid_slots;
-  s->grid_always = src->grid_always; s->grid_n_always = src->grid_n_always; s->grid_n_cells = src->grid_n_cells;
-  s->grid_far_eo = src->grid_far_eo;
-  for (int q = 0; q < 3; ++q) {
-    s->grid_res[q] = src->grid_res[q]; s->grid_min[q] = src->grid_min[q]; s->grid_max[q] = src->grid_max[q];
-    s->grid_cell[q] = src->grid_cell[q]; s->grid_inv[q] = src->grid_inv[q]; s->bs_rmax[q] = src->bs_rmax[q];
-  }
-  s->bsoa = src->bsoa; s->bs_stride = src->bs_stride; s->gs_stride = src->gs_stride; s->cs_stride = src->cs_stride;
-  s->bs_levels = src->bs_levels; s->n_diag = src->n_diag;
-  s->lights = src->lights; s->tex = src->tex; s->tex_data = src->tex_data;
-  s->dome_cands = src->dome_cands;
-  s->n_cu = src->n_cu;
+  s->sh = src->sh;
+  s->sh->refs.fetch_add(1);
   s->count_rays = src->count_rays; s->dome_shortcut = src->dome_shortcut; s->timing = src->timing;
-  s->family = src->family;
-  s->family->fetch_add(1);
-  // what is this handle's own
   int rc = PT_OK;
-  const size_t nh = (size_t)std::max(s->n_shapes, 1), nd = (size_t)std::max(s->n_diag, 1);
+  const size_t nh = (size_t)std::max(s->sh->sc.n_shapes, 1), nd = (size_t)std::max(s->sh->sc.n_diag, 1);
   if (hipMalloc((void **)&s->hoist, nh * sizeof(PtHoist)) != hipSuccess || hipMalloc((void **)&s->hoist_diag, nd * sizeof(PtHoistDiag)) != hipSuccess) {
-    pt_scene_free(s);
+    pt_scene_free(s);  // (drops the reference: the tables stay with the handles that still use them)
     return fail(PT_ERR_NOMEM, "hipMalloc(per-camera constants) failed");
   }
   if ((rc = handle_state(s))) return rc;
@@ -914,8 +352,8 @@ extern "C" int pt_set_count_rays(pt_scene *s, int enable) {
   return PT_OK;
 }
 
-static int check_params(const pt_scene *s, const pt_camera *cam, const pt_params *p) {
-  if (!s || !cam || !p) return fail(PT_ERR_INVALID, "null argument");
+static int check_params(const pt_camera *cam, const pt_params *p) {
+  if (!cam || !p) return fail(PT_ERR_INVALID, "null argument");
   if (p->width <= 0 || p->height <= 0) return fail(PT_ERR_INVALID, "bad image size %dx%d", p->width, p->height);
   if (p->samples_per_side < 0 || p->samples_per_side > 1024)
     return fail(PT_ERR_INVALID, "bad samples_per_side %d", p->samples_per_side);
@@ -992,42 +430,44 @@ static void fill_cone_model(PtKArgs &a, const pt_camera *cam, int width, int hei
 
 // the scene's tables as the kernels see them (launch(); the probes of ptrace_debug.h)
 static void fill_scene_args(const pt_scene *s, PtKArgs &a) {
-  a.recs = s->recs;
-  a.aux = s->aux;
+  const PtSceneShared &sh = *s->sh;
+  const PtSceneScalars &sc = sh.sc;
+  a.recs = sh.recs;
+  a.aux = sh.aux;
   a.hoist = s->hoist;
-  a.diag = s->diag;
+  a.diag = sh.diag;
   a.hoist_diag = s->hoist_diag;
   a.queue = s->queue;
-  a.bounds = s->bounds;
-  a.bsoa = s->bsoa;
-  a.bs_stride = s->bs_stride;
-  for (int q = 0; q < 3; ++q) a.bs_rmax[q] = s->bs_rmax[q];
-  a.gs_stride = s->gs_stride;
-  a.cs_stride = s->cs_stride;
-  a.bs_levels = s->bs_levels && s->n_spheres >= pt_tuning().levels_min;
-  a.grid_cells = s->grid_cells;
-  a.grid_occ = s->grid_occ;
-  a.grid_balls = s->grid_balls;
-  a.grid_slots = s->grid_slots;
-  a.grid_always = s->grid_always;
-  a.grid_n_always = s->grid_n_always;
-  a.grid_far_eo = s->grid_far_eo;
+  a.bounds = sh.bounds;
+  a.bsoa = sh.bsoa;
+  a.bs_stride = sc.bs_stride;
+  for (int q = 0; q < 3; ++q) a.bs_rmax[q] = sc.bs_rmax[q];
+  a.gs_stride = sc.gs_stride;
+  a.cs_stride = sc.cs_stride;
+  a.bs_levels = sc.bs_levels && sc.n_spheres >= pt_tuning().levels_min;
+  a.grid_cells = sh.grid_cells;
+  a.grid_occ = sh.grid_occ;
+  a.grid_balls = sh.grid_balls;
+  a.grid_slots = sh.grid_slots;
+  a.grid_always = sh.grid_always;
+  a.grid_n_always = sc.grid_n_always;
+  a.grid_far_eo = sc.grid_far_eo;
   a.grid_occ_lds = -1;
   a.scene_lds = -1;
   for (int q = 0; q < 3; ++q) {
-    a.grid_res[q] = s->grid_res[q];
-    a.grid_min[q] = s->grid_min[q];
-    a.grid_max[q] = s->grid_max[q];
-    a.grid_cell[q] = s->grid_cell[q];
-    a.grid_inv[q] = s->grid_inv[q];
+    a.grid_res[q] = sc.grid_res[q];
+    a.grid_min[q] = sc.grid_min[q];
+    a.grid_max[q] = sc.grid_max[q];
+    a.grid_cell[q] = sc.grid_cell[q];
+    a.grid_inv[q] = sc.grid_inv[q];
   }
-  a.n_diag = s->n_diag;
-  a.lights = s->lights;
-  a.tex = s->tex;
-  a.tex_data = s->tex_data;
-  a.n_shapes = s->n_shapes;
-  a.n_spheres = s->n_spheres;
-  a.n_lights = s->n_lights;
+  a.n_diag = sc.n_diag;
+  a.lights = sh.lights;
+  a.tex = sh.tex;
+  a.tex_data = sh.tex_data;
+  a.n_shapes = sc.n_shapes;
+  a.n_spheres = sc.n_spheres;
+  a.n_lights = sc.n_lights;
 }
 
 static_assert(PT_PLAN_BLOCK == PT_BLOCK && PT_PLAN_REGION == PT_REGION && PT_PLAN_CELL == PT_CELL && PT_PLAN_CELL_CHUNK == PT_CELL_CHUNK &&
@@ -1046,6 +486,21 @@ static int ensure(T **ptr, size_t *have, size_t need, hipStream_t st) {
   *have = 0;
   HIP_TRY(hipMalloc((void **)ptr, need * sizeof(T)));
   *have = need;
+  return PT_OK;
+}
+
+// The cold half of the argument block is read from device memory: refresh the copy when it changed
+// (the output pointer stays a by-value argument: double-buffered frames alternate it every launch).
+static int refresh_cold(ColdArgs &c, const PtKArgs &a, hipStream_t st) {
+  PtKArgs cold = a;
+  cold.out = nullptr;
+  cold.qpar = 0;
+  if (c.valid && c.stream == st && memcmp(&c.last, &cold, sizeof cold) == 0) return PT_OK;
+  // pageable source: the runtime stages the bytes before returning, so `cold` may go out of scope
+  HIP_TRY(hipMemcpyAsync(c.dev, &cold, sizeof cold, hipMemcpyHostToDevice, st));
+  c.last = cold;
+  c.valid = true;
+  c.stream = st;
   return PT_OK;
 }
 
@@ -1141,8 +596,8 @@ static int launch(pt_scene *s, const pt_camera *cam, const pt_params *p, void *o
     w.x = o.x * cam->m[0] + o.y * cam->m[1] + o.z * cam->m[2] + cam->m[3];
     w.y = o.x * cam->m[4] + o.y * cam->m[5] + o.z * cam->m[6] + cam->m[7];
     w.z = o.x * cam->m[8] + o.y * cam->m[9] + o.z * cam->m[10] + cam->m[11];
-    hipLaunchKernelGGL(pt_prep_hoist, dim3((s->n_shapes + 255) / 256), dim3(256), 0, st, s->recs, s->hoist,
-                       s->hoist_diag, s->n_shapes, s->n_diag, w);
+    hipLaunchKernelGGL(pt_prep_hoist, dim3((a.n_shapes + 255) / 256), dim3(256), 0, st, a.recs, s->hoist,
+                       s->hoist_diag, a.n_shapes, a.n_diag, w);
     s->hoist_cam = *cam;
     s->hoist_valid = true;
     s->hoist_stream = st;
@@ -1180,29 +635,17 @@ static int launch(pt_scene *s, const pt_camera *cam, const pt_params *p, void *o
 
   // path tracer: per-region masks/keys from the first pass, work units for the second from pt_unit_scatter
   if (pl.path_tiled) {
-    if (pl.nregions > s->region_cap || pl.units_need > s->units_cap) {
-      HIP_TRY(hipStreamSynchronize(st));
-      if (s->region_keys) HIP_TRY(hipFree(s->region_keys));
-      if (s->units) HIP_TRY(hipFree(s->units));
-      if (s->region_mask) HIP_TRY(hipFree(s->region_mask));
-      s->region_keys = nullptr;
-      s->units = nullptr;
-      s->region_mask = nullptr;
-      s->region_cap = 0;
-      s->units_cap = 0;
-      HIP_TRY(hipMalloc((void **)&s->region_keys, (size_t)pl.nregions));
-      HIP_TRY(hipMalloc((void **)&s->units, (size_t)pl.units_need * sizeof(int4)));
-      HIP_TRY(hipMalloc((void **)&s->region_mask, (size_t)pl.nregions * sizeof(unsigned long long)));
-      s->region_cap = pl.nregions;
-      s->units_cap = pl.units_need;
-    }
+    int rc = ensure(&s->region_keys, &s->region_keys_cap, (size_t)pl.nregions, st);
+    if (!rc) rc = ensure(&s->region_mask, &s->region_mask_cap, (size_t)pl.nregions, st);
+    if (!rc) rc = ensure(&s->units, &s->units_cap, (size_t)pl.units_need, st);
+    if (rc) return rc;
     a.units = s->units;
     a.region_keys = s->region_keys;
     a.region_mask = s->region_mask;
     a.spec_draws = pl.spec_draws;
     a.tree_jump_lds = pl.tree_jump_lds;
     if (pl.q_alt) {
-      int rc = ensure(&s->handover, &s->handover_doubles, pl.handover_doubles, st);
+      rc = ensure(&s->handover, &s->handover_doubles, pl.handover_doubles, st);
       if (rc) return rc;
       rc = ensure(&s->units_handed, &s->units_handed_n, (size_t)pl.handover_cap, st);
       if (rc) return rc;
@@ -1223,7 +666,7 @@ static int launch(pt_scene *s, const pt_camera *cam, const pt_params *p, void *o
       const double ox = -cam->screen_distance * cam->m[0] + cam->m[3], oy = -cam->screen_distance * cam->m[4] + cam->m[7],
                    oz = -cam->screen_distance * cam->m[8] + cam->m[11];
       double best = -0.5;
-      for (const auto &dc : s->dome_cands) {
+      for (const auto &dc : s->sh->dome_cands) {
         const double *m = dc.invm;
         const double px = ox * m[0] + oy * m[1] + oz * m[2] + m[3], py = ox * m[4] + oy * m[5] + oz * m[6] + m[7],
                      pz = ox * m[8] + oy * m[9] + oz * m[10] + m[11];
@@ -1237,38 +680,16 @@ static int launch(pt_scene *s, const pt_camera *cam, const pt_params *p, void *o
   }
   // large scenes: two-level culling (cells of PT_CELL x PT_CELL global pixels, then 8x8 tiles)
   if (pl.hier) {
-    const size_t need = (size_t)pl.ncells * pl.cell_stride;
-    if (need > s->cell_list_cap || pl.ncells > s->cell_count_cap) {
-      HIP_TRY(hipStreamSynchronize(st));
-      if (s->cell_list) HIP_TRY(hipFree(s->cell_list));
-      if (s->cell_count) HIP_TRY(hipFree(s->cell_count));
-      s->cell_list = nullptr;
-      s->cell_count = nullptr;
-      s->cell_list_cap = 0;
-      s->cell_count_cap = 0;
-      HIP_TRY(hipMalloc((void **)&s->cell_list, need * sizeof(unsigned int)));
-      HIP_TRY(hipMalloc((void **)&s->cell_count, (size_t)pl.ncells * sizeof(int)));
-      s->cell_list_cap = need;
-      s->cell_count_cap = pl.ncells;
-    }
+    int rc = ensure(&s->cell_list, &s->cell_list_cap, (size_t)pl.ncells * pl.cell_stride, st);
+    if (!rc) rc = ensure(&s->cell_count, &s->cell_count_cap, (size_t)pl.ncells, st);
+    if (rc) return rc;
     a.cell_list = s->cell_list;
     a.cell_count = s->cell_count;
     a.cells_x = pl.cells_x;
     a.cell_stride = pl.cell_stride;
   }
-  // the cold half of the argument block is read from device memory: refresh the copy when it changed
-  // (the output pointer stays a by-value argument: double-buffered frames alternate it every launch)
-  a.cold = s->args_dev;
-  PtKArgs cold = a;
-  cold.out = nullptr;
-  cold.qpar = 0;
-  if (!(s->args_valid && s->args_stream == st && memcmp(&s->args_last, &cold, sizeof cold) == 0)) {
-    // pageable source: the runtime stages the bytes before returning, so `cold` may go out of scope
-    HIP_TRY(hipMemcpyAsync(s->args_dev, &cold, sizeof cold, hipMemcpyHostToDevice, st));
-    s->args_last = cold;
-    s->args_valid = true;
-    s->args_stream = st;
-  }
+  a.cold = s->args.dev;
+  if (int rc = refresh_cold(s->args, a, st)) return rc;
   const void *main_fn = nullptr;  // the render kernel proper (the last one launched), for pt_stats.vgprs
   const bool prof = s->timing && s->profiling && (size_t)(2 * s->prof_used + 1) < s->prof.size();
   const hipEvent_t ev_a = s->timing ? (prof ? s->prof[2 * s->prof_used] : s->ev0) : nullptr;
@@ -1353,16 +774,16 @@ static int launch(pt_scene *s, const pt_camera *cam, const pt_params *p, void *o
       // second pass: the pixels the first one flagged, fullest regions first
       if (pl.tree)  // one pixel per unit: "64 lanes per pixel, whatever the number of flagged pixels"
         hipLaunchKernelGGL(pt_unit_scatter, dim3(pl.grid_scatter), dim3(PT_SCATTER_BLOCK), 0, st, s->region_keys, s->region_mask, pl.nregions,
-                           s->units, s->units_cap, s->queue_last, (long long)1 << 60, 64, 1, pl.q_min, pl.q_budget_per_flagged, pl.q_budget_min);
+                           s->units, (int)s->units_cap, s->queue_last, (long long)1 << 60, 64, 1, pl.q_min, pl.q_budget_per_flagged, pl.q_budget_min);
       else
         hipLaunchKernelGGL(pt_unit_scatter, dim3(pl.grid_scatter), dim3(PT_SCATTER_BLOCK), 0, st, s->region_keys, s->region_mask, pl.nregions,
-                           s->units, s->units_cap, s->queue_last, pl.lanes_cap, pl.nsamp, (long long)pl.min_rounds);
+                           s->units, (int)s->units_cap, s->queue_last, pl.lanes_cap, pl.nsamp, (long long)pl.min_rounds);
       if (pl.q_alt) {
         // num_of_rays > 1: the one-queue kernel IN FRONT of the tree kernel, with an argument block of its own (a lane per
         // pixel: 20 doubles per depth and lane, its own grid, its own slots for the ray counts); it returns at once unless
         // PT_Q_CHOICE says 1, and then leaves the pixels over its budget to the tree kernel behind it (PT_Q_HEAVY)
         PtKArgs aq = a;
-        aq.cold = s->args_dev2;
+        aq.cold = s->args2.dev;
         aq.nthreads = pl.grid_q * PT_BLOCK;
         aq.frame_doubles = 20;
         aq.p_max_path = pl.q_p_max_path;
@@ -1375,15 +796,7 @@ static int launch(pt_scene *s, const pt_camera *cam, const pt_params *p, void *o
         aq.grid_occ_lds = -1;
         aq.diag_lds = pl.q_diag_lds;
         aq.ws = s->ws;
-        PtKArgs cold2 = aq;
-        cold2.out = nullptr;
-        cold2.qpar = 0;
-        if (!(s->args2_valid && s->args2_stream == st && memcmp(&s->args2_last, &cold2, sizeof cold2) == 0)) {
-          HIP_TRY(hipMemcpyAsync(s->args_dev2, &cold2, sizeof cold2, hipMemcpyHostToDevice, st));
-          s->args2_last = cold2;
-          s->args2_valid = true;
-          s->args2_stream = st;
-        }
+        if (int rc = refresh_cold(s->args2, aq, st)) return rc;
 #define PT_ALT(K_)                                              \
   do {                                                          \
     HIP_TRY(path_lds_limit((const void *)(K_), pl.lds_q));      \
@@ -1513,19 +926,14 @@ static int fold_stats(pt_scene *s) {
   return PT_OK;
 }
 
-extern "C" int pt_render_device(pt_scene *s, const pt_camera *cam, const pt_params *p, void *out_dev,
-                                size_t out_bytes, void *stream) {
-  int rc = check_params(s, cam, p);
-  if (rc) return rc;
-  const size_t need = pt_output_bytes(p);
-  if (out_bytes < need) return fail(PT_ERR_SIZE, "output buffer too small: %zu < %zu bytes", out_bytes, need);
-  if (need > 0 && !out_dev) return fail(PT_ERR_INVALID, "null output buffer");
+// a frame (hits_channels >= 0: a hit-record frame) into a device buffer: asynchronous when the caller names a stream
+static int render_to_device(pt_scene *s, const pt_camera *cam, const pt_params *p, void *out_dev, void *stream, int hits_channels = -1) {
   HIP_TRY(hipSetDevice(s->device));
   // an earlier asynchronous render that was never synchronised simply loses its statistics:
   // folding them here would block the host on the device every frame
   s->pending = false;
   hipStream_t st = stream ? (hipStream_t)stream : s->stream;
-  rc = launch(s, cam, p, out_dev, st);
+  int rc = launch(s, cam, p, out_dev, st, hits_channels);
   if (rc) return rc;
   if (s->stats.n_pixels > 0) {
     s->pending = true;
@@ -1533,6 +941,36 @@ extern "C" int pt_render_device(pt_scene *s, const pt_camera *cam, const pt_para
   }
   if (!stream) return pt_sync(s);
   return PT_OK;
+}
+
+// ... and into a host buffer of `need` bytes, through the handle's staging buffer: kernel + copy, synchronised
+static int render_to_host(pt_scene *s, const pt_camera *cam, const pt_params *p, void *out_host, size_t need, int hits_channels = -1) {
+  HIP_TRY(hipSetDevice(s->device));
+  int rc = s->pending ? fold_stats(s) : PT_OK;
+  if (rc) return rc;
+  if ((rc = ensure(&s->out_dev, &s->out_dev_bytes, need, s->stream))) return rc;
+  rc = launch(s, cam, p, s->out_dev, s->stream, hits_channels);
+  if (rc) return rc;
+  if (need > 0) {
+    // (a hit-record frame: the padding behind the shape plane is the only part no lane writes, the copy carries whatever the buffer held)
+    HIP_TRY(hipMemcpyAsync(out_host, s->out_dev, need, hipMemcpyDeviceToHost, s->stream));
+    HIP_TRY(hipEventRecord(s->ev2, s->stream));
+    s->pending = true;
+    s->pending_copy = true;
+  }
+  HIP_TRY(hipStreamSynchronize(s->stream));
+  return fold_stats(s);
+}
+
+extern "C" int pt_render_device(pt_scene *s, const pt_camera *cam, const pt_params *p, void *out_dev,
+                                size_t out_bytes, void *stream) {
+  if (!s) return fail(PT_ERR_INVALID, "null argument");
+  int rc = check_params(cam, p);
+  if (rc) return rc;
+  const size_t need = pt_output_bytes(p);
+  if (out_bytes < need) return fail(PT_ERR_SIZE, "output buffer too small: %zu < %zu bytes", out_bytes, need);
+  if (need > 0 && !out_dev) return fail(PT_ERR_INVALID, "null output buffer");
+  return render_to_device(s, cam, p, out_dev, stream);
 }
 
 extern "C" int pt_sync(pt_scene *s) {
@@ -1543,33 +981,13 @@ extern "C" int pt_sync(pt_scene *s) {
 
 extern "C" int pt_render(pt_scene *s, const pt_camera *cam, const pt_params *p, void *out_host,
                          size_t out_bytes) {
-  int rc = check_params(s, cam, p);
+  if (!s) return fail(PT_ERR_INVALID, "null argument");
+  int rc = check_params(cam, p);
   if (rc) return rc;
   const size_t need = pt_output_bytes(p);
   if (out_bytes < need) return fail(PT_ERR_SIZE, "output buffer too small: %zu < %zu bytes", out_bytes, need);
   if (need > 0 && !out_host) return fail(PT_ERR_INVALID, "null output buffer");
-  HIP_TRY(hipSetDevice(s->device));
-  if (s->pending) {
-    rc = fold_stats(s);
-    if (rc) return rc;
-  }
-  if (need > s->out_dev_bytes) {
-    if (s->out_dev) HIP_TRY(hipFree(s->out_dev));
-    s->out_dev = nullptr;
-    s->out_dev_bytes = 0;
-    HIP_TRY(hipMalloc(&s->out_dev, need));
-    s->out_dev_bytes = need;
-  }
-  rc = launch(s, cam, p, s->out_dev, s->stream);
-  if (rc) return rc;
-  if (need > 0) {
-    HIP_TRY(hipMemcpyAsync(out_host, s->out_dev, need, hipMemcpyDeviceToHost, s->stream));
-    HIP_TRY(hipEventRecord(s->ev2, s->stream));
-    s->pending = true;
-    s->pending_copy = true;
-  }
-  HIP_TRY(hipStreamSynchronize(s->stream));
-  return fold_stats(s);
+  return render_to_host(s, cam, p, out_host, need);
 }
 
 // ---- hit-record frames (include/ptrace.h, ABI 1.6) -------------------------------------------------------------------
@@ -1626,7 +1044,7 @@ static int hits_check(pt_scene *s, const pt_camera *cam, const pt_params *p, int
   if (!s || !cam || !p) return fail(PT_ERR_INVALID, "null argument");
   if (!hits_channels_ok(channels)) return fail(PT_ERR_INVALID, "unknown hit channel bits %#x", channels);
   q = hits_params(p);
-  int rc = check_params(s, cam, &q);
+  int rc = check_params(cam, &q);
   if (rc) return rc;
   const size_t need = pt_hits_bytes(&q, channels);
   if (out_bytes < need) return fail(PT_ERR_SIZE, "hit-record buffer too small: %zu < %zu bytes", out_bytes, need);
@@ -1639,17 +1057,7 @@ extern "C" int pt_render_hits_device(pt_scene *s, const pt_camera *cam, const pt
   pt_params q;
   int rc = hits_check(s, cam, p, channels, out_dev, out_bytes, q);
   if (rc) return rc;
-  HIP_TRY(hipSetDevice(s->device));
-  s->pending = false;  // (as pt_render_device: an unsynchronised earlier render loses its statistics)
-  hipStream_t st = stream ? (hipStream_t)stream : s->stream;
-  rc = launch(s, cam, &q, out_dev, st, channels);
-  if (rc) return rc;
-  if (s->stats.n_pixels > 0) {
-    s->pending = true;
-    s->pending_copy = false;
-  }
-  if (!stream) return pt_sync(s);
-  return PT_OK;
+  return render_to_device(s, cam, &q, out_dev, stream, channels);
 }
 
 extern "C" int pt_render_hits(pt_scene *s, const pt_camera *cam, const pt_params *p, int channels, void *out_host,
@@ -1657,30 +1065,7 @@ extern "C" int pt_render_hits(pt_scene *s, const pt_camera *cam, const pt_params
   pt_params q;
   int rc = hits_check(s, cam, p, channels, out_host, out_bytes, q);
   if (rc) return rc;
-  const size_t need = pt_hits_bytes(&q, channels);
-  HIP_TRY(hipSetDevice(s->device));
-  if (s->pending) {
-    rc = fold_stats(s);
-    if (rc) return rc;
-  }
-  if (need > s->out_dev_bytes) {
-    if (s->out_dev) HIP_TRY(hipFree(s->out_dev));
-    s->out_dev = nullptr;
-    s->out_dev_bytes = 0;
-    HIP_TRY(hipMalloc(&s->out_dev, need));
-    s->out_dev_bytes = need;
-  }
-  rc = launch(s, cam, &q, s->out_dev, s->stream, channels);
-  if (rc) return rc;
-  if (need > 0) {
-    // (the padding behind the shape plane is the only part no lane writes: the copy carries whatever the buffer held)
-    HIP_TRY(hipMemcpyAsync(out_host, s->out_dev, need, hipMemcpyDeviceToHost, s->stream));
-    HIP_TRY(hipEventRecord(s->ev2, s->stream));
-    s->pending = true;
-    s->pending_copy = true;
-  }
-  HIP_TRY(hipStreamSynchronize(s->stream));
-  return fold_stats(s);
+  return render_to_host(s, cam, &q, out_host, pt_hits_bytes(&q, channels), channels);
 }
 
 // Page-locked host memory for pt_render's output: the D2H copy then is one DMA at link speed into the
@@ -2086,14 +1471,11 @@ extern "C" int pt_debug_plan(const pt_scene_desc *desc, const pt_camera *cam, co
   if (!out) return fail(PT_ERR_INVALID, "null argument");
   int rc = check_desc(desc);
   if (rc) return rc;
-  pt_scene tmp;  // (a bag of facts here: no HIP call touches it)
-  HostTables h;
-  analyse_scene(desc, pt_tuning(), &tmp, h);
-  tmp.n_cu = n_cu > 0 ? n_cu : 256;
-  tmp.dome_shortcut = dome_shortcut != 0;
-  rc = check_params(&tmp, cam, p);
+  PtSceneHost h;
+  pt_build_scene(desc, pt_tuning(), h);
+  rc = check_params(cam, p);
   if (rc) return rc;
-  const PtSceneFacts f = scene_facts(&tmp);
+  const PtSceneFacts f = pt_scene_facts(h.sc, n_cu > 0 ? n_cu : 256, dome_shortcut != 0);
   PtPlan pl;
   pt_make_plan(f, cam, p, pt_tuning(), pl);
   plan_info(pl, f, p, out);
@@ -2106,14 +1488,12 @@ extern "C" int pt_debug_plan_hits(const pt_scene_desc *desc, const pt_camera *ca
   if (!hits_channels_ok(channels)) return fail(PT_ERR_INVALID, "unknown hit channel bits %#x", channels);
   int rc = check_desc(desc);
   if (rc) return rc;
-  pt_scene tmp;  // (a bag of facts here: no HIP call touches it)
-  HostTables h;
-  analyse_scene(desc, pt_tuning(), &tmp, h);
-  tmp.n_cu = n_cu > 0 ? n_cu : 256;
+  PtSceneHost h;
+  pt_build_scene(desc, pt_tuning(), h);
   const pt_params q = hits_params(p);
-  rc = check_params(&tmp, cam, &q);
+  rc = check_params(cam, &q);
   if (rc) return rc;
-  const PtSceneFacts f = scene_facts(&tmp);
+  const PtSceneFacts f = pt_scene_facts(h.sc, n_cu > 0 ? n_cu : 256, true);
   PtPlan pl;
   bool cull = false;
   pt_make_hits_plan(f, cam, &q, pt_tuning(), pl, cull);
@@ -2127,8 +1507,8 @@ extern "C" int pt_debug_plan_hits(const pt_scene_desc *desc, const pt_camera *ca
 }
 
 extern "C" int pt_debug_plan_scene(pt_scene *s, const pt_camera *cam, const pt_params *p, pt_plan_info *out) {
-  if (!out) return fail(PT_ERR_INVALID, "null argument");
-  int rc = check_params(s, cam, p);
+  if (!out || !s) return fail(PT_ERR_INVALID, "null argument");
+  int rc = check_params(cam, p);
   if (rc) return rc;
   const PtSceneFacts f = scene_facts(s);
   PtPlan pl;
@@ -2247,16 +1627,16 @@ extern "C" int pt_debug_cull_probe(pt_scene *s, const pt_camera *cam, int width,
   PtKArgs *a_dev = nullptr;
   int *keep_dev = nullptr;
   HIP_TRY(hipMalloc((void **)&a_dev, sizeof a));
-  HIP_TRY(hipMalloc((void **)&keep_dev, sizeof(int) * std::max(1, s->n_shapes)));
+  HIP_TRY(hipMalloc((void **)&keep_dev, sizeof(int) * std::max(1, s->sh->sc.n_shapes)));
   a.cold = a_dev;
-  a.recs = s->recs;
-  a.bounds = s->bounds;
-  a.n_shapes = s->n_shapes;
-  a.n_spheres = s->n_spheres;
+  a.recs = s->sh->recs;
+  a.bounds = s->sh->bounds;
+  a.n_shapes = s->sh->sc.n_shapes;
+  a.n_spheres = s->sh->sc.n_spheres;
   HIP_TRY(hipMemcpy(a_dev, &a, sizeof a, hipMemcpyHostToDevice));
   hipLaunchKernelGGL(pt_cull_probe_kernel, dim3(1), dim3(64), 0, 0, a, x0, x1, row0, row1, pixel_x, pixel_row, keep_dev);
   HIP_TRY(hipGetLastError());
-  HIP_TRY(hipMemcpy(keep, keep_dev, sizeof(int) * s->n_shapes, hipMemcpyDeviceToHost));
+  HIP_TRY(hipMemcpy(keep, keep_dev, sizeof(int) * a.n_shapes, hipMemcpyDeviceToHost));
   (void)hipFree(a_dev);
   (void)hipFree(keep_dev);
   return PT_OK;
@@ -2283,16 +1663,16 @@ extern "C" int pt_debug_probe(int op, const double *x, const double *y, double *
 
 // ---- diagnostics: the hit record, camera rays and BRDF scattering of the device path on their own ----------------
 extern "C" int pt_debug_hit_probe(pt_scene *s, int shape_index, const double *rays, int n, double *out) {
-  if (!s || !rays || !out || n <= 0 || shape_index >= s->n_shapes) return fail(PT_ERR_INVALID, "bad probe arguments");
+  if (!s || !rays || !out || n <= 0 || shape_index >= s->sh->sc.n_shapes) return fail(PT_ERR_INVALID, "bad probe arguments");
   HIP_TRY(hipSetDevice(s->device));
   PtKArgs a;
   memset(&a, 0, sizeof a);
-  a.recs = s->recs;
-  a.aux = s->aux;
-  a.diag = s->diag;
-  a.n_shapes = s->n_shapes;
-  a.n_spheres = s->n_spheres;
-  a.n_diag = s->n_diag;
+  a.recs = s->sh->recs;
+  a.aux = s->sh->aux;
+  a.diag = s->sh->diag;
+  a.n_shapes = s->sh->sc.n_shapes;
+  a.n_spheres = s->sh->sc.n_spheres;
+  a.n_diag = s->sh->sc.n_diag;
   double *rd = nullptr, *od = nullptr;
   HIP_TRY(hipMalloc((void **)&rd, (size_t)n * 8 * sizeof(double)));
   HIP_TRY(hipMalloc((void **)&od, (size_t)n * 12 * sizeof(double)));

@@ -1233,3 +1233,25 @@ def test_cloned_handles_share_the_scene_and_outlive_the_first(dev):
             assert h.stats().n_rays > 0
         for h in (clones[1], grand, clones[0]):
             h.close()
+
+
+def test_a_clone_grows_its_own_workspace_from_a_small_frame_to_a_larger_one(dev):
+    """The grow-only buffers of a handle (region keys, masks and units, the frame stack, the hand-over tables) are the
+    handle's own: a clone that renders num_of_rays > 1 at 64x48 and then at 160x96 reallocates them on its second frame,
+    and both frames equal the first handle's bit for bit -- whichever of the two rendered first."""
+    from pytracer_amd import flatten, scenes
+
+    flat = flatten.flatten_world(scenes.synthetic_world(32, with_plane=True))
+    sizes = ((64, 48), (160, 96))
+    cams = [flatten.flatten_camera(scenes.synthetic_camera(W, H)) for W, H in sizes]
+    pars = [abi.make_params(W, H, abi.RENDERER_PATHTRACER, samples_per_side=1, num_of_rays=3, max_depth=3, path_state=45, path_seq=54)
+            for W, H in sizes]
+    with dev.DeviceScene(flat) as first:
+        clone = first.clone()
+        small = clone.render(cams[0], pars[0])
+        large = clone.render(cams[1], pars[1])  # (grows every buffer the small frame sized)
+        assert util.bits_equal(large, first.render(cams[1], pars[1]))
+        assert util.bits_equal(small, first.render(cams[0], pars[0]))  # (the first handle: large, then small -- nothing shrinks)
+        assert util.bits_equal(small, clone.render(cams[0], pars[0]))
+        assert clone.stats().n_rays > 0
+        clone.close()
