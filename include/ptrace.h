@@ -126,7 +126,7 @@ typedef struct pt_params {
   int32_t max_depth;        /* PathTracer.max_depth (render.py:96)                       */
   int32_t rr_limit;         /* PathTracer.russian_roulette_limit (render.py:97)          */
   int32_t pcg_mode;         /* PT_PCG_*                                                  */
-  uint64_t jitter_state, jitter_seq; /* ImageTracer.pcg seeds (SEQ mode only; < 2^63)    */
+  uint64_t jitter_state, jitter_seq; /* ImageTracer.pcg seeds (SEQ mode only)            */
   uint64_t path_state, path_seq;     /* PathTracer.pcg seeds (SEQ) / S0,Q0 (PIXEL, SAMPLE) */
   /* Pixel partition for multi-GPU: rows are cut in blocks of `row_block` rows, block b belongs
    * to rank b % n_ranks; a rank's output holds its rows compactly in ascending global order.

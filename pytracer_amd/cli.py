@@ -102,6 +102,9 @@ def plan_render(width, height, algorithm, num_of_rays, max_depth, init_state, in
     if side * side != samples_per_pixel:
         raise UsageError(f"--samples-per-pixel {samples_per_pixel}: must be a perfect square (1, 4, 9, 16, ...)")
     world, camera, K = _load_scene(input_scene_name, parse_float_overrides(declare_float), width, height)
+    # the seeds are uint64_t at the boundary (include/ptrace.h): any int is taken mod 2^64 here, where every generator class
+    # agrees (pytracer's own PCG raises from its first draw for some negative states, pcg.py:39,58)
+    init_state, init_seq = int(init_state) & (2**64 - 1), int(init_seq) & (2**64 - 1)
     make = {
         "onoff": lambda: K.OnOffRenderer(world=world),
         "flat": lambda: K.FlatRenderer(world=world),

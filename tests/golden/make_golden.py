@@ -170,6 +170,37 @@ def g1_pcg():
          floats=np.array(floats, dtype=np.float64))
 
 
+M64 = (1 << 64) - 1
+# tests/seed_sweep.py: the states of its seed pairs, and sequence numbers either side of 2^32, 2^63 and 2^64
+G15_STATES = [2**32 + 45, 2**64 - 1, 2**63 + 12345, 0x9E3779B97F4A7C15]
+G15_SEQS = [54, 2**32 - 1, 2**32, 2**63 - 1, 2**63, 2**64 - 1]
+G15_OUT_OF_RANGE = [-1, -(2**63), 2**64 + 5, 2**70 + 3]  # ints no uint64_t holds, each as a state and as a sequence number
+
+
+def g15_pcg_wide():
+    """The reference's PCG over the whole 64-bit range of both seeds, and for ints outside it.  The seeds are stored mod
+    2^64 (``seeds``) and as decimal strings (``raw``); the state is masked as the reference's own ``random()`` masks it
+    (its constructor's ``self.state += init_state`` is not masked, and is read by that ``random()`` only).  ``valid`` is 0
+    where the reference's constructor raises instead (a sum below zero there makes the discarded output's rotation a
+    negative shift count: ``PCG(-(2**63), 54)``); such a row holds zeros."""
+    raw = [(s, q) for s in G15_STATES for q in G15_SEQS]
+    raw += [(x, 54) for x in G15_OUT_OF_RANGE] + [(45, x) for x in G15_OUT_OF_RANGE]
+    st, inc, outs, valid = [], [], [], []
+    for s, q in raw:
+        try:
+            p = PCG(s, q)
+        except ValueError:
+            st.append(0), inc.append(0), outs.append([0] * 8), valid.append(0)
+            continue
+        st.append(p.state & M64)
+        inc.append(p.inc & M64)
+        outs.append([p.random() for _ in range(8)])
+        valid.append(1)
+    save("g15_pcg_wide", seeds=np.array([(s & M64, q & M64) for s, q in raw], dtype=np.uint64),
+         raw=np.array([[str(s), str(q)] for s, q in raw]), valid=np.array(valid, dtype=np.uint8),
+         state=np.array(st, dtype=np.uint64), inc=np.array(inc, dtype=np.uint64), outputs=np.array(outs, dtype=np.uint32))
+
+
 def rnd_transform(r):
     t = translation(Vec(4 * r() - 2, 4 * r() - 2, 4 * r() - 2))
     rot = rotation_x(360 * r()) * rotation_y(360 * r()) * rotation_z(360 * r())
@@ -729,7 +760,7 @@ if __name__ == "__main__":
     table = {"g1": g1_pcg, "g2": g2_xform, "g3": g3_shapes, "g4": g4_camera, "g6": g6_g7_scatter_onb,
              "g8": g8_pigments, "g9": g9_furnace, "g5": g5_frames, "g10": g10_postprocess, "g5c4": g5_c4,
              "g5cli": g5_cli, "g5seq": g5_seq, "g5sample": g5_sample, "g11": g11_imagetracer, "g12": g12_families,
-             "g13": g13_planes}
+             "g13": g13_planes, "g15": g15_pcg_wide}
     if argv:
         parses = sum(1 for k in argv if k in ("g5", "g5cli", "g5seq", "g5sample"))
         if parses > 1:
@@ -739,6 +770,6 @@ if __name__ == "__main__":
     else:
         import subprocess
 
-        for k in ["g1", "g2", "g3", "g4", "g6", "g8", "g9", "g5", "g10", "g5cli", "g5c4", "g5seq", "g5sample", "g11", "g12", "g13"]:  # (g10 reads g5's frames)
+        for k in ["g1", "g2", "g3", "g4", "g6", "g8", "g9", "g5", "g10", "g5cli", "g5c4", "g5seq", "g5sample", "g11", "g12", "g13", "g15"]:  # (g10 reads g5's frames)
             subprocess.run([sys.executable, os.path.abspath(__file__), "--out", OUT_DIR, k], check=True,
                            env=dict(os.environ, PYTHONDONTWRITEBYTECODE="1"))
