@@ -415,4 +415,7 @@ def rows_for_rank(height: int, row_block: int, n_ranks: int, rank: int) -> List[
     """Global row indices rank ``rank`` owns (ascending): block b -> rank b % n_ranks."""
     rb = max(1, int(row_block))
     nr = max(1, int(n_ranks))
-    return [r for r in range(height) if (r // rb) % nr == rank]
+    if not 0 <= rank < nr:
+        return []
+    # block by block, not row by row: a rank's share of a frame of 2^26 rows is a handful of rows
+    return [r for b in range(int(rank), -(-int(height) // rb), nr) for r in range(b * rb, min((b + 1) * rb, int(height)))]

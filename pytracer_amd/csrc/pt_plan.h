@@ -194,10 +194,13 @@ static inline int pt_plan_rows(const pt_params *p) {
   if (!p || p->height <= 0) return 0;
   const int rb = p->row_block > 0 ? p->row_block : 1;
   const int nr = p->n_ranks > 0 ? p->n_ranks : 1;
-  int rows = 0;
-  for (int b = 0; b * rb < p->height; ++b)
-    if (b % nr == p->rank) rows += std::min(rb, p->height - b * rb);
-  return rows;
+  // block b belongs to rank b % nr.  In closed form, in 64 bits: a frame of 2^26 rows has millions of blocks, and at heights
+  // near INT_MAX the product b * rb of a loop over the blocks leaves int
+  const long long H = p->height, nb = (H + rb - 1) / rb;
+  if (p->rank < 0 || p->rank >= nr || p->rank >= nb) return 0;
+  long long rows = ((nb - 1 - p->rank) / nr + 1) * rb;
+  if ((nb - 1) % nr == p->rank) rows -= nb * rb - H;  // (the frame's last block may be cut short)
+  return (int)rows;
 }
 
 // Sizes the kernels' records have (pt_layout.h; kept here as numbers so that the plan needs no device header): checked by

@@ -176,15 +176,7 @@ extern "C" int pt_device_info(int device, int *compute_units, int *clock_khz) {
   return PT_OK;
 }
 
-extern "C" int pt_rows_for_rank(const pt_params *p) {
-  if (!p || p->height <= 0) return 0;
-  const int rb = p->row_block > 0 ? p->row_block : 1;
-  const int nr = p->n_ranks > 0 ? p->n_ranks : 1;
-  int rows = 0;
-  for (int b = 0; b * rb < p->height; ++b)
-    if (b % nr == p->rank) rows += std::min(rb, p->height - b * rb);
-  return rows;
-}
+extern "C" int pt_rows_for_rank(const pt_params *p) { return pt_plan_rows(p); }
 
 extern "C" size_t pt_output_bytes(const pt_params *p) {
   if (!p) return 0;

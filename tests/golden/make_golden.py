@@ -750,6 +750,27 @@ def g13_planes():
              **scene.to_dict(), **abi.camera_to_dict(cam))
 
 
+def g16_geometry_rays():
+    """The reference's ``ImageTracer.fire_ray`` at the pixels tests/frame_geometry.py names -- frames of up to 2^26 rows and 2^18
+    columns, so a stand-in image that holds a width and a height (all ``fire_ray`` reads of it): rays[camera, point, offset] =
+    (origin, direction), cameras (perspective, orthogonal) as tests/frame_geometry.py::camera_of builds them."""
+    from types import SimpleNamespace
+
+    from tests import frame_geometry as fg
+
+    cameras = [PerspectiveCamera(screen_distance=1.0, aspect_ratio=fg.ASPECT, transformation=translation(Vec(-1.0, 0.0, 1.0))),
+               OrthogonalCamera(aspect_ratio=fg.ASPECT, transformation=translation(Vec(-1.0, 0.0, 1.5)) * scaling(Vec(1.0, 5.0, 3.0)))]
+    at = fg.ray_points()
+    rays = np.zeros((len(cameras), len(at), len(fg.RAY_OFFSETS), 6))
+    for j, camera in enumerate(cameras):
+        for i, (col, row, w, h) in enumerate(at):
+            tracer = ImageTracer(SimpleNamespace(width=w, height=h), camera)
+            for k, (up, vp) in enumerate(fg.RAY_OFFSETS):
+                ray = tracer.fire_ray(col, row, up, vp)
+                rays[j, i, k] = [ray.origin.x, ray.origin.y, ray.origin.z, ray.dir.x, ray.dir.y, ray.dir.z]
+    save("g16_geometry_rays", at=np.array(at, dtype=np.int64), offsets=np.array(fg.RAY_OFFSETS), rays=rays)
+
+
 if __name__ == "__main__":
     argv = sys.argv[1:]
     if "--out" in argv:
@@ -760,7 +781,7 @@ if __name__ == "__main__":
     table = {"g1": g1_pcg, "g2": g2_xform, "g3": g3_shapes, "g4": g4_camera, "g6": g6_g7_scatter_onb,
              "g8": g8_pigments, "g9": g9_furnace, "g5": g5_frames, "g10": g10_postprocess, "g5c4": g5_c4,
              "g5cli": g5_cli, "g5seq": g5_seq, "g5sample": g5_sample, "g11": g11_imagetracer, "g12": g12_families,
-             "g13": g13_planes, "g15": g15_pcg_wide}
+             "g13": g13_planes, "g15": g15_pcg_wide, "g16": g16_geometry_rays}
     if argv:
         parses = sum(1 for k in argv if k in ("g5", "g5cli", "g5seq", "g5sample"))
         if parses > 1:
@@ -770,6 +791,6 @@ if __name__ == "__main__":
     else:
         import subprocess
 
-        for k in ["g1", "g2", "g3", "g4", "g6", "g8", "g9", "g5", "g10", "g5cli", "g5c4", "g5seq", "g5sample", "g11", "g12", "g13", "g15"]:  # (g10 reads g5's frames)
+        for k in ["g1", "g2", "g3", "g4", "g6", "g8", "g9", "g5", "g10", "g5cli", "g5c4", "g5seq", "g5sample", "g11", "g12", "g13", "g15", "g16"]:  # (g10 reads g5's frames)
             subprocess.run([sys.executable, os.path.abspath(__file__), "--out", OUT_DIR, k], check=True,
                            env=dict(os.environ, PYTHONDONTWRITEBYTECODE="1"))

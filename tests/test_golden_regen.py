@@ -15,7 +15,8 @@ REFERENCE = "/root/reference/src/pytracer"
 @pytest.mark.parametrize("gen,files", [("g1", ["g1_pcg"]), ("g4", ["g4_camera"]),
                                        ("g5cli", ["g5_cli_demo_flat_s1_64x48", "g5_cli_demo_path_s1_32x24_n10d3"]),
                                        ("g12", ["g12_family_" + f for f in ("mirrored", "sheared", "camera", "pigments", "lights", "mixed")]),
-                                       ("g13", ["g13_planes_" + n for n in ("closed", "fan", "coincident")])])
+                                       ("g13", ["g13_planes_" + n for n in ("closed", "fan", "coincident")]),
+                                       ("g16", ["g16_geometry_rays"])])
 def test_regenerated_fixture_equals_the_committed_one(tmp_path, gen, files):
     env = dict(os.environ, PYTHONDONTWRITEBYTECODE="1")
     r = subprocess.run([sys.executable, os.path.join(ROOT, "tests", "golden", "make_golden.py"), "--out", str(tmp_path), gen],
