@@ -246,6 +246,17 @@ int pt_render_hits(pt_scene *scene, const pt_camera *cam, const pt_params *p, in
                    size_t out_bytes);
 int pt_render_hits_device(pt_scene *scene, const pt_camera *cam, const pt_params *p, int channels, void *out_dev,
                           size_t out_bytes, void *stream);
+/* ---- the scene's kernel argument block, for add-on libraries built from the same tree (ABI 1.7) --------------
+ * Fills `out` with the block the kernels take for this scene: the tables pt_scene_upload left in HBM and the
+ * scalars of its analysis, nothing of a camera or a frame.  Its layout is csrc/pt_layout.h's PtKArgs -- not part
+ * of this header, and free to change with every build: the call is meant for libraries compiled from the same tree
+ * as this one, which check the size (out_bytes != sizeof(PtKArgs): PT_ERR_INVALID).  The block's `cold` field points
+ * to a device-resident copy of the same block that the handle owns: made on the first call, kept, freed by
+ * pt_scene_free; a handle from pt_scene_clone has its own.  The tables are immutable after the upload, so kernels
+ * given this block may run on any stream, concurrently with frames of the same scene, until the handle is freed.
+ * The one user today is libptrace_rays.so (include/ptrace_rays.h: closest-hit and any-hit queries for a caller's
+ * own rays), in two calls: this one, then pt_rays_trace or pt_rays_trace_device with the block. */
+int pt_scene_kernel_args(pt_scene *scene, void *out, size_t out_bytes);
 /* Enable (1) / disable (0) the in-kernel ray counter (default on). */
 int pt_set_count_rays(pt_scene *scene, int enable);
 /* Measurement switch: 0 = primary rays are always generated and traced, also where the image can only show
@@ -314,9 +325,9 @@ int pt_last_error(char *buf, size_t n);
  * (pytracer_amd.prefer_device_kernargs(), the `render` command and bench.py do).  A value set after the runtime came up
  * is reported here but has no effect. */
 int pt_device_kernargs(void);
-/* Library/ABI version: (major<<16)|minor; this header describes 1.6.  The minor grows whenever a struct here grows or an
+/* Library/ABI version: (major<<16)|minor; this header describes 1.7.  The minor grows whenever a struct here grows or an
  * entry point is added (1.2: pt_stats gained `kernel` and `_reserved` -- 56 bytes, which pt_get_stats writes in full --,
- * pt_scene_clone, pt_image_sparse_*; 1.3: PT_PCG_SEQ on the device for OnOff / Flat / PointLight; 1.4: pt_device_kernargs, no load-time setenv; 1.5: pt_device_alloc / _free / _download, pt_stream_create / _sync / _destroy; 1.6: pt_hits_bytes, pt_hits_plane_offset, pt_render_hits, pt_render_hits_device): a caller built
+ * pt_scene_clone, pt_image_sparse_*; 1.3: PT_PCG_SEQ on the device for OnOff / Flat / PointLight; 1.4: pt_device_kernargs, no load-time setenv; 1.5: pt_device_alloc / _free / _download, pt_stream_create / _sync / _destroy; 1.6: pt_hits_bytes, pt_hits_plane_offset, pt_render_hits, pt_render_hits_device; 1.7: pt_scene_kernel_args): a caller built
  * against an older header must check pt_version() before it hands pt_get_stats its smaller struct. */
 int pt_version(void);
 

@@ -17,7 +17,7 @@ EXPORTS = ("pt_device_count", "pt_scene_upload", "pt_scene_clone", "pt_scene_fre
            "pt_image_average_luminosity", "pt_image_tonemap", "pt_host_alloc", "pt_host_free", "pt_set_dome_shortcut", "pt_device_info",
            "pt_image_sparse_fixed_bytes", "pt_image_sparse_encode", "pt_image_sparse_decode", "pt_image_sparse_decode_many", "pt_device_kernargs",
            "pt_device_alloc", "pt_device_free", "pt_device_download", "pt_stream_create", "pt_stream_sync", "pt_stream_destroy",
-           "pt_hits_bytes", "pt_hits_plane_offset", "pt_render_hits", "pt_render_hits_device")
+           "pt_hits_bytes", "pt_hits_plane_offset", "pt_render_hits", "pt_render_hits_device", "pt_scene_kernel_args")
 
 
 # every symbol include/ptrace_debug.h declares for ordinary builds (diagnostics: not part of the boundary)
@@ -28,8 +28,9 @@ DEBUG_EXPORTS = ("pt_debug_probe", "pt_debug_cull_probe", "pt_debug_hit_probe", 
 
 # include/ptrace.h: pt_version() = major << 16 | minor; abi.Stats mirrors the 56-byte pt_stats of minor >= 2, the tracer's
 # default alignment needs the PT_PCG_SEQ of minor >= 3, device.device_kernargs() the entry point of minor 4
-# ... devmem.DeviceBuffer / Stream the entry points of minor 5, hits.HitFrame those of minor 6
-ABI_MAJOR, ABI_MINOR_NEEDED = 1, 6
+# ... devmem.DeviceBuffer / Stream the entry points of minor 5, hits.HitFrame those of minor 6, rays (ray batches through
+# libptrace_rays.so) the pt_scene_kernel_args of minor 7
+ABI_MAJOR, ABI_MINOR_NEEDED = 1, 7
 
 
 class PtraceError(RuntimeError):
@@ -174,6 +175,8 @@ def lib():
         L.pt_render_hits.argtypes = [C.c_void_p, P(abi.Camera), P(abi.Params), C.c_int, C.c_void_p, C.c_size_t]
         L.pt_render_hits_device.restype = C.c_int
         L.pt_render_hits_device.argtypes = [C.c_void_p, P(abi.Camera), P(abi.Params), C.c_int, C.c_void_p, C.c_size_t, C.c_void_p]
+        L.pt_scene_kernel_args.restype = C.c_int
+        L.pt_scene_kernel_args.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t]
         # diagnostics (include/ptrace_debug.h): bound when the build carries them -- a renderer never needs one
         if hasattr(L, "pt_debug_cull_probe"):
             L.pt_debug_cull_probe.restype = C.c_int

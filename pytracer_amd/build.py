@@ -1,8 +1,12 @@
-"""Build recipe for libptrace.so (HIP, gfx950 only).
+"""Build recipe for libptrace.so and its add-on libptrace_rays.so (HIP, gfx950 only).
 
 ``hipcc --offload-arch=gfx950 -O3 -ffp-contract=off``: the parity kernels must not fuse a*b+c (the
 reference is Python: every operation rounds), and nothing enables fast-math.  The library is built
 in-tree (``pytracer_amd/libptrace.so``) so it travels to the GPU box with the repository snapshot.
+
+``libptrace_rays.so`` (csrc/ptrace_rays.hip, include/ptrace_rays.h: ray batches) is a second translation unit and a second
+shared object ON PURPOSE: ``code_hash()`` of libptrace.so is what ties every ``profiles/pmc_*.json`` to the kernels it
+measured, and a kernel added to ptrace.hip would change it.  Same flags, its own ``-cuid``; built after libptrace.so.
 """
 from __future__ import annotations
 
@@ -15,14 +19,18 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(HERE, "libptrace.so")
 SOURCES = ["ptrace.hip"]
+RAYS_LIB = os.path.join(HERE, "libptrace_rays.so")
+RAYS_SOURCES = ["ptrace_rays.hip"]
 # every file the one translation unit includes: all of csrc/ (tests/test_host.py checks this list against the #include lines)
 DEPS = sorted(f for f in os.listdir(CSRC) if f.endswith((".hip", ".h"))) + [os.path.join("..", "..", "include", "ptrace.h"),
-                                                                            os.path.join("..", "..", "include", "ptrace_debug.h")]
+                                                                            os.path.join("..", "..", "include", "ptrace_debug.h"),
+                                                                            os.path.join("..", "..", "include", "ptrace_rays.h")]
 FLAGS = ["--offload-arch=gfx950", "-O3", "-ffp-contract=off", "-fno-fast-math", "-std=c++17", "-fPIC",
          "-shared", "-Wall", "-Wno-unused-function", "-Wno-pass-failed",
          # a fixed compilation-unit id: by default clang derives it from the command line (paths included), which would make
          # code_hash() depend on WHERE the library was built
          "-cuid=libptrace"]
+RAYS_FLAGS = FLAGS[:-1] + ["-cuid=libptrace_rays"]
 
 
 def code_hash(lib: str = LIB) -> str:
@@ -61,21 +69,22 @@ def _hipcc() -> str:
 
 
 def needs_build() -> bool:
-    if not os.path.exists(LIB):
+    if not os.path.exists(LIB) or not os.path.exists(RAYS_LIB):
         return True
-    t = os.path.getmtime(LIB)
+    t = min(os.path.getmtime(LIB), os.path.getmtime(RAYS_LIB))  # (one list of files for both: they share the headers)
     return any(os.path.getmtime(os.path.join(CSRC, d)) > t for d in DEPS)
 
 
 def build(force: bool = False, verbose: bool = False) -> str:
     if not force and not needs_build():
         return LIB
-    cmd = [_hipcc()] + FLAGS + ["-o", LIB] + [os.path.join(CSRC, s) for s in SOURCES]
-    if verbose:
-        print(" ".join(cmd), file=sys.stderr)
-    r = subprocess.run(cmd, capture_output=True, text=True)
-    if r.returncode != 0:
-        raise RuntimeError(f"hipcc failed ({r.returncode}):\n{r.stdout}\n{r.stderr}")
+    for flags, lib, sources in ((FLAGS, LIB, SOURCES), (RAYS_FLAGS, RAYS_LIB, RAYS_SOURCES)):
+        cmd = [_hipcc()] + flags + ["-o", lib] + [os.path.join(CSRC, s) for s in sources]
+        if verbose:
+            print(" ".join(cmd), file=sys.stderr)
+        r = subprocess.run(cmd, capture_output=True, text=True)
+        if r.returncode != 0:
+            raise RuntimeError(f"hipcc failed ({r.returncode}):\n{r.stdout}\n{r.stderr}")
     return LIB
 
 

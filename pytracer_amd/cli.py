@@ -233,5 +233,54 @@ def hits(width, height, channels, output, samples_per_pixel, declare_float, devi
     tracer.close()
 
 
+@click.command("rays")
+@click.option("--input", "input_name", type=str, required=True, help="A .npy file of [n, 8] rays: origin xyz, direction xyz, tmin, tmax")
+@click.option("--output", type=str, default="hits.npz", help="Name of the .npz file to create")
+@click.option("--any-hit", is_flag=True, default=False,
+              help="Only ask whether anything lies in (tmin, tmax): writes `blocked` (int32, 1 / 0) instead of hit records.")
+@click.option("--channels", type=str, default="all", help="Comma-separated planes to write besides shape_index: t, point, normal, uv, all")
+@click.option("--width", type=int, default=640, help="Width the scene's camera is built for (built-in scenes)")
+@click.option("--height", type=int, default=480, help="Height the scene's camera is built for")
+@click.option("--declare-float", "-d", type=str, multiple=True, help="Declare a variable: --declare-float=VAR:VALUE")
+@click.option("--device", type=int, default=0, help="GPU to trace on")
+@click.argument("input_scene_name", type=str, default="builtin:demo")
+def rays(input_name, output, any_hit, channels, width, height, declare_float, device, input_scene_name):
+    """World.ray_intersection (or, with --any-hit, the test World.is_point_visible makes) for a file of rays: an .npz of
+    shape_index (int32, -1 = no hit) and the selected planes [n(, components)]."""
+    import numpy as np
+
+    from . import flatten
+    from . import rays as rb
+
+    try:
+        try:
+            bits = 0 if any_hit else rb.ray_channels(channels)
+        except ValueError as e:
+            raise UsageError(f"--channels: {e}") from None
+        try:
+            batch = np.load(input_name)
+        except (OSError, ValueError) as e:
+            raise UsageError(f"--input {input_name}: {e}") from None
+        if batch.ndim != 2 or batch.shape[1] != 8:
+            raise UsageError(f"--input {input_name}: expected [n, 8] rays (origin, direction, tmin, tmax), got {batch.shape}")
+        world, _, _ = _load_scene(input_scene_name, parse_float_overrides(declare_float), width, height)
+    except UsageError as e:
+        click.echo(f"pytracer_amd rays: {e}", err=True)
+        sys.exit(2)
+    from . import _lib
+    from .device import DeviceScene
+
+    _lib.standalone()  # (torch-free, like `render`)
+    block = rb.ray_planes(batch)
+    with DeviceScene(flatten.flatten_world(world), device) as scene:
+        if any_hit:
+            planes = {"blocked": scene.occluded(block)}
+        else:
+            planes = scene.trace_rays(block, bits).planes()
+    np.savez(output, **planes)
+    click.echo(f"{block.shape[1]} ray(s), {len(world.shapes)} shape(s): wrote {output} ({', '.join(planes)})")
+
+
 cli.add_command(render)
 cli.add_command(hits)
+cli.add_command(rays)

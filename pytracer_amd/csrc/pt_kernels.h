@@ -115,6 +115,7 @@ struct Hit {
 #include "pt_math.h"
 #include "pt_query.h"
 #include "pt_shade.h"
+#ifndef PT_QUERY_PARTS_ONLY  // (ptrace_rays.hip defines it: the queries and the hit record, none of the frame kernels)
 #include "pt_camera.h"
 #include "pt_simple.h"
 #include "pt_tile.h"
@@ -122,3 +123,4 @@ struct Hit {
 #include "pt_path.h"
 #include "pt_tree.h"
 #include "pt_probes.h"
+#endif

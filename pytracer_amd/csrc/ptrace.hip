@@ -29,9 +29,10 @@
 // pt_stats gained `kernel` + `_reserved`, pt_scene_clone / pt_image_sparse_* arrived; minor 3: PT_PCG_SEQ accepted for
 // OnOff / Flat / PointLight at any samples_per_side; minor 4: pt_device_kernargs, and the library no longer sets
 // HIP_FORCE_DEV_KERNARG when it is loaded; minor 5: pt_device_alloc / pt_device_free / pt_device_download / pt_stream_*;
-// minor 6: hit-record frames -- pt_hits_bytes / pt_hits_plane_offset / pt_render_hits / pt_render_hits_device);
+// minor 6: hit-record frames -- pt_hits_bytes / pt_hits_plane_offset / pt_render_hits / pt_render_hits_device;
+// minor 7: pt_scene_kernel_args, the scene's argument block for add-on libraries built from this tree -- libptrace_rays.so);
 // a caller built against an older header checks pt_version() first.
-#define PT_VERSION ((1 << 16) | 6)
+#define PT_VERSION ((1 << 16) | 7)
 
 // (Kernel arguments in device memory -- HIP_FORCE_DEV_KERNARG=1, ~1 us per launch, profiles/r04_dev_kernarg.txt -- are the
 // CALLER's choice: the HIP runtime reads the variable when it initialises, and a library that edited the process environment
@@ -111,6 +112,7 @@ struct pt_scene {
   bool queue_clean = false;
   ColdArgs args;                        // the argument block (cold fields)
   ColdArgs args2;                       // ... pt_path_flagged_kernel's, when a frame enqueues both second-pass kernels (PT_Q_CHOICE)
+  ColdArgs scene_args;                  // pt_scene_kernel_args: the scene-only block (no camera, no frame), made on first call
   int last_handover_cap = 0;            // records the last num_of_rays > 1 frame's hand-over table held (pt_debug_handed_over)
   bool choice_pending = false;          // ray_counter_host[2] will hold the frame's PT_Q_CHOICE word once ev_count has passed
   unsigned char *region_keys = nullptr;  // path tracer region ordering
@@ -202,7 +204,7 @@ extern "C" void pt_scene_free(pt_scene *s) {
   if (s->launched && s->last_stream) (void)hipStreamSynchronize(s->last_stream);
   shared_release(s->sh);
   for (void *p : {(void *)s->hoist, (void *)s->hoist_diag, (void *)s->ws, (void *)s->handover, (void *)s->units_handed, (void *)s->out_dev,
-                  (void *)s->ray_counter, (void *)s->ray_partials, (void *)s->queue, (void *)s->args.dev, (void *)s->args2.dev,
+                  (void *)s->ray_counter, (void *)s->ray_partials, (void *)s->queue, (void *)s->args.dev, (void *)s->args2.dev, (void *)s->scene_args.dev,
                   (void *)s->region_keys, (void *)s->units, (void *)s->region_mask, (void *)s->cell_list, (void *)s->cell_count})
     (void)hipFree(p);
   if (s->ray_counter_host) (void)hipHostFree(s->ray_counter_host);
@@ -460,6 +462,30 @@ static void fill_scene_args(const pt_scene *s, PtKArgs &a) {
   a.n_shapes = sc.n_shapes;
   a.n_spheres = sc.n_spheres;
   a.n_lights = sc.n_lights;
+}
+
+// The scene's block for a library of kernels built from this tree but linked into another shared object (ptrace_rays.hip:
+// ray batches): fill_scene_args with `cold` pointing to a device-resident copy of the same block, which this handle owns.
+// Nothing a frame sets is in it (camera, output, workspace: zero), so it stays valid while frames run through the handle.
+extern "C" int pt_scene_kernel_args(pt_scene *s, void *out, size_t out_bytes) {
+  if (!s || !out) return fail(PT_ERR_INVALID, "null argument");
+  if (out_bytes != sizeof(PtKArgs))
+    return fail(PT_ERR_INVALID, "argument block of %zu bytes asked for, this library's has %zu: caller built from another tree?", out_bytes,
+                sizeof(PtKArgs));
+  HIP_TRY(hipSetDevice(s->device));
+  PtKArgs a;
+  memset(&a, 0, sizeof a);
+  fill_scene_args(s, a);
+  ColdArgs &c = s->scene_args;
+  if (!c.dev) HIP_TRY(hipMalloc((void **)&c.dev, sizeof(PtKArgs)));
+  a.cold = c.dev;
+  if (!c.valid || memcmp(&c.last, &a, sizeof a) != 0) {  // (first call; or a tuning switch changed bs_levels in between)
+    HIP_TRY(hipMemcpy(c.dev, &a, sizeof a, hipMemcpyHostToDevice));
+    c.last = a;
+    c.valid = true;
+  }
+  memcpy(out, &a, sizeof a);
+  return PT_OK;
 }
 
 static_assert(PT_PLAN_BLOCK == PT_BLOCK && PT_PLAN_REGION == PT_REGION && PT_PLAN_CELL == PT_CELL && PT_PLAN_CELL_CHUNK == PT_CELL_CHUNK &&

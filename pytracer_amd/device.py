@@ -93,6 +93,7 @@ class DeviceScene:
         if getattr(self, "_h", None) is not None and self._h.value:
             _lib.lib().pt_scene_free(self._h)
             self._h = C.c_void_p()
+            self._kargs = None  # (its device copy went with the handle)
 
     def __del__(self):
         try:
@@ -153,6 +154,73 @@ class DeviceScene:
             dev_ptr = dev_ptr.data_ptr()
         _lib.check(_lib.lib().pt_render_hits_device(self._h, C.byref(cam), C.byref(params), abi.hit_channels(channels),
                                                     C.c_void_p(dev_ptr), int(nbytes), C.c_void_p(handle) if handle else None))
+
+    # -- ray batches (include/ptrace_rays.h, libptrace_rays.so): the caller's own rays through the scene ---------------------
+    def kernel_args(self):
+        """The scene's argument block (``pt_scene_kernel_args``, ABI 1.7) as ``pt_rays_trace*`` take it: fetched once per handle."""
+        from . import _rays_lib
+
+        if getattr(self, "_kargs", None) is None:
+            self._kargs = _rays_lib.scene_args(self._h)
+        return self._kargs
+
+    def _trace(self, rays, channels: int, anyhit: bool, device, stream, out):
+        from . import _rays_lib, rays as rb
+
+        L = _rays_lib.lib()
+        block = self.kernel_args()
+        handle = getattr(stream, "handle", stream)
+        if device:
+            # (a DeviceBuffer, or anything else that names device memory the same way: a torch tensor has data_ptr() and nbytes)
+            if not callable(getattr(rays, "data_ptr", None)) or int(rays.nbytes) % 64:
+                raise TypeError("device=True takes the rays as a DeviceBuffer (or a device tensor) holding [8, n] float64")
+            n = int(rays.nbytes) // 64
+            need = rb.rays_bytes(n, channels, anyhit)
+            if out is None:
+                from .devmem import DeviceBuffer
+
+                out = DeviceBuffer((need,), np.uint8, self.device)
+            _rays_lib.check(L.pt_rays_trace_device(self.device, block, len(block), C.c_void_p(rays.data_ptr()), n, channels, int(anyhit),
+                                                   C.c_void_p(out.data_ptr()), int(out.nbytes), C.c_void_p(handle) if handle else None))
+            if hasattr(out, "rendered_on"):
+                out.rendered_on(stream)
+            return out, n
+        if stream is not None or out is not None:
+            raise ValueError("stream= and out= go with device=True (host batches are staged and synchronous)")
+        rays = np.ascontiguousarray(rays, dtype=np.float64)
+        if rays.ndim != 2 or rays.shape[0] != 8:
+            raise ValueError(f"rays must be the [8, n] block of pytracer_amd.rays.ray_planes, not {rays.shape}")
+        n = rays.shape[1]
+        buf = np.empty(rb.rays_bytes(n, channels, anyhit), dtype=np.uint8)
+        _rays_lib.check(L.pt_rays_trace(self.device, block, len(block), rays.ctypes.data_as(C.c_void_p), n, channels, int(anyhit),
+                                        buf.ctypes.data_as(C.c_void_p), buf.nbytes))
+        return buf, n
+
+    def trace_rays(self, rays, channels=None, device: bool = False, stream=None, out=None):
+        """``World.ray_intersection`` (world.py:51-69) for a batch: ``rays`` is the ``[8, n]`` block of
+        :func:`pytracer_amd.rays.ray_planes` -> :class:`pytracer_amd.rays.RayHits` with the selected ``channels`` (default: t,
+        point, normal, uv).  ``device=True``: ``rays`` is a :class:`pytracer_amd.devmem.DeviceBuffer` holding that block, the
+        batch is enqueued on ``stream`` (a ``Stream`` or ``hipStream_t``; ``None``: synchronous) and the result stays in HBM:
+        -> the output ``DeviceBuffer`` (``out``, or a new one), which remembers the stream -- ``RayHits(buf.numpy(), n, channels)``
+        views a download."""
+        from . import rays as rb
+
+        bits = rb.RAY_CHANNELS if channels is None else rb.ray_channels(channels)
+        buf, n = self._trace(rays, bits, False, device, stream, out)
+        return buf if device else rb.RayHits(buf, n, bits)
+
+    def occluded(self, rays, device: bool = False, stream=None, out=None):
+        """``[n]`` int32, 1 where some shape has a root in the ray's (tmin, tmax) -- ``Shape.quick_ray_intersection`` over the
+        world, what ``World.is_point_visible`` negates (world.py:76-78) -- else 0.  ``device=True``: as :meth:`trace_rays`, the
+        result a ``DeviceBuffer`` whose first ``4 n`` bytes are that plane."""
+        buf, n = self._trace(rays, 0, True, device, stream, out)
+        return buf if device else buf[: n * 4].view(np.int32)
+
+    def points_visible(self, points, observer) -> np.ndarray:
+        """``[n]`` bool: ``World.is_point_visible(points[i], observer)`` (world.py:71-80)."""
+        from . import rays as rb
+
+        return self.occluded(rb.visibility_rays(points, observer)) == 0
 
     def cull_probe(self, cam: abi.Camera, width: int, height: int, x0: int, x1: int, row0: int, row1: int,
                    pixel=None) -> np.ndarray:

@@ -1,0 +1,160 @@
+"""Ray batches: ``World.ray_intersection`` (world.py:51-69) and ``World.is_point_visible`` (world.py:71-80) for a caller's
+own rays, many at a time, on the device (include/ptrace_rays.h, libptrace_rays.so).
+
+A hit shader gets its first hits from ``GpuImageTracer.fire_all_hits``; its second question -- a shadow ray to a light, a
+mirror bounce, an ambient-occlusion probe -- goes through ``DeviceScene.trace_rays`` / ``occluded`` / ``points_visible``
+(or ``GpuImageTracer.world_queries(world)``, the same on the tracer's cached scene).
+
+Layout: planar.  A batch is ``[8, n]`` float64 -- origin xyz, direction xyz, tmin, tmax, the fields of ``Ray`` (ray.py:29-50);
+a result is one buffer, the int32 shape plane first (padded to 8 bytes), then the selected fp64 planes of ``n`` values each.
+"""
+from __future__ import annotations
+
+import numpy as np
+
+from . import abi
+
+RAY_CHANNELS = abi.HIT_T | abi.HIT_POINT | abi.HIT_NORMAL | abi.HIT_UV
+MAX_RAYS = 2 ** 31 - 1
+_PLANES = {abi.HIT_T: 1, abi.HIT_POINT: 3, abi.HIT_NORMAL: 3, abi.HIT_UV: 2}
+_CHANNEL_OF = {"t": abi.HIT_T, "point": abi.HIT_POINT, "normal": abi.HIT_NORMAL, "uv": abi.HIT_UV}
+
+
+def ray_channels(channels) -> int:
+    """``PT_HIT_*`` bits a ray batch can carry, from an int, names (``"normal,t"``) or ``"all"`` (= t, point, normal, uv: the
+    rays themselves are the caller's)."""
+    if isinstance(channels, str) and channels.strip().lower() == "all":
+        return RAY_CHANNELS
+    bits = abi.hit_channels(channels)
+    if bits & ~RAY_CHANNELS:
+        raise ValueError(f"a ray batch has the channels t, point, normal, uv; not {bits & ~RAY_CHANNELS:#x}")
+    return bits
+
+
+def _ok(n: int, channels: int, anyhit: bool) -> bool:
+    return 0 <= n <= MAX_RAYS and channels >= 0 and not channels & ~RAY_CHANNELS and not (anyhit and channels)
+
+
+def rays_bytes(n: int, channels: int, anyhit: bool = False) -> int:
+    """Mirror of ``pt_rays_bytes``: 0 for arguments the library refuses."""
+    if not _ok(n, channels, anyhit):
+        return 0
+    return ((n * 4 + 7) & ~7) + n * 8 * sum(k for bit, k in _PLANES.items() if channels & bit)
+
+
+def rays_plane_offset(n: int, channels: int, anyhit: bool, channel: int, component: int = 0) -> int:
+    """Mirror of ``pt_rays_plane_offset`` (bytes; ``channel`` 0: the int32 plane; < 0: not selected)."""
+    if not _ok(n, channels, anyhit):
+        return -1
+    if channel == 0:
+        return 0 if component == 0 else -1
+    if channel not in _PLANES or not channels & channel or not 0 <= component < _PLANES[channel]:
+        return -1
+    before = sum(k for bit, k in _PLANES.items() if bit < channel and channels & bit)
+    return ((n * 4 + 7) & ~7) + n * 8 * (before + component)
+
+
+def ray_planes(origins, dirs=None, tmin=1e-5, tmax=float("inf")) -> np.ndarray:
+    """The ``[8, n]`` input block from ``[n, 3]`` origins and directions (``tmin`` / ``tmax``: scalars or ``[n]``; the defaults
+    are ``Ray``'s, ray.py:44-45), or from one ``[n, 8]`` array of (origin, dir, tmin, tmax) rows."""
+    o = np.asarray(origins, dtype=np.float64)
+    if dirs is None:
+        if o.ndim != 2 or o.shape[1] != 8:
+            raise ValueError(f"rays must be [n, 8] (origin, dir, tmin, tmax), not {o.shape}")
+        return np.ascontiguousarray(o.T)
+    d = np.asarray(dirs, dtype=np.float64)
+    if o.ndim != 2 or o.shape[1] != 3 or d.shape != o.shape:
+        raise ValueError(f"origins and dirs must both be [n, 3], not {o.shape} and {d.shape}")
+    block = np.empty((8, o.shape[0]), dtype=np.float64)
+    block[0:3] = o.T
+    block[3:6] = d.T
+    block[6] = tmin
+    block[7] = tmax
+    return block
+
+
+def visibility_rays(points, observer) -> np.ndarray:
+    """The rays of ``World.is_point_visible(point, observer)`` (world.py:71-80) for ``[n, 3]`` points, as an ``[8, n]`` block:
+    from the observer, ``dir = point - observer``, ``tmin = 1e-2 / dir.norm()`` with the norm as geometry.py computes it
+    (``sqrt(x*x + y*y + z*z)``), ``tmax = 1.0`` -- each operation as the reference orders it, so the rays are the
+    reference's to the bit.  ``observer``: one point or ``[n, 3]``."""
+    p = np.asarray(points, dtype=np.float64).reshape(-1, 3)
+    ob = np.broadcast_to(np.asarray(observer, dtype=np.float64).reshape(-1, 3), p.shape)
+    dx, dy, dz = p[:, 0] - ob[:, 0], p[:, 1] - ob[:, 1], p[:, 2] - ob[:, 2]
+    block = np.empty((8, p.shape[0]), dtype=np.float64)
+    block[0:3] = ob.T
+    block[3], block[4], block[5] = dx, dy, dz
+    with np.errstate(divide="ignore", invalid="ignore"):
+        block[6] = 1e-2 / np.sqrt(dx * dx + dy * dy + dz * dz)
+    block[7] = 1.0
+    return block
+
+
+class RayHits:
+    """Views over the buffer of a closest-hit batch (``buf``: ``pt_rays_bytes`` bytes, contiguous ``uint8``).  Nothing here
+    copies: ``point``, ``normal`` and ``uv`` are strided views ``[n, components]``."""
+
+    def __init__(self, buf, n: int, channels=RAY_CHANNELS):
+        self.channels = ray_channels(channels)
+        self.n = int(n)
+        self.nbytes = rays_bytes(self.n, self.channels, False)
+        buf = np.asarray(buf)
+        if buf.dtype != np.uint8 or buf.ndim != 1:
+            buf = buf.reshape(-1).view(np.uint8)
+        if buf.nbytes < self.nbytes:
+            raise ValueError(f"ray-batch buffer too small: {buf.nbytes} < {self.nbytes} bytes")
+        self.buffer = buf
+        self.shape_index = buf[: self.n * 4].view(np.int32)
+
+    def _planes(self, channel: int, count: int) -> np.ndarray:
+        if not self.channels & channel:
+            name = next(k for k, v in _CHANNEL_OF.items() if v == channel)
+            raise KeyError(f"channel {name!r} was not selected for this batch (channels = {self.channels:#x})")
+        off = rays_plane_offset(self.n, self.channels, False, channel, 0)
+        return self.buffer[off: off + self.n * 8 * count].view(np.float64).reshape(count, self.n)
+
+    def has(self, name: str) -> bool:
+        return bool(self.channels & _CHANNEL_OF[name])
+
+    @property
+    def hit(self) -> np.ndarray:
+        return self.shape_index >= 0
+
+    @property
+    def t(self) -> np.ndarray:
+        return self._planes(abi.HIT_T, 1)[0]
+
+    @property
+    def point(self) -> np.ndarray:
+        return self._planes(abi.HIT_POINT, 3).T
+
+    @property
+    def normal(self) -> np.ndarray:
+        return self._planes(abi.HIT_NORMAL, 3).T
+
+    @property
+    def uv(self) -> np.ndarray:
+        return self._planes(abi.HIT_UV, 2).T
+
+    def planes(self) -> dict:
+        """name -> view, for every selected channel (what the ``rays`` command writes into its ``.npz``)."""
+        out = {"shape_index": self.shape_index}
+        for name in ("t", "point", "normal", "uv"):
+            if self.has(name):
+                out[name] = getattr(self, name)
+        return out
+
+
+class WorldQueries:
+    """``World.ray_intersection`` / ``World.is_point_visible`` in batches on a device scene (``GpuImageTracer.world_queries``)."""
+
+    def __init__(self, scene):
+        self.scene = scene
+
+    def ray_intersections(self, rays, dirs=None, channels=RAY_CHANNELS, tmin=1e-5, tmax=float("inf")) -> RayHits:
+        """``[n, 8]`` rays (or ``[n, 3]`` origins and ``dirs``) -> :class:`RayHits`, the ``HitRecord`` of every ray."""
+        return self.scene.trace_rays(ray_planes(rays, dirs, tmin, tmax), channels)
+
+    def are_points_visible(self, points, observer) -> np.ndarray:
+        """``[n]`` bool: ``world.is_point_visible(points[i], observer)``."""
+        return self.scene.points_visible(points, observer)

@@ -263,6 +263,15 @@ class GpuImageTracer:
         self.last_path = "device-hits"
         return frame
 
+    def world_queries(self, world):
+        """``world.ray_intersection`` / ``world.is_point_visible`` in batches, on the device scene this tracer caches for
+        ``world`` (the one ``fire_all_hits(world)`` rendered from): -> :class:`pytracer_amd.rays.WorldQueries` with
+        ``ray_intersections(rays)`` and ``are_points_visible(points, observer)``.  Where a hit shader asked its first question
+        it asks its second -- a shadow ray per light, a mirror bounce."""
+        from .rays import WorldQueries
+
+        return WorldQueries(self._device_scene(world))
+
     def _hit_shader_frame(self, func, callback, callback_kwargs) -> None:
         if callback:
             callback(col=0, row=0, **callback_kwargs)
