@@ -34,6 +34,10 @@
  * (tmin, tmax): Shape.quick_ray_intersection, shapes.py:133-151, 191-199), 0 = free.
  *
  * n = 0: PT_OK, nothing launched, nothing written.  n < 0 or n > 2^31 - 1: PT_ERR_INVALID.
+ *
+ * Interface 1.1 adds the question a renderer asks next -- the hit's material, and its shading under the scene's point
+ * lights -- as ptrace_surface.h (included below), served by libptrace_surface.so from the same argument block.  The seven
+ * entry points of this library are those of 1.0, unchanged.
  */
 #ifndef PTRACE_RAYS_H
 #define PTRACE_RAYS_H
@@ -46,7 +50,7 @@
 extern "C" {
 #endif
 
-/* (major << 16) | minor of THIS library's interface; this header describes 1.0. */
+/* (major << 16) | minor of THIS library's interface; this header describes 1.1. */
 int pt_rays_version(void);
 /* sizeof(PtKArgs) this library was built with: what pt_scene_kernel_args must be asked for. */
 size_t pt_rays_args_bytes(void);
@@ -68,4 +72,7 @@ int pt_rays_last_error(char *buf, size_t n);
 #ifdef __cplusplus
 }
 #endif
+
+#include "ptrace_surface.h" /* 1.1: materials and point-light shading of the records (libptrace_surface.so) */
+
 #endif /* PTRACE_RAYS_H */

@@ -20,7 +20,7 @@
 #define PT_QUERY_PARTS_ONLY
 #include "pt_kernels.h"
 
-#define PT_RAYS_VERSION ((1 << 16) | 0)
+#define PT_RAYS_VERSION ((1 << 16) | 1)  // 1.1: the block also feeds the surface queries (include/ptrace_surface.h)
 #define PT_RAYS_CHANNELS (PT_HIT_T | PT_HIT_POINT | PT_HIT_NORMAL | PT_HIT_UV)
 #define PT_RAYS_MAX_N 2147483647LL  // the grid is n / 256 blocks in x
 

@@ -94,6 +94,9 @@ class DeviceScene:
             _lib.lib().pt_scene_free(self._h)
             self._h = C.c_void_p()
             self._kargs = None  # (its device copy went with the handle)
+            slots, self._slots = getattr(self, "_slots", None), None
+            if slots is not None:
+                slots.free()
 
     def __del__(self):
         try:
@@ -221,6 +224,116 @@ class DeviceScene:
         from . import rays as rb
 
         return self.occluded(rb.visibility_rays(points, observer)) == 0
+
+    # -- surface queries (include/ptrace_surface.h, libptrace_surface.so): the records' materials, and their light --------
+    def slot_table(self):
+        """The scene's ``World.shapes`` index -> record table in HBM (``pt_rays_slots_device``), made once per handle like
+        :meth:`kernel_args` and freed with it -> :class:`pytracer_amd.devmem.DeviceBuffer`."""
+        from . import _surface_lib
+        from .devmem import DeviceBuffer
+
+        if getattr(self, "_slots", None) is None:
+            L, block = _surface_lib.lib(), self.kernel_args()
+            need = int(L.pt_rays_slots_bytes(block, len(block)))
+            table = DeviceBuffer((max(need, 8),), np.uint8, self.device)
+            _surface_lib.check(L.pt_rays_slots_device(self.device, block, len(block), C.c_void_p(table.data_ptr()), table.nbytes, None))
+            self._slots = table
+        return self._slots
+
+    @staticmethod
+    def _plane_ptr(x, what: str):
+        """A device address from a ``DeviceBuffer`` / device tensor (``data_ptr()``) or a raw address (a plane inside one)."""
+        if x is None:
+            return None
+        if callable(getattr(x, "data_ptr", None)):
+            return C.c_void_p(int(x.data_ptr()))
+        if isinstance(x, (int, np.integer)):
+            return C.c_void_p(int(x))
+        raise TypeError(f"device=True takes {what} as a DeviceBuffer, a device tensor or a raw device address, not {type(x).__name__}")
+
+    @staticmethod
+    def _device_count(first, n) -> int:
+        if n is not None:
+            return int(n)
+        if not hasattr(first, "nbytes"):
+            raise ValueError("n= is needed when the planes are raw device addresses")
+        return int(first.nbytes) // 4
+
+    def surface(self, shape_index, uv=None, channels="all", device: bool = False, stream=None, out=None, n=None):
+        """The material of every hit record: ``brdf.pigment.get_color(uv)`` and ``emitted_radiance.get_color(uv)``
+        (materials.py:50-100; ``channels``: ``"brdf_color"``, ``"emitted"``, ``"all"``, ``"none"`` or ``PT_SURF_*`` bits) and the
+        BRDF's kind.  ``shape_index``: ``World.shapes`` indices (negative: no hit), any shape; ``uv``: ``[..., 2]`` (not needed
+        without a colour) -> :class:`pytracer_amd.rays.SurfaceColors`.  ``device=True``: ``shape_index`` (``n`` int32) and
+        ``uv`` (two planes of ``n`` doubles) are in HBM -- ``DeviceBuffer`` s, device tensors, or raw addresses of planes inside
+        a ray-batch or hit-frame buffer, then with ``n=`` -- the batch is enqueued on ``stream`` and the result stays there:
+        -> the output ``DeviceBuffer`` (``out``, or a new one), as :meth:`trace_rays`."""
+        from . import _surface_lib, rays as rb
+
+        L, block, bits = _surface_lib.lib(), self.kernel_args(), rb.surface_channels(channels)
+        if device:
+            handle = getattr(stream, "handle", stream)
+            n = self._device_count(shape_index, n)
+            if out is None:
+                from .devmem import DeviceBuffer
+
+                out = DeviceBuffer((max(rb.surface_bytes(n, bits), 8),), np.uint8, self.device)
+            _surface_lib.check(L.pt_rays_surface_device(self.device, block, len(block), C.c_void_p(self.slot_table().data_ptr()),
+                                                        self._plane_ptr(shape_index, "shape_index"), self._plane_ptr(uv, "uv"), n, bits,
+                                                        self._plane_ptr(out, "out"), int(out.nbytes), C.c_void_p(handle) if handle else None))
+            if hasattr(out, "rendered_on"):
+                out.rendered_on(stream)
+            return out
+        if stream is not None or out is not None or n is not None:
+            raise ValueError("stream=, out= and n= go with device=True (host batches are staged and synchronous)")
+        shape = np.ascontiguousarray(shape_index, dtype=np.int32).reshape(-1)
+        n = shape.shape[0]
+        uvp = rb.planar(uv, 2) if bits else None
+        if uvp is not None and uvp.shape[1] != n:
+            raise ValueError(f"{n} shape indices but {uvp.shape[1]} (u, v) pairs")
+        buf = np.empty(rb.surface_bytes(n, bits), dtype=np.uint8)
+        _surface_lib.check(L.pt_rays_surface(self.device, block, len(block), shape.ctypes.data_as(C.c_void_p),
+                                             uvp.ctypes.data_as(C.c_void_p) if uvp is not None else None, n, bits,
+                                             buf.ctypes.data_as(C.c_void_p), buf.nbytes))
+        return rb.SurfaceColors(buf, n, bits)
+
+    def shade_lights(self, shape_index, point, normal, uv, dirs, ambient=(0.1, 0.1, 0.1), background=(0.0, 0.0, 0.0),
+                     device: bool = False, stream=None, out=None, n=None):
+        """``PointLightRenderer.__call__`` (render.py:157-193) for every hit record: ``background`` where nothing was hit, else
+        ``ambient`` + emitted + one term per point light of the scene that ``World.is_point_visible`` sees from the hit point.
+        ``point``, ``normal``, ``dirs``: ``[..., 3]``, ``uv``: ``[..., 2]``, ``dirs`` the directions of the rays that were traced
+        -> ``[n, 3]`` float64 (a view of the three planes the library wrote).  ``device=True``: planes in HBM as for
+        :meth:`surface`; -> the output ``DeviceBuffer`` of ``[3, n]`` float64."""
+        from . import _surface_lib, rays as rb
+
+        L, block = _surface_lib.lib(), self.kernel_args()
+        amb, bg = _surface_lib.rgb(ambient), _surface_lib.rgb(background)
+        if device:
+            handle = getattr(stream, "handle", stream)
+            n = self._device_count(shape_index, n)
+            if out is None:
+                from .devmem import DeviceBuffer
+
+                out = DeviceBuffer((3, max(n, 1)), np.float64, self.device)
+            ptr = self._plane_ptr
+            _surface_lib.check(L.pt_rays_shade_lights_device(self.device, block, len(block), C.c_void_p(self.slot_table().data_ptr()),
+                                                             ptr(shape_index, "shape_index"), ptr(point, "point"), ptr(normal, "normal"),
+                                                             ptr(uv, "uv"), ptr(dirs, "dirs"), n, amb, bg, ptr(out, "out"), int(out.nbytes),
+                                                             C.c_void_p(handle) if handle else None))
+            if hasattr(out, "rendered_on"):
+                out.rendered_on(stream)
+            return out
+        if stream is not None or out is not None or n is not None:
+            raise ValueError("stream=, out= and n= go with device=True (host batches are staged and synchronous)")
+        shape = np.ascontiguousarray(shape_index, dtype=np.int32).reshape(-1)
+        n = shape.shape[0]
+        planes = [rb.planar(point, 3), rb.planar(normal, 3), rb.planar(uv, 2), rb.planar(dirs, 3)]
+        if any(p.shape[1] != n for p in planes):
+            raise ValueError(f"{n} shape indices but {[p.shape[1] for p in planes]} points, normals, (u, v) pairs and directions")
+        buf = np.empty((3, n), dtype=np.float64)
+        _surface_lib.check(L.pt_rays_shade_lights(self.device, block, len(block), shape.ctypes.data_as(C.c_void_p),
+                                                  *[p.ctypes.data_as(C.c_void_p) for p in planes], n, amb, bg,
+                                                  buf.ctypes.data_as(C.c_void_p), buf.nbytes))
+        return buf.T
 
     def cull_probe(self, cam: abi.Camera, width: int, height: int, x0: int, x1: int, row0: int, row1: int,
                    pixel=None) -> np.ndarray:

@@ -5,6 +5,10 @@ A hit shader gets its first hits from ``GpuImageTracer.fire_all_hits``; its seco
 mirror bounce, an ambient-occlusion probe -- goes through ``DeviceScene.trace_rays`` / ``occluded`` / ``points_visible``
 (or ``GpuImageTracer.world_queries(world)``, the same on the tracer's cached scene).
 
+Its third -- the hit's material, and its colour under the scene's point lights -- goes through ``DeviceScene.surface`` /
+``shade_lights`` (include/ptrace_surface.h, libptrace_surface.so), or ``WorldQueries.materials`` / ``point_light_radiance``,
+which take a :class:`RayHits` or a hit-record frame as it is: :class:`SurfaceColors` views the answer.
+
 Layout: planar.  A batch is ``[8, n]`` float64 -- origin xyz, direction xyz, tmin, tmax, the fields of ``Ray`` (ray.py:29-50);
 a result is one buffer, the int32 shape plane first (padded to 8 bytes), then the selected fp64 planes of ``n`` values each.
 """
@@ -18,6 +22,10 @@ RAY_CHANNELS = abi.HIT_T | abi.HIT_POINT | abi.HIT_NORMAL | abi.HIT_UV
 MAX_RAYS = 2 ** 31 - 1
 _PLANES = {abi.HIT_T: 1, abi.HIT_POINT: 3, abi.HIT_NORMAL: 3, abi.HIT_UV: 2}
 _CHANNEL_OF = {"t": abi.HIT_T, "point": abi.HIT_POINT, "normal": abi.HIT_NORMAL, "uv": abi.HIT_UV}
+
+
+SURF_BRDF_COLOR, SURF_EMITTED, SURF_ALL = 1, 2, 3  # PT_SURF_* of include/ptrace_surface.h
+_SURF_OF = {"brdf_color": SURF_BRDF_COLOR, "emitted": SURF_EMITTED}
 
 
 def ray_channels(channels) -> int:
@@ -145,8 +153,109 @@ class RayHits:
         return out
 
 
+def surface_channels(channels) -> int:
+    """``PT_SURF_*`` bits from an int, names (``"emitted"``, ``"brdf_color,emitted"``), ``"all"`` or ``"none"``."""
+    if isinstance(channels, str):
+        names = [x.strip().lower() for x in channels.split(",") if x.strip()]
+        if names == ["all"]:
+            return SURF_ALL
+        if names == ["none"]:
+            return 0
+        unknown = [x for x in names if x not in _SURF_OF]
+        if unknown:
+            raise ValueError(f"a surface batch has the channels brdf_color, emitted; not {', '.join(unknown)}")
+        return sum({_SURF_OF[x] for x in names})
+    bits = int(channels)
+    if bits < 0 or bits & ~SURF_ALL:
+        raise ValueError(f"a surface batch has the channels brdf_color (1), emitted (2); not {bits:#x}")
+    return bits
+
+
+def surface_bytes(n: int, channels: int) -> int:
+    """Mirror of ``pt_rays_surface_bytes``: 0 for arguments the library refuses."""
+    if not (0 <= n <= MAX_RAYS and 0 <= channels <= SURF_ALL):
+        return 0
+    return ((n * 4 + 7) & ~7) + n * 24 * bin(channels).count("1")
+
+
+def surface_plane_offset(n: int, channels: int, channel: int, component: int = 0) -> int:
+    """Mirror of ``pt_rays_surface_plane_offset`` (bytes; ``channel`` 0: the int32 plane of BRDF kinds; < 0: not selected)."""
+    if not (0 <= n <= MAX_RAYS and 0 <= channels <= SURF_ALL):
+        return -1
+    if channel == 0:
+        return 0 if component == 0 else -1
+    if channel not in (SURF_BRDF_COLOR, SURF_EMITTED) or not channels & channel or not 0 <= component < 3:
+        return -1
+    before = 3 if channel == SURF_EMITTED and channels & SURF_BRDF_COLOR else 0
+    return ((n * 4 + 7) & ~7) + n * 8 * (before + component)
+
+
+class SurfaceColors:
+    """Views over the buffer of a surface batch (``buf``: ``pt_rays_surface_bytes`` bytes, contiguous ``uint8``): the BRDF kind
+    of every record's material (``abi.BRDF_*``; -1 where nothing was hit) and the selected colours.  Nothing here copies:
+    ``brdf_color`` and ``emitted`` are strided views with the component as last axis.  ``shape``: what the records' axis is
+    viewed as (a frame's ``[nsamp, rows, W]``); default ``[n]``."""
+
+    def __init__(self, buf, n: int, channels=SURF_ALL, shape=None):
+        self.channels = surface_channels(channels)
+        self.n = int(n)
+        self.shape = (self.n,) if shape is None else tuple(int(x) for x in shape)
+        if int(np.prod(self.shape, dtype=np.int64)) != self.n:
+            raise ValueError(f"shape {self.shape} does not hold {self.n} records")
+        self.nbytes = surface_bytes(self.n, self.channels)
+        buf = np.asarray(buf)
+        if buf.dtype != np.uint8 or buf.ndim != 1:
+            buf = buf.reshape(-1).view(np.uint8)
+        if buf.nbytes < self.nbytes:
+            raise ValueError(f"surface buffer too small: {buf.nbytes} < {self.nbytes} bytes")
+        self.buffer = buf
+        self.brdf_kind = buf[: self.n * 4].view(np.int32).reshape(self.shape)
+
+    def _colour(self, channel: int) -> np.ndarray:
+        if not self.channels & channel:
+            name = next(k for k, v in _SURF_OF.items() if v == channel)
+            raise KeyError(f"channel {name!r} was not selected for this surface batch (channels = {self.channels:#x})")
+        off = surface_plane_offset(self.n, self.channels, channel, 0)
+        planes = self.buffer[off: off + self.n * 24].view(np.float64).reshape((3,) + self.shape)
+        return np.moveaxis(planes, 0, -1)
+
+    def has(self, name: str) -> bool:
+        return bool(self.channels & _SURF_OF[name])
+
+    @property
+    def hit(self) -> np.ndarray:
+        return self.brdf_kind >= 0
+
+    @property
+    def brdf_color(self) -> np.ndarray:
+        """``material.brdf.pigment.get_color(uv)`` per record; zeros where nothing was hit."""
+        return self._colour(SURF_BRDF_COLOR)
+
+    @property
+    def emitted(self) -> np.ndarray:
+        """``material.emitted_radiance.get_color(uv)`` per record; zeros where nothing was hit."""
+        return self._colour(SURF_EMITTED)
+
+    def planes(self) -> dict:
+        out = {"brdf_kind": self.brdf_kind}
+        for name in ("brdf_color", "emitted"):
+            if self.has(name):
+                out[name] = getattr(self, name)
+        return out
+
+
+def planar(values, components: int) -> np.ndarray:
+    """``[..., components]`` -> the ``[components, n]`` planes the library reads.  The strided views of a :class:`RayHits` or
+    a hit-record frame ARE such planes seen from the other side: for them this is a view, not a copy."""
+    a = np.asarray(values, dtype=np.float64)
+    if a.ndim < 1 or a.shape[-1] != components:
+        raise ValueError(f"expected [..., {components}], not {a.shape}")
+    return np.ascontiguousarray(np.moveaxis(a, -1, 0)).reshape(components, -1)
+
+
 class WorldQueries:
-    """``World.ray_intersection`` / ``World.is_point_visible`` in batches on a device scene (``GpuImageTracer.world_queries``)."""
+    """``World.ray_intersection`` / ``World.is_point_visible`` in batches on a device scene (``GpuImageTracer.world_queries``),
+    and what a renderer does with the records: their materials, their colour under the world's point lights."""
 
     def __init__(self, scene):
         self.scene = scene
@@ -158,3 +267,22 @@ class WorldQueries:
     def are_points_visible(self, points, observer) -> np.ndarray:
         """``[n]`` bool: ``world.is_point_visible(points[i], observer)``."""
         return self.scene.points_visible(points, observer)
+
+    def materials(self, hits, channels=SURF_ALL) -> SurfaceColors:
+        """The material of every record of ``hits`` (a :class:`RayHits` or a :class:`pytracer_amd.hits.HitFrame` with the
+        ``uv`` channel): ``brdf.pigment.get_color(uv)``, ``emitted_radiance.get_color(uv)`` and the BRDF's kind ->
+        :class:`SurfaceColors`, shaped like ``hits.shape_index``."""
+        bits = surface_channels(channels)
+        out = self.scene.surface(hits.shape_index, hits.uv if bits else None, bits)
+        return SurfaceColors(out.buffer, out.n, bits, shape=hits.shape_index.shape)
+
+    def point_light_radiance(self, hits, dirs=None, ambient=(0.1, 0.1, 0.1), background=(0.0, 0.0, 0.0)) -> np.ndarray:
+        """``PointLightRenderer(world, background, ambient)(ray)`` (render.py:157-193) for every record of ``hits`` -- a
+        :class:`RayHits` or a hit-record frame with ``point``, ``normal`` and ``uv`` -- where ``dirs`` are the directions of
+        the rays that were traced (default: a frame's ``ray_dir``) -> ``hits.shape_index.shape + (3,)``."""
+        if dirs is None:
+            if not hasattr(hits, "ray_dir"):
+                raise ValueError("dirs= is needed: a ray batch does not carry the rays it was traced from")
+            dirs = hits.ray_dir
+        out = self.scene.shade_lights(hits.shape_index, hits.point, hits.normal, hits.uv, dirs, ambient, background)
+        return out.reshape(hits.shape_index.shape + (3,))

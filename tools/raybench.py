@@ -8,7 +8,14 @@ hit-record frame itself leaves them), the mirror bounces off their hits (d - 2 (
 from the hit points to a light at (0, 0, 10) (any-hit).  Per batch: warm-up launches, then a timed loop of
 ``pt_rays_trace_device`` on a stream of its own between two events.  One process; prints Mray/s per batch and the
 ``pt_render_hits`` kernel time of the same frame beside the primary batch (that frame culls per tile; a batch cannot).
-Needs torch only to put the batches into device memory and to read the events."""
+Needs torch only to put the batches into device memory and to read the events.
+
+    python tools/raybench.py --shade [...]
+
+The surface queries (libptrace_surface.so) on the same frame of C2 with two point lights, (-2, 3, 6) and (1, -4, 5) radius 2:
+``surface`` (both colours) and ``shade_lights`` on the frame's hit records, read in place out of the hit-record buffer in HBM,
+timed the same way; then the two-step point-light frame -- the ``pt_render_hits`` kernel plus ``shade_lights`` -- beside the
+fused RENDERER_POINTLIGHT frame kernel (``stats().kernel_ms``), which culls per tile and keeps the record in registers."""
 import argparse
 import ctypes as C
 import os
@@ -25,7 +32,10 @@ def main():
     ap.add_argument("--height", type=int, default=720)
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--steps", type=int, default=10)
+    ap.add_argument("--shade", action="store_true", help="time the surface queries instead of the ray batches")
     args = ap.parse_args()
+    if args.shade:
+        return shade(args)
     import torch
 
     from pytracer_amd import _rays_lib, abi, flatten, rays as rb, scenes
@@ -79,5 +89,64 @@ def main():
                   + (f"  = {ms / frame_ms:.2f} x the frame's kernel time" if label.startswith("primary") else ""))
 
 
+def shade(args):
+    import torch
+
+    from pytracer_amd import abi, flatten, hostmodel as hm, rays as rb, scenes
+    from pytracer_amd.device import DeviceScene
+    from pytracer_amd.devmem import DeviceBuffer
+
+    W, H = args.width, args.height
+    n = W * H
+    world = scenes.synthetic_world(32, with_plane=True)
+    world.add_light(hm.PointLight(hm.Vec(-2.0, 3.0, 6.0), hm.Color(1.0, 0.9, 0.8), 0.0))
+    world.add_light(hm.PointLight(hm.Vec(1.0, -4.0, 5.0), hm.Color(0.2, 0.3, 0.9), 2.0))
+    flat = flatten.flatten_world(world)
+    cam = flatten.flatten_camera(scenes.synthetic_camera(W, H))
+    p_hits = abi.make_params(W, H, abi.RENDERER_FLAT, samples_per_side=0)
+    p_fused = abi.make_params(W, H, abi.RENDERER_POINTLIGHT, samples_per_side=0)
+    with DeviceScene(flat) as ds:
+        def kernel_ms(call):
+            ms = []
+            for _ in range(args.warmup + args.steps):
+                call()
+                ms.append(ds.stats().kernel_ms)
+            return float(np.median(ms[args.warmup:]))
+
+        fused_ms = kernel_ms(lambda: ds.render(cam, p_fused))
+        fused = ds.render(cam, p_fused)
+        hits_ms = kernel_ms(lambda: ds.render_hits(cam, p_hits, abi.HIT_ALL))
+        frame = ds.render_hits(cam, p_hits, abi.HIT_ALL)
+        buf = torch.from_numpy(frame.buffer).cuda()
+        base = buf.data_ptr()
+        at = lambda ch, comp=0: base + abi.hits_plane_offset(p_hits, abi.HIT_ALL, ch, comp)  # noqa: E731
+        colours = DeviceBuffer((3, n), np.float64)
+        mats = DeviceBuffer((rb.surface_bytes(n, rb.SURF_ALL),), np.uint8)
+        ds.slot_table()
+        stream = torch.cuda.Stream()
+        torch.cuda.synchronize()
+        calls = [("surface (brdf colour, emitted)", lambda: ds.surface(base, at(abi.HIT_UV), "all", device=True, stream=stream.cuda_stream, out=mats, n=n)),
+                 ("shade_lights (2 lights)", lambda: ds.shade_lights(base, at(abi.HIT_POINT), at(abi.HIT_NORMAL), at(abi.HIT_UV), at(abi.HIT_RAY, 3),
+                                                                     device=True, stream=stream.cuda_stream, out=colours, n=n))]
+        print(f"C2 + 2 lights {W}x{H}: fused RENDERER_POINTLIGHT kernel {fused_ms:.3f} ms; pt_render_hits (all channels) kernel {hits_ms:.3f} ms")
+        took = {}
+        for label, go in calls:
+            for _ in range(args.warmup):
+                go()
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record(stream)
+            for _ in range(args.steps):
+                go()
+            e1.record(stream)
+            e1.synchronize()
+            took[label] = ms = e0.elapsed_time(e1) / args.steps
+            print(f"{label:32s} {n:8d} records  {ms:8.3f} ms  {n / ms / 1e3:8.1f} Mrecord/s")
+        two_step = hits_ms + took["shade_lights (2 lights)"]
+        same = colours.numpy().reshape(3, H, W).transpose(1, 2, 0).tobytes() == fused.tobytes()
+        print(f"pt_render_hits + shade_lights {two_step:.3f} ms = {two_step / fused_ms:.2f} x the fused kernel; the two frames are "
+              f"{'byte-identical' if same else 'DIFFERENT'}")
+        return 0 if same else 1
+
+
 if __name__ == "__main__":
-    main()
+    sys.exit(main())
