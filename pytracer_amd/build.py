@@ -1,4 +1,4 @@
-"""Build recipe for libptrace.so and its add-ons libptrace_rays.so and libptrace_surface.so (HIP, gfx950 only).
+"""Build recipe for libptrace.so and its add-ons libptrace_rays.so, libptrace_surface.so and libptrace_scatter.so (HIP, gfx950 only).
 
 ``hipcc --offload-arch=gfx950 -O3 -ffp-contract=off``: the parity kernels must not fuse a*b+c (the
 reference is Python: every operation rounds), and nothing enables fast-math.  The library is built
@@ -10,6 +10,9 @@ measured, and a kernel added to ptrace.hip would change it.  Same flags, its own
 
 ``libptrace_surface.so`` (csrc/ptrace_surface.hip, include/ptrace_surface.h: materials and point-light shading of hit
 records) is the third, for the same reason once more: the exported symbols of libptrace_rays.so are its interface 1.0's.
+
+``libptrace_scatter.so`` (csrc/ptrace_scatter.hip, include/ptrace_scatter.h: BRDF.scatter_ray and the Russian roulette for hit
+records) is the fourth: the exported symbols of libptrace_surface.so are pinned to its eleven as well.
 """
 from __future__ import annotations
 
@@ -26,11 +29,14 @@ RAYS_LIB = os.path.join(HERE, "libptrace_rays.so")
 RAYS_SOURCES = ["ptrace_rays.hip"]
 SURFACE_LIB = os.path.join(HERE, "libptrace_surface.so")
 SURFACE_SOURCES = ["ptrace_surface.hip"]
+SCATTER_LIB = os.path.join(HERE, "libptrace_scatter.so")
+SCATTER_SOURCES = ["ptrace_scatter.hip"]
 # every file the one translation unit includes: all of csrc/ (tests/test_host.py checks this list against the #include lines)
 DEPS = sorted(f for f in os.listdir(CSRC) if f.endswith((".hip", ".h"))) + [os.path.join("..", "..", "include", "ptrace.h"),
                                                                             os.path.join("..", "..", "include", "ptrace_debug.h"),
                                                                             os.path.join("..", "..", "include", "ptrace_rays.h"),
-                                                                            os.path.join("..", "..", "include", "ptrace_surface.h")]
+                                                                            os.path.join("..", "..", "include", "ptrace_surface.h"),
+                                                                            os.path.join("..", "..", "include", "ptrace_scatter.h")]
 FLAGS = ["--offload-arch=gfx950", "-O3", "-ffp-contract=off", "-fno-fast-math", "-std=c++17", "-fPIC",
          "-shared", "-Wall", "-Wno-unused-function", "-Wno-pass-failed",
          # a fixed compilation-unit id: by default clang derives it from the command line (paths included), which would make
@@ -38,6 +44,7 @@ FLAGS = ["--offload-arch=gfx950", "-O3", "-ffp-contract=off", "-fno-fast-math", 
          "-cuid=libptrace"]
 RAYS_FLAGS = FLAGS[:-1] + ["-cuid=libptrace_rays"]
 SURFACE_FLAGS = FLAGS[:-1] + ["-cuid=libptrace_surface"]
+SCATTER_FLAGS = FLAGS[:-1] + ["-cuid=libptrace_scatter"]
 
 
 def code_hash(lib: str = LIB) -> str:
@@ -76,17 +83,18 @@ def _hipcc() -> str:
 
 
 def needs_build() -> bool:
-    libs = (LIB, RAYS_LIB, SURFACE_LIB)
+    libs = (LIB, RAYS_LIB, SURFACE_LIB, SCATTER_LIB)
     if not all(os.path.exists(lib) for lib in libs):
         return True
-    t = min(os.path.getmtime(lib) for lib in libs)  # (one list of files for all three: they share the headers)
+    t = min(os.path.getmtime(lib) for lib in libs)  # (one list of files for all four: they share the headers)
     return any(os.path.getmtime(os.path.join(CSRC, d)) > t for d in DEPS)
 
 
 def build(force: bool = False, verbose: bool = False) -> str:
     if not force and not needs_build():
         return LIB
-    for flags, lib, sources in ((FLAGS, LIB, SOURCES), (RAYS_FLAGS, RAYS_LIB, RAYS_SOURCES), (SURFACE_FLAGS, SURFACE_LIB, SURFACE_SOURCES)):
+    for flags, lib, sources in ((FLAGS, LIB, SOURCES), (RAYS_FLAGS, RAYS_LIB, RAYS_SOURCES), (SURFACE_FLAGS, SURFACE_LIB, SURFACE_SOURCES),
+                                (SCATTER_FLAGS, SCATTER_LIB, SCATTER_SOURCES)):
         cmd = [_hipcc()] + flags + ["-o", lib] + [os.path.join(CSRC, s) for s in sources]
         if verbose:
             print(" ".join(cmd), file=sys.stderr)

@@ -335,6 +335,59 @@ class DeviceScene:
                                                   buf.ctypes.data_as(C.c_void_p), buf.nbytes))
         return buf.T
 
+    # -- the bounce (include/ptrace_scatter.h, libptrace_scatter.so): roulette and BRDF.scatter_ray, a generator per record ---
+    def scatter(self, shape_index, point, normal, uv, dirs, pcg, roulette: bool = False, channels="all", device: bool = False,
+                stream=None, out=None, n=None):
+        """The bounce of ``PathTracer.__call__`` (render.py:107-134, one child) for every hit record: the Russian roulette
+        (``roulette``: whether ``ray.depth >= russian_roulette_limit`` holds for this batch) and ``brdf.scatter_ray``
+        (materials.py:132-196), drawing from the record's own generator.  ``point``, ``normal``, ``dirs``: ``[..., 3]``,
+        ``uv``: ``[..., 2]``, ``dirs`` the directions of the rays that were traced; ``pcg``: ``uint64[2, n]`` -- state and
+        increment per record (:func:`pytracer_amd.rays.pcg_streams`, or ``ScatteredRays.pcg`` of the bounce before);
+        ``channels``: ``"weight"``, ``"emitted"``, ``"all"``, ``"none"`` or ``PT_SCAT_*`` bits
+        -> :class:`pytracer_amd.rays.ScatteredRays`, whose ``rays`` block :meth:`trace_rays` takes as it stands.
+        ``device=True``: the planes are in HBM as for :meth:`shade_lights` (``pcg``: a buffer of ``[2, n]`` uint64, or a pair
+        of plane addresses); the batch is enqueued on ``stream`` -> the output ``DeviceBuffer`` (``out``, or a new one)."""
+        from . import _scatter_lib, rays as rb
+
+        L, block, bits = _scatter_lib.lib(), self.kernel_args(), rb.scatter_channels(channels)
+        if device:
+            handle = getattr(stream, "handle", stream)
+            n = self._device_count(shape_index, n)
+            if isinstance(pcg, (tuple, list)):
+                state, inc = pcg
+            else:
+                base = int(self._plane_ptr(pcg, "pcg").value or 0)
+                state, inc = base, base + 8 * n
+            if out is None:
+                from .devmem import DeviceBuffer
+
+                out = DeviceBuffer((max(rb.scatter_bytes(n, bits), 8),), np.uint8, self.device)
+            ptr = self._plane_ptr
+            _scatter_lib.check(L.pt_rays_scatter_device(self.device, block, len(block), C.c_void_p(self.slot_table().data_ptr()),
+                                                        ptr(shape_index, "shape_index"), ptr(point, "point"), ptr(normal, "normal"),
+                                                        ptr(uv, "uv"), ptr(dirs, "dirs"), ptr(state, "pcg state"), ptr(inc, "pcg inc"), n,
+                                                        int(bool(roulette)), bits, ptr(out, "out"), int(out.nbytes),
+                                                        C.c_void_p(handle) if handle else None))
+            if hasattr(out, "rendered_on"):
+                out.rendered_on(stream)
+            return out
+        if stream is not None or out is not None or n is not None:
+            raise ValueError("stream=, out= and n= go with device=True (host batches are staged and synchronous)")
+        shape = np.ascontiguousarray(shape_index, dtype=np.int32).reshape(-1)
+        n = shape.shape[0]
+        planes = [rb.planar(point, 3), rb.planar(normal, 3), rb.planar(uv, 2), rb.planar(dirs, 3)]
+        if any(p.shape[1] != n for p in planes):
+            raise ValueError(f"{n} shape indices but {[p.shape[1] for p in planes]} points, normals, (u, v) pairs and directions")
+        gen = np.ascontiguousarray(pcg, dtype=np.uint64)
+        if gen.shape != (2, n):
+            raise ValueError(f"pcg must be uint64[2, {n}] (state and increment per record: pytracer_amd.rays.pcg_streams), not {gen.shape}")
+        buf = np.empty(rb.scatter_bytes(n, bits), dtype=np.uint8)
+        _scatter_lib.check(L.pt_rays_scatter(self.device, block, len(block), shape.ctypes.data_as(C.c_void_p),
+                                             *[p.ctypes.data_as(C.c_void_p) for p in planes], gen[0].ctypes.data_as(C.c_void_p),
+                                             gen[1].ctypes.data_as(C.c_void_p), n, int(bool(roulette)), bits,
+                                             buf.ctypes.data_as(C.c_void_p), buf.nbytes))
+        return rb.ScatteredRays(buf, n, bits)
+
     def cull_probe(self, cam: abi.Camera, width: int, height: int, x0: int, x1: int, row0: int, row1: int,
                    pixel=None) -> np.ndarray:
         """Diagnostics: which shapes (by ``World.shapes`` index) the conservative cull of the primary rays through

@@ -87,3 +87,16 @@ class DeviceBuffer:
             self.free()
         except Exception:  # noqa: BLE001
             pass
+
+
+class DeviceSpan:
+    """``nbytes`` bytes at ``offset`` inside a device buffer (anything with ``data_ptr()``), or at a raw device address: what a
+    ``device=True`` call takes where it wants a buffer that knows its size -- the ray block inside a scatter batch handed to
+    ``DeviceScene.trace_rays``.  Owns nothing; the buffer must outlive it."""
+
+    def __init__(self, base, nbytes: int, offset: int = 0):
+        self._base, self.offset, self.nbytes = base, int(offset), int(nbytes)
+
+    def data_ptr(self) -> int:
+        base = self._base.data_ptr() if callable(getattr(self._base, "data_ptr", None)) else int(self._base)
+        return base + self.offset

@@ -9,6 +9,11 @@ Its third -- the hit's material, and its colour under the scene's point lights -
 ``shade_lights`` (include/ptrace_surface.h, libptrace_surface.so), or ``WorldQueries.materials`` / ``point_light_radiance``,
 which take a :class:`RayHits` or a hit-record frame as it is: :class:`SurfaceColors` views the answer.
 
+Its fourth -- the bounce: the Russian roulette and ``brdf.scatter_ray`` of every record, each with a generator of its own
+carried from bounce to bounce -- goes through ``DeviceScene.scatter`` (include/ptrace_scatter.h, libptrace_scatter.so) or
+``WorldQueries.scatter``: :class:`ScatteredRays` views the answer, whose ray block goes straight back into ``trace_rays``.
+:func:`pcg_streams` makes the generators.
+
 Layout: planar.  A batch is ``[8, n]`` float64 -- origin xyz, direction xyz, tmin, tmax, the fields of ``Ray`` (ray.py:29-50);
 a result is one buffer, the int32 shape plane first (padded to 8 bytes), then the selected fp64 planes of ``n`` values each.
 """
@@ -26,6 +31,12 @@ _CHANNEL_OF = {"t": abi.HIT_T, "point": abi.HIT_POINT, "normal": abi.HIT_NORMAL,
 
 SURF_BRDF_COLOR, SURF_EMITTED, SURF_ALL = 1, 2, 3  # PT_SURF_* of include/ptrace_surface.h
 _SURF_OF = {"brdf_color": SURF_BRDF_COLOR, "emitted": SURF_EMITTED}
+
+
+SCAT_WEIGHT, SCAT_EMITTED, SCAT_ALL = 1, 2, 3  # PT_SCAT_* of include/ptrace_scatter.h
+SCAT_RAYS, SCAT_PCG = 4, 8  # plane selectors of scatter_plane_offset (always written: not channel bits)
+_SCAT_OF = {"weight": SCAT_WEIGHT, "emitted": SCAT_EMITTED}
+_PCG_MULT = 6364136223846793005
 
 
 def ray_channels(channels) -> int:
@@ -244,6 +255,141 @@ class SurfaceColors:
         return out
 
 
+def scatter_channels(channels) -> int:
+    """``PT_SCAT_*`` bits from an int, names (``"weight"``, ``"weight,emitted"``), ``"all"`` or ``"none"``."""
+    if isinstance(channels, str):
+        names = [x.strip().lower() for x in channels.split(",") if x.strip()]
+        if names == ["all"]:
+            return SCAT_ALL
+        if names == ["none"]:
+            return 0
+        unknown = [x for x in names if x not in _SCAT_OF]
+        if unknown:
+            raise ValueError(f"a scatter batch has the channels weight, emitted; not {', '.join(unknown)}")
+        return sum({_SCAT_OF[x] for x in names})
+    bits = int(channels)
+    if bits < 0 or bits & ~SCAT_ALL:
+        raise ValueError(f"a scatter batch has the channels weight (1), emitted (2); not {bits:#x}")
+    return bits
+
+
+def scatter_bytes(n: int, channels: int) -> int:
+    """Mirror of ``pt_rays_scatter_bytes``: 0 for arguments the library refuses."""
+    if not (0 <= n <= MAX_RAYS and 0 <= channels <= SCAT_ALL):
+        return 0
+    return ((n * 4 + 7) & ~7) + n * 8 * (10 + 3 * bin(channels).count("1"))
+
+
+def scatter_plane_offset(n: int, channels: int, channel: int, component: int = 0) -> int:
+    """Mirror of ``pt_rays_scatter_plane_offset`` (bytes; ``channel`` 0: the int32 status plane, ``SCAT_RAYS``: the eight ray
+    planes, ``SCAT_PCG``: state and increment, ``SCAT_WEIGHT`` / ``SCAT_EMITTED``; < 0: not selected)."""
+    if not (0 <= n <= MAX_RAYS and 0 <= channels <= SCAT_ALL):
+        return -1
+    pad = (n * 4 + 7) & ~7
+    if channel == 0:
+        return 0 if component == 0 else -1
+    if component < 0:
+        return -1
+    if channel == SCAT_RAYS:
+        return pad + n * 8 * component if component < 8 else -1
+    if channel == SCAT_PCG:
+        return pad + n * 8 * (8 + component) if component < 2 else -1
+    if channel not in (SCAT_WEIGHT, SCAT_EMITTED) or not channels & channel or component >= 3:
+        return -1
+    before = 3 if channel == SCAT_EMITTED and channels & SCAT_WEIGHT else 0
+    return pad + n * 8 * (10 + before + component)
+
+
+class ScatteredRays:
+    """Views over the buffer of a scatter batch (``buf``: ``pt_rays_scatter_bytes`` bytes, contiguous ``uint8``).  Nothing here
+    copies.  ``status``: -1 no hit, 0 terminated (by the roulette or a black BRDF pigment: the record's value is ``emitted``),
+    1 scattered; ``rays``: the ``[8, n]`` block ``trace_rays`` reads (a dead ray where ``status != 1``: it hits nothing);
+    ``pcg_state`` / ``pcg_inc``: every record's generator behind its draws; ``weight`` (the BRDF pigment's colour behind the
+    roulette's compensation) and ``emitted`` with the component as last axis.  ``shape``: what the records' axis is viewed as."""
+
+    def __init__(self, buf, n: int, channels=SCAT_ALL, shape=None):
+        self.channels = scatter_channels(channels)
+        self.n = int(n)
+        self.shape = (self.n,) if shape is None else tuple(int(x) for x in shape)
+        if int(np.prod(self.shape, dtype=np.int64)) != self.n:
+            raise ValueError(f"shape {self.shape} does not hold {self.n} records")
+        self.nbytes = scatter_bytes(self.n, self.channels)
+        buf = np.asarray(buf)
+        if buf.dtype != np.uint8 or buf.ndim != 1:
+            buf = buf.reshape(-1).view(np.uint8)
+        if buf.nbytes < self.nbytes:
+            raise ValueError(f"scatter buffer too small: {buf.nbytes} < {self.nbytes} bytes")
+        self.buffer = buf
+        self.status = buf[: self.n * 4].view(np.int32).reshape(self.shape)
+        off = scatter_plane_offset(self.n, self.channels, SCAT_RAYS, 0)
+        self.rays = buf[off: off + self.n * 64].view(np.float64).reshape(8, self.n)
+        pcg = buf[off + self.n * 64: off + self.n * 80].view(np.uint64).reshape(2, self.n)
+        self.pcg = pcg  # [2, n]: what the next scatter takes as it is
+        self.pcg_state, self.pcg_inc = pcg[0].reshape(self.shape), pcg[1].reshape(self.shape)
+
+    def _colour(self, channel: int) -> np.ndarray:
+        if not self.channels & channel:
+            name = next(k for k, v in _SCAT_OF.items() if v == channel)
+            raise KeyError(f"channel {name!r} was not selected for this scatter batch (channels = {self.channels:#x})")
+        off = scatter_plane_offset(self.n, self.channels, channel, 0)
+        planes = self.buffer[off: off + self.n * 24].view(np.float64).reshape((3,) + self.shape)
+        return np.moveaxis(planes, 0, -1)
+
+    def has(self, name: str) -> bool:
+        return bool(self.channels & _SCAT_OF[name])
+
+    @property
+    def scattered(self) -> np.ndarray:
+        return self.status == 1
+
+    @property
+    def dirs(self) -> np.ndarray:
+        """``[n, 3]``: the scattered directions -- the next step's ``dirs`` (a view of three of the ray planes)."""
+        return self.rays[3:6].T
+
+    @property
+    def weight(self) -> np.ndarray:
+        return self._colour(SCAT_WEIGHT)
+
+    @property
+    def emitted(self) -> np.ndarray:
+        return self._colour(SCAT_EMITTED)
+
+    def planes(self) -> dict:
+        out = {"status": self.status, "rays": self.rays, "pcg_state": self.pcg_state, "pcg_inc": self.pcg_inc}
+        for name in ("weight", "emitted"):
+            if self.has(name):
+                out[name] = getattr(self, name)
+        return out
+
+
+def pcg_streams(init_state, init_seqs, skip: int = 0) -> np.ndarray:
+    """``uint64[2, n]``: state and increment of ``PCG(init_state, seq)`` (pcg.py:25-41; csrc/pt_math.h: pcg_seed) for every
+    ``seq`` of ``init_seqs``, ``skip`` draws in -- the generators a scatter batch carries.  Every value of the 64-bit range is
+    legal and wraps, as the C arithmetic does: ``inc = (seq << 1) | 1``, ``state = (inc + init_state) * M + inc``, then the
+    jump ``state * A + inc * G`` with the two coefficients of ``skip`` steps (the generator is a linear congruential one)."""
+    from .hostmodel import pcg_advance
+
+    skip = int(skip)
+    if skip < 0:
+        raise ValueError("skip must not be negative")
+    if isinstance(init_seqs, np.ndarray) and init_seqs.dtype.kind in "iu":
+        seqs = init_seqs.astype(np.uint64).reshape(-1)  # (a signed array wraps like the C cast)
+    else:  # Python ints of any size (numpy would turn a list with values beyond 2^63 into floats)
+        seqs = np.array([int(x) & (2 ** 64 - 1) for x in np.atleast_1d(np.asarray(init_seqs, dtype=object)).reshape(-1)], dtype=np.uint64)
+    s0 = np.uint64(int(init_state) & (2 ** 64 - 1))
+    mult = np.uint64(_PCG_MULT)
+    out = np.empty((2, seqs.shape[0]), dtype=np.uint64)
+    with np.errstate(over="ignore"):
+        inc = (seqs << np.uint64(1)) | np.uint64(1)
+        state = (inc + s0) * mult + inc
+        if skip:
+            a, g = np.uint64(pcg_advance(1, 0, skip)), np.uint64(pcg_advance(0, 1, skip))
+            state = state * a + inc * g
+    out[0], out[1] = state, inc
+    return out
+
+
 def planar(values, components: int) -> np.ndarray:
     """``[..., components]`` -> the ``[components, n]`` planes the library reads.  The strided views of a :class:`RayHits` or
     a hit-record frame ARE such planes seen from the other side: for them this is a view, not a copy."""
@@ -286,3 +432,17 @@ class WorldQueries:
             dirs = hits.ray_dir
         out = self.scene.shade_lights(hits.shape_index, hits.point, hits.normal, hits.uv, dirs, ambient, background)
         return out.reshape(hits.shape_index.shape + (3,))
+
+    def scatter(self, hits, dirs, pcg, roulette: bool = False, channels=SCAT_ALL) -> ScatteredRays:
+        """The bounce of ``PathTracer.__call__`` (render.py:107-134, one child) for every record of ``hits`` -- a
+        :class:`RayHits` or a hit-record frame with ``point``, ``normal`` and ``uv``: the roulette (where ``roulette`` says that
+        ``ray.depth >= russian_roulette_limit`` holds) and ``brdf.scatter_ray``, drawing from ``pcg`` (``uint64[2, n]``: every
+        record's generator, :func:`pcg_streams` or the ``pcg`` of the scatter before).  ``dirs``: the directions of the rays
+        that were traced (``None``: a frame's ``ray_dir``) -> :class:`ScatteredRays`, shaped like ``hits.shape_index``."""
+        if dirs is None:
+            if not hasattr(hits, "ray_dir"):
+                raise ValueError("dirs= is needed: a ray batch does not carry the rays it was traced from")
+            dirs = hits.ray_dir
+        bits = scatter_channels(channels)
+        out = self.scene.scatter(hits.shape_index, hits.point, hits.normal, hits.uv, dirs, pcg, roulette, bits)
+        return ScatteredRays(out.buffer, out.n, bits, shape=hits.shape_index.shape)

@@ -1,4 +1,4 @@
-"""Three worked hit shaders: renderers of a user's own that get the GPU for their tracing half.
+"""Four worked hit shaders: renderers of a user's own that get the GPU for their tracing half.
 
 A *hit shader* is any object with a ``world`` attribute and a method ``shade_hits(frame) -> [nsamp, H, W, 3]``:
 ``GpuImageTracer.fire_all_rays(shader)`` renders the hit-record frame of its camera on the device
@@ -13,6 +13,11 @@ world that can intersect rays (pytracer's ``World``; the parameter holders of :m
 :class:`PointLightShader` is the reference's ``PointLightRenderer`` (render.py:157-193) put together from the public pieces:
 trace (the hit-record frame), then shade (``WorldQueries.point_light_radiance``: materials, shadow rays and the light sum on
 the device), with nothing but arrays in between.
+
+:class:`PathTracerShader` is the reference's ``PathTracer`` (render.py:99-139) with one ray per hit, put together the same way:
+trace, then per depth scatter (``WorldQueries.scatter``: pigments, Russian roulette and ``brdf.scatter_ray`` on the device, every
+sample's generator carried along) and trace again (``WorldQueries.ray_intersections`` on the scattered block), and at the end
+the recursion's sums in numpy.
 """
 from __future__ import annotations
 
@@ -180,3 +185,155 @@ class PointLightShader(_HitShader):
             lc = light.color
             r, g, b = r + bc[0] * lc.r * cos_theta * factor, g + bc[1] * lc.g * cos_theta * factor, b + bc[2] * lc.b * cos_theta * factor
         return Color(r, g, b)
+
+
+class PathTracerShader(_HitShader):
+    """``PathTracer`` (render.py:99-139) with ``num_of_rays=1`` as a hit shader, breadth-first: all samples of the frame take
+    their first bounce together, then their second, ... down to ``max_depth``; then the recursion unwinds in numpy with the
+    reference's own operations, ``cum = 0.0 + weight * child`` and ``emitted + cum * (1.0 / num_of_rays)`` (black beyond
+    ``max_depth``, ``background_color`` on a miss, ``emitted`` where the roulette ends a path).
+
+    Streams: sample ``k`` of pixel ``i = row * W + col`` owns ``PCG(S0, Q0 + i * S**2 + k)`` with (S0, Q0) the seeds of ``pcg``,
+    entered behind the sample's two jitter draws when ``samples_per_side > 0`` -- the fused path tracer's ``pcg_mode="sample"``
+    (csrc/pt_path.h: path_start_sample, path_seed_round).  Handed to a ``GpuImageTracer(..., pcg=PCG(S0, Q0),
+    pcg_mode="sample")`` -- the tracer's generator jitters the hit-record frame, so it has to have this shader's seeds -- the
+    frame is the one ``fire_all_rays(PathTracer(world, background_color, PCG(S0, Q0), 1, max_depth, limit))`` renders, byte
+    for byte.
+
+    What cannot be walked breadth-first is refused with a ``ValueError`` that names the alternative: ``num_of_rays != 1`` (the
+    children of a hit draw from ONE stream depth-first), a tracer with ``pcg_mode="seq"`` (one serial stream for the whole
+    frame) and ``pcg_mode="pixel"`` with more than one sample (a pixel's samples share a stream in program order).
+
+    ``__call__(ray)`` is the same arithmetic ray by ray, drawing from ``pcg`` itself, on a world that can intersect."""
+
+    hit_channels = abi.HIT_ALL
+    _ALTERNATIVE = ("hand the fused renderer to the tracer instead: GpuImageTracer.fire_all_rays(PathTracer(world, background_color, pcg, "
+                    "num_of_rays, max_depth, russian_roulette_limit)) renders every num_of_rays and pcg_mode on the device")
+
+    def __init__(self, world, tracer=None, background_color: Color = BLACK, pcg=None, num_of_rays: int = 1, max_depth: int = 10,
+                 russian_roulette_limit: int = 3):
+        super().__init__(world, background_color)
+        from .hostmodel import PCG
+
+        if int(num_of_rays) != 1:
+            raise ValueError(f"PathTracerShader traces one ray per hit, not num_of_rays={num_of_rays}: the children of a hit draw from one "
+                             f"stream depth-first, which cannot be walked breadth-first; {self._ALTERNATIVE}")
+        self.tracer = tracer
+        self.pcg = pcg if pcg is not None else PCG()
+        self.num_of_rays, self.max_depth, self.russian_roulette_limit = 1, int(max_depth), int(russian_roulette_limit)
+        self._check_tracer()
+
+    def _check_tracer(self) -> None:
+        tracer = self.tracer
+        if tracer is None:
+            return
+        mode, S = getattr(tracer, "pcg_mode", "sample"), int(getattr(tracer, "samples_per_side", 0))
+        if mode == "seq" or (mode == "auto" and S > 0):  # ("auto" jitters a hit-record frame from the serial stream)
+            raise ValueError(f'PathTracerShader needs a generator per sample, not pcg_mode="{mode}" (one serial stream for the whole '
+                             f'frame): build the tracer with pcg_mode="sample", or {self._ALTERNATIVE}')
+        if mode == "pixel" and S > 1:
+            raise ValueError(f'PathTracerShader needs a generator per sample, not pcg_mode="pixel" with {S * S} samples (a pixel\'s samples '
+                             f'share one stream in program order): build the tracer with pcg_mode="sample", or {self._ALTERNATIVE}')
+
+    def _queries(self):
+        if self.tracer is None:
+            raise TypeError("PathTracerShader.shade_hits needs the tracer whose device scene holds the world: PathTracerShader(world, tracer, ...)")
+        return self.tracer.world_queries(self.world)
+
+    def sample_streams(self, frame) -> np.ndarray:
+        """``uint64[2, n]``: the generator of every sample of ``frame`` where its path starts (behind the two jitter draws)."""
+        from . import flatten
+        from .rays import pcg_streams
+
+        s0, q0 = flatten.recover_seeds(self.pcg, True)
+        p = frame.params
+        grow = np.asarray(abi.rows_for_rank(p.height, p.row_block, p.n_ranks, p.rank), dtype=np.uint64)
+        with np.errstate(over="ignore"):
+            pix = grow[:, None] * np.uint64(frame.width) + np.arange(frame.width, dtype=np.uint64)[None, :]
+            seq = np.uint64(q0 & (2 ** 64 - 1)) + pix[None] * np.uint64(frame.nsamp) + np.arange(frame.nsamp, dtype=np.uint64)[:, None, None]
+        return pcg_streams(s0, seq.reshape(-1), 2 if frame.samples_per_side > 0 else 0)
+
+    def shade_hits(self, frame) -> np.ndarray:
+        from .rays import SCAT_ALL
+
+        self._check_tracer()
+        q = self._queries()
+        bg = self.background_color
+        bg = np.array((bg.r, bg.g, bg.b), dtype=np.float64)
+        shape3 = frame.shape_index.shape
+        hits, dirs, pcg = frame, None, self.sample_streams(frame)
+        levels = []
+        for depth in range(self.max_depth + 1):
+            sc = q.scatter(hits, dirs, pcg, roulette=depth >= self.russian_roulette_limit, channels=SCAT_ALL)
+            status = np.asarray(sc.status).reshape(-1)
+            levels.append((status, np.asarray(sc.weight).reshape(-1, 3), np.asarray(sc.emitted).reshape(-1, 3),
+                           depth >= self.russian_roulette_limit))
+            if depth == self.max_depth or not np.any(status == 1):  # (a child beyond max_depth is black without a query)
+                break
+            hits, dirs, pcg = q.ray_intersections(sc.rays.T, channels="point,normal,uv"), sc.dirs, sc.pcg
+        # render.py:135-139 from the deepest call upwards.  (A path that ends at a hit without the roulette ended on a black BRDF
+        # pigment: the reference still adds its empty sum, emitted + 0.0 * (1.0 / num_of_rays).)
+        k = 1.0 / self.num_of_rays
+        val = np.zeros((status.shape[0], 3), dtype=np.float64)
+        for status, weight, emitted, roulette in reversed(levels):
+            cum = 0.0 + weight * val
+            ended = emitted if roulette else emitted + 0.0 * k
+            val = np.where((status == 1)[:, None], emitted + cum * k, np.where((status == 0)[:, None], ended, bg[None, :]))
+        return val.reshape(shape3 + (3,))
+
+    # -- ray by ray ---------------------------------------------------------------------------------------------------------
+    def __call__(self, ray) -> Color:
+        if not callable(getattr(self.world, "ray_intersection", None)):
+            raise TypeError(f"{type(self.world).__name__} has no ray_intersection(ray): it is a parameter holder that cannot trace a ray.  "
+                            "Hand PathTracerShader to GpuImageTracer.fire_all_rays (the device traces), or give it a pytracer World")
+        return self._radiance(ray, int(getattr(ray, "depth", 0)))
+
+    def _radiance(self, ray, depth: int) -> Color:
+        from .hits import HitRay
+        from .hostmodel import Vec
+
+        if depth > self.max_depth:
+            return Color(0.0, 0.0, 0.0)
+        record = self.world.ray_intersection(ray)
+        if record is None:
+            return self.background_color
+        material = getattr(record, "material", None) or self.world.shapes[record.shape_index].material
+        uv, wp, nrm = record.surface_point, record.world_point, record.normal
+        hc, em = pigment_color(material.brdf.pigment, uv), pigment_color(material.emitted_radiance, uv)
+        r, g, b = hc.r, hc.g, hc.b
+        lum = max(max(r, g), b)
+        if depth >= self.russian_roulette_limit:  # render.py:116-123
+            q = max(0.05, 1 - lum)
+            if self.pcg.random_float() > q:
+                f = 1.0 / (1.0 - q)
+                r, g, b = r * f, g * f, b * f
+            else:
+                return em
+        cr = cg = cb = 0.0
+        if lum > 0.0:
+            d = ray.dir
+            o, nd, tmin = scatter_ray(material.brdf, self.pcg, (d.x, d.y, d.z), (wp.x, wp.y, wp.z), (nrm.x, nrm.y, nrm.z))
+            child = self._radiance(HitRay(Vec(*o), Vec(*nd), tmin, float("inf"), depth + 1), depth + 1)
+            cr, cg, cb = cr + r * child.r, cg + g * child.g, cb + b * child.b
+        k = 1.0 / self.num_of_rays
+        return Color(em.r + cr * k, em.g + cg * k, em.b + cb * k)
+
+
+def scatter_ray(brdf, pcg, in_dir, point, normal):
+    """``brdf.scatter_ray`` (materials.py:132-152, 175-196; the orthonormal basis of geometry.py:247-262) in Python floats with
+    ``x * x`` for ``x**2``, for a BRDF that may be a parameter holder (by class name) -> (origin, direction, tmin)."""
+    nx, ny, nz = normal
+    if type(brdf).__name__ == "SpecularBRDF":
+        rd, nn = _unit(*in_dir), _unit(nx, ny, nz)
+        dp = nn[0] * rd[0] + nn[1] * rd[1] + nn[2] * rd[2]
+        return point, (rd[0] - dp * (2.0 * nn[0]), rd[1] - dp * (2.0 * nn[1]), rd[2] - dp * (2.0 * nn[2])), 1e-5
+    sign = 1.0 if nz > 0.0 else -1.0
+    a = -1.0 / (sign + nz)
+    b = nx * ny * a
+    e1 = (1.0 + sign * nx * nx * a, sign * b, -sign * nx)
+    e2 = (b, sign + ny * ny * a, -ny)
+    cts = pcg.random_float()
+    ct, st = math.sqrt(cts), math.sqrt(1.0 - cts)
+    phi = 2.0 * math.pi * pcg.random_float()
+    cp, sp = math.cos(phi), math.sin(phi)
+    return point, tuple(ct * (cp * e1[i]) + ct * (sp * e2[i]) + st * normal[i] for i in range(3)), 1.0e-3

@@ -1,0 +1,186 @@
+"""Worlds, hit records with generators, and their expected bounces for the scatter tests (tests/test_scatter_host.py,
+tests/test_gpu_scatter.py).
+
+Per world the records of ``surface_batches.batch`` (the oracle's ``world_intersect`` of the frame's primary rays and of the
+mirror bounces off their hits), record ``i`` with the generator ``PCG(S0, Q0 + i)``.  Expected, per record and for ``roulette``
+0 and 1, in a Python loop over the oracle in its ``x * x`` mode -- render.py:107-134 for one child:
+
+* ``oracle.pigment`` twice (hit colour, emitted), ``lum = max(max(r, g), b)``;
+* the roulette: ``oracle.Pcg.random_float``, ``q = max(0.05, 1 - lum)``, ``hit_color * (1.0 / (1.0 - q))`` or termination;
+* ``oracle.scatter`` for the ray of a record that goes on (``lum > 0``);
+* the generator's words read back from ``Pcg.st``.
+
+Besides ``demo`` (diffuse, mirror, emissive, misses), ``c2`` and ``pigments`` there is ``roulette4``, a tiny world of four
+spheres for the roulette's cases: a black pigment (``lum == 0``: every record ends, with the roulette by its one draw), a
+pigment with ``lum > 1`` (``q`` clamps at 0.05), and ``lum`` in (0, 1) on a diffuse and on a mirror sphere.
+
+Computed once per process and shared; nothing here is modified by a test."""
+import numpy as np
+
+from pytracer_amd import abi, flatten, rays as rb
+from pytracer_amd import hostmodel as hm
+
+from . import ray_batches as B
+from . import surface_batches as S
+
+S0, Q0 = 45, 54  # chosen once: with them both outcomes of the roulette occur in every world's batch (checked in batch())
+WORLDS = ("demo", "c2", "pigments", "roulette4")
+BOTH_KINDS = ("demo", "roulette4")  # worlds whose batch must hold diffuse AND mirror records that scatter
+TINY_SIZE = (32, 24)
+DEAD_RAY = np.array([0.0, 0.0, 0.0, 0.0, 0.0, 1.0, 0.0, 0.0])  # include/ptrace_scatter.h
+
+_worlds, _records, _batches = {}, {}, {}
+
+
+def tiny_world():
+    """-> (hostmodel World, camera): four unit spheres side by side in front of the default camera."""
+    mats = [hm.Material(hm.DiffuseBRDF(hm.UniformPigment(hm.Color(0.0, 0.0, 0.0))), hm.UniformPigment(hm.Color(0.5, 0.25, 0.125))),
+            hm.Material(hm.DiffuseBRDF(hm.UniformPigment(hm.Color(1.5, 0.8, 0.2))), hm.UniformPigment(hm.Color(0.0, 0.0, 0.0))),
+            hm.Material(hm.DiffuseBRDF(hm.UniformPigment(hm.Color(0.3, 0.6, 0.45))), hm.UniformPigment(hm.Color(0.05, 0.0, 0.1))),
+            hm.Material(hm.SpecularBRDF(hm.UniformPigment(hm.Color(0.7, 0.2, 0.55))), hm.UniformPigment(hm.Color(0.0, 0.0, 0.0)))]
+    world = hm.World()
+    for (y, z), m in zip(((1.05, 1.05), (-1.05, 1.05), (1.05, -1.05), (-1.05, -1.05)), mats):
+        world.add_shape(hm.Sphere(hm.translation(hm.Vec(2.0, y, z)), m))
+    return world, hm.PerspectiveCamera(screen_distance=1.0, aspect_ratio=TINY_SIZE[0] / TINY_SIZE[1])
+
+
+def host_world(name):
+    return tiny_world() if name == "roulette4" else S.host_world(name)
+
+
+def size(name):
+    return TINY_SIZE if name == "roulette4" else S.WORLDS[name]
+
+
+def world(name):
+    """-> (FlatScene, Camera)"""
+    if name != "roulette4":
+        return S.world(name)
+    if name not in _worlds:
+        wd, cam = tiny_world()
+        _worlds[name] = (flatten.flatten_world(wd), flatten.flatten_camera(cam))
+    return _worlds[name]
+
+
+def records(orc, name) -> dict:
+    """-> {"rays": [n, 8], "rec": RayHits (the oracle's records), "n_primary": int}: ``surface_batches.batch``'s, or for the tiny
+    world the same construction."""
+    if name != "roulette4":
+        return S.batch(orc, name)
+    if name not in _records:
+        flat, cam = world(name)
+        w, h = TINY_SIZE
+        first = np.array([orc.tracer_fire_ray(cam, w, h, col, row) for row in range(h) for col in range(w)])
+        rays = np.vstack([first, S.mirror_bounces(first, B.expected(orc, flat, first))])
+        rec = B.expected(orc, flat, rays)
+        rays.setflags(write=False)
+        rec.buffer.setflags(write=False)
+        _records[name] = {"rays": rays, "rec": rec, "n_primary": first.shape[0]}
+    return _records[name]
+
+
+def streams(n: int, first: int = 0) -> np.ndarray:
+    """``uint64[2, n]``: the generators of records ``first .. first + n - 1``, ``PCG(S0, Q0 + i)``."""
+    return rb.pcg_streams(S0, Q0 + first + np.arange(n, dtype=np.uint64))
+
+
+def state_drawing_one() -> int:
+    """A generator state whose next ``random()`` is 0xFFFFFFFF, i.e. whose next ``random_float()`` is exactly 1.0 (pcg.py:43-58:
+    rotation 0 -- the top five bits clear -- and bits 27 .. 58 of ``(state >> 18) ^ state`` all set, solved from the top down).
+    A record's generator is handed over as raw words, so the draw can be aimed: on a black pigment ``q = max(0.05, 1 - 0) = 1.0``
+    and the draw EQUALS q -- ``draw > q`` fails, the path ends, and ``1.0 / (1.0 - q)`` is never formed."""
+    old = 0
+    for b in range(58, 26, -1):
+        if not (old >> (b + 18)) & 1:
+            old |= 1 << b
+    return old
+
+
+def expected(orc, flat, rec, dirs, pcg, roulette: bool) -> dict:
+    """render.py:107-134 for one child of every record, through the oracle -> the planes a scatter batch holds:
+    {"status" [n] int32, "rays" [8, n], "pcg" [2, n] uint64, "weight" [n, 3], "emitted" [n, 3], "kind" [n] (BRDF kind, -1: no hit)}."""
+    n = rec.n
+    status, kind = np.full(n, -1, np.int32), np.full(n, -1, np.int32)
+    rays = np.tile(DEAD_RAY[:, None], (1, n))
+    gen = np.array(pcg, dtype=np.uint64)
+    weight, emitted = np.zeros((n, 3)), np.zeros((n, 3))
+    uv, point, normal = np.array(rec.uv), np.array(rec.point), np.array(rec.normal)
+    dirs = np.asarray(dirs, dtype=np.float64)
+    for i in np.flatnonzero(rec.hit):
+        s = int(rec.shape_index[i])
+        u, v = float(uv[i, 0]), float(uv[i, 1])
+        hc, em = orc.pigment(flat, s, False, u, v), orc.pigment(flat, s, True, u, v)
+        lum = max(max(float(hc[0]), float(hc[1])), float(hc[2]))
+        g = orc.Pcg()
+        g.st[0], g.st[1] = int(gen[0, i]), int(gen[1, i])
+        alive = True
+        if roulette:
+            q = max(0.05, 1 - lum)
+            if g.random_float() > q:
+                hc = hc * (1.0 / (1.0 - q))
+            else:
+                alive = False
+        status[i], kind[i] = 0, int(flat.brdf_kind[s])
+        if alive and lum > 0.0:
+            rays[:, i] = orc.scatter(int(kind[i]), g, dirs[i], point[i], normal[i], 0)
+            status[i] = 1
+        gen[0, i] = g.state
+        weight[i], emitted[i] = hc, em
+    return {"status": status, "rays": rays, "pcg": gen, "weight": weight, "emitted": emitted, "kind": kind}
+
+
+def batch(orc, name) -> dict:
+    """-> {"rays", "rec", "n_primary", "dirs": [n, 3], "pcg": uint64[2, n], "want": {False: ..., True: ...}} with ``want[roulette]``
+    the planes of :func:`expected`.  Asserts what the GPU comparisons rely on: both outcomes of the roulette in every world, both
+    BRDF kinds among the scattered records of ``demo`` and the tiny world, and the tiny world's four cases."""
+    if name in _batches:
+        return _batches[name]
+    old = orc.lib().pto_get_sqr_mode()
+    orc.set_sqr_mode(orc.SQR_MUL)
+    try:
+        r = records(orc, name)
+        flat = world(name)[0]
+        rec = r["rec"]
+        dirs = np.ascontiguousarray(r["rays"][:, 3:6])
+        pcg = streams(rec.n)
+        want = {flag: expected(orc, flat, rec, dirs, pcg, flag) for flag in (False, True)}
+        out = {"rays": r["rays"], "rec": rec, "n_primary": r["n_primary"], "dirs": dirs, "pcg": pcg, "want": want}
+        for a in [dirs, pcg] + [x for w in want.values() for x in w.values()]:
+            a.setflags(write=False)
+        check(name, out, flat)
+        _batches[name] = out
+        return out
+    finally:
+        orc.set_sqr_mode(old)
+
+
+def check(name, b, flat) -> dict:
+    """The properties of a batch the tests rely on; -> counts (for a test's printout)."""
+    rec, plain, rr = b["rec"], b["want"][False], b["want"][True]
+    hit = rec.hit
+    survived = hit & np.any(rr["weight"] != plain["weight"], axis=1)  # (compensated: 1 / (1 - q) > 1 changes a non-black colour)
+    ended = hit & (rr["status"] == 0) & (plain["status"] == 1)        # ended by the roulette alone
+    counts = {"records": rec.n, "hits": int(hit.sum()), "survived": int(survived.sum()), "ended": int(ended.sum()),
+              "diffuse": int(((plain["status"] == 1) & (plain["kind"] == abi.BRDF_DIFFUSE)).sum()),
+              "mirror": int(((plain["status"] == 1) & (plain["kind"] == abi.BRDF_SPECULAR)).sum())}
+    assert counts["survived"] > 10 and counts["ended"] > 10, (name, counts)
+    assert np.array_equal(plain["status"] == -1, ~hit) and np.array_equal(rr["status"] == -1, ~hit)
+    # a draw per hit under the roulette, two more per diffuse bounce, none otherwise: the generators say so
+    assert np.array_equal(plain["pcg"][0] != b["pcg"][0], (plain["status"] == 1) & (plain["kind"] == abi.BRDF_DIFFUSE))
+    assert np.array_equal(rr["pcg"][0] != b["pcg"][0], hit) and np.array_equal(rr["pcg"][1], b["pcg"][1])
+    if name in BOTH_KINDS:
+        assert counts["diffuse"] > 10 and counts["mirror"] > 10, (name, counts)
+    if name == "demo":
+        assert (~hit).sum() > 100 and np.any(plain["emitted"] != 0.0)
+    if name == "roulette4":
+        shape = np.asarray(rec.shape_index)
+        for s in range(4):
+            assert (shape == s).sum() > 10, (s, int((shape == s).sum()))
+        black, bright, mid, mirror = (shape == s for s in range(4))
+        assert np.all(plain["status"][black] == 0) and np.all(rr["status"][black] == 0)   # lum == 0: ends with and without the roulette
+        assert np.all(rr["pcg"][0][black] != b["pcg"][0][black])                           # ... behind the roulette's one draw
+        k = 1.0 / (1.0 - 0.05)                                                            # lum > 1: q clamps at 0.05
+        assert np.all(rr["weight"][bright & survived] == np.array([1.5, 0.8, 0.2]) * k) and (bright & survived).sum() > 10
+        assert (mid & survived).sum() > 3 and (mid & ended).sum() > 3 and (mirror & survived).sum() > 3 and (mirror & ended).sum() > 3
+        assert np.all(plain["kind"][mirror] == abi.BRDF_SPECULAR)
+    return counts

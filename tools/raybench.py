@@ -15,7 +15,16 @@ Needs torch only to put the batches into device memory and to read the events.
 The surface queries (libptrace_surface.so) on the same frame of C2 with two point lights, (-2, 3, 6) and (1, -4, 5) radius 2:
 ``surface`` (both colours) and ``shade_lights`` on the frame's hit records, read in place out of the hit-record buffer in HBM,
 timed the same way; then the two-step point-light frame -- the ``pt_render_hits`` kernel plus ``shade_lights`` -- beside the
-fused RENDERER_POINTLIGHT frame kernel (``stats().kernel_ms``), which culls per tile and keeps the record in registers."""
+fused RENDERER_POINTLIGHT frame kernel (``stats().kernel_ms``), which culls per tile and keeps the record in registers.
+
+    python tools/raybench.py --scatter [...]
+
+The bounce (libptrace_scatter.so: pt_rays_scatter_device) on the hit records of the C2 frame, read in place out of the
+hit-record buffer in HBM, a generator per record, both channels, with ``roulette`` 0 and 1, timed the same way: records/s and the
+effective bandwidth from the bytes a record moves (112 B in, 132 B out; a record without a hit reads 20 B of them), beside the
+6.29 TB/s a float4 copy reaches on this chip.  Then the whole ``PathTracerShader`` route (hit-record frame, then per depth a
+scatter and a trace, the sums on the host) beside the fused ``PathTracer`` at ``num_of_rays=1, max_depth=3``: wall time of
+``fire_all_rays``, and whether the two frames are byte-identical."""
 import argparse
 import ctypes as C
 import os
@@ -33,9 +42,12 @@ def main():
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--steps", type=int, default=10)
     ap.add_argument("--shade", action="store_true", help="time the surface queries instead of the ray batches")
+    ap.add_argument("--scatter", action="store_true", help="time the bounce (roulette + scatter_ray) and the PathTracerShader route")
     args = ap.parse_args()
     if args.shade:
         return shade(args)
+    if args.scatter:
+        return scatter(args)
     import torch
 
     from pytracer_amd import _rays_lib, abi, flatten, rays as rb, scenes
@@ -146,6 +158,81 @@ def shade(args):
         print(f"pt_render_hits + shade_lights {two_step:.3f} ms = {two_step / fused_ms:.2f} x the fused kernel; the two frames are "
               f"{'byte-identical' if same else 'DIFFERENT'}")
         return 0 if same else 1
+
+
+COPY_TBS = 6.29  # a float4 copy kernel on this chip (the ceiling a streaming kernel is held against)
+SCATTER_BYTES_IN, SCATTER_BYTES_OUT = 112, 132  # per record with a hit, both channels (include/ptrace_scatter.h)
+
+
+def scatter(args):
+    import time
+
+    import torch
+
+    from pytracer_amd import abi, flatten, hostmodel as hm, rays as rb, scenes, shaders
+    from pytracer_amd.device import DeviceScene
+    from pytracer_amd.devmem import DeviceBuffer
+    from pytracer_amd.tracer import GpuImageTracer
+
+    W, H = args.width, args.height
+    n = W * H
+    world = scenes.synthetic_world(32, with_plane=True)
+    flat = flatten.flatten_world(world)
+    camera = scenes.synthetic_camera(W, H)
+    cam = flatten.flatten_camera(camera)
+    p_hits = abi.make_params(W, H, abi.RENDERER_FLAT, samples_per_side=0)
+    with DeviceScene(flat) as ds:
+        frame = ds.render_hits(cam, p_hits, abi.HIT_ALL)
+        hit = int(frame.hit.sum())
+        buf = torch.from_numpy(frame.buffer).cuda()
+        base = buf.data_ptr()
+        at = lambda ch, comp=0: base + abi.hits_plane_offset(p_hits, abi.HIT_ALL, ch, comp)  # noqa: E731
+        pcg = torch.from_numpy(rb.pcg_streams(42, 54 + np.arange(n, dtype=np.uint64)).view(np.int64)).cuda()
+        out = DeviceBuffer((rb.scatter_bytes(n, rb.SCAT_ALL),), np.uint8)
+        ds.slot_table()
+        stream = torch.cuda.Stream()
+        torch.cuda.synchronize()
+        print(f"C2 {W}x{H}: {n} records in the hit-record frame, {hit} with a hit; {SCATTER_BYTES_IN} B in + {SCATTER_BYTES_OUT} B out per record")
+        for roulette in (0, 1):
+            def go():
+                ds.scatter(base, at(abi.HIT_POINT), at(abi.HIT_NORMAL), at(abi.HIT_UV), at(abi.HIT_RAY, 3), pcg, roulette, "all",
+                           device=True, stream=stream.cuda_stream, out=out, n=n)
+
+            for _ in range(args.warmup):
+                go()
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record(stream)
+            for _ in range(args.steps):
+                go()
+            e1.record(stream)
+            e1.synchronize()
+            ms = e0.elapsed_time(e1) / args.steps
+            sc = rb.ScatteredRays(out.numpy(), n)
+            tbs = n * (SCATTER_BYTES_IN + SCATTER_BYTES_OUT) / (ms * 1e-3) / 1e12
+            print(f"scatter roulette={roulette} (weight, emitted) {n:8d} records  {ms:8.3f} ms  {n / ms / 1e3:8.1f} Mrecord/s  "
+                  f"{tbs:5.2f} TB/s effective = {tbs / COPY_TBS:.2f} x the {COPY_TBS} TB/s of a float4 copy  "
+                  f"({int((sc.status == 1).sum())} scattered, {int((sc.status == 0).sum())} terminated)")
+    # the whole route beside the fused renderer
+    bg = hm.Color(0.1, 0.2, 0.3)
+    images = {}
+    for label, make in (("fused PathTracer", lambda t: hm.PathTracer(world, bg, hm.PCG(45, 54), 1, 3, 2)),
+                        ("PathTracerShader", lambda t: shaders.PathTracerShader(world, t, bg, hm.PCG(45, 54), 1, 3, 2))):
+        image = hm.HdrImage(W, H)
+        tracer = GpuImageTracer(image, camera, samples_per_side=0, pcg=hm.PCG(45, 54), pcg_mode="sample")
+        func = make(tracer)
+        wall = []
+        for _ in range(args.warmup + args.steps):
+            t0 = time.perf_counter()
+            tracer.fire_all_rays(func)
+            wall.append((time.perf_counter() - t0) * 1e3)
+        images[label] = np.array(image.array)
+        kernel = f", kernel {tracer.last_stats.kernel_ms:.3f} ms" if label.startswith("fused") else ""
+        print(f"{label:18s} num_of_rays=1 max_depth=3 limit=2: fire_all_rays {float(np.median(wall[args.warmup:])):9.3f} ms wall{kernel}  "
+              f"(last_path {tracer.last_path})")
+        tracer.close()
+    same = images["fused PathTracer"].tobytes() == images["PathTracerShader"].tobytes()
+    print(f"the two frames are {'byte-identical' if same else 'DIFFERENT'}")
+    return 0 if same else 1
 
 
 if __name__ == "__main__":
