@@ -306,6 +306,8 @@ static inline void pt_make_plan(const PtSceneFacts &s, const pt_camera *cam, con
     pl.grid4_y = (unsigned)(((rows + 15) / 16 + 1) / 2);
     grid = (int)(pl.grid4_x * pl.grid4_y);
     const size_t scene_bytes = (size_t)s.n_shapes * (PT_PLAN_REC_BYTES + PT_PLAN_AUX_BYTES);
+    // (24 KB: this limit is also what bounds the kernel's unrolled staging copy, PT_TILE4_STAGE_ROUNDS in pt_tile.h --
+    //  6 rounds of 4 waves x 1 KiB; raise the two together)
     pl.t4lds = t.tile4_lds != 0 && p->renderer == PT_RENDERER_FLAT && scene_bytes <= 24 * 1024;
     pl.lds_main = pl.t4lds ? scene_bytes : 0;
   }

@@ -966,12 +966,17 @@ PT_DEV void sphere_roots1(const PtKArgs &a, int slot, bool active, double tmin, 
 }
 
 // SLDS (small worlds, Flat): the shapes' records (128 B + 256 B each) are staged in LDS by the workgroup and shading
-//   gathers from there instead of through the vector memory path (C2: 14.4 -> 13.9 us per frame).
+//   gathers from there instead of through the vector memory path (C2: 14.4 -> 13.9 us per frame).  The copy is asynchronous
+//   (global -> LDS loads issued at the top, no register staging) and is waited for by the one barrier in front of the shading.
 // (A variant with 16x8 tiles and two pixels per lane -- twice the waves, half the pixels each, for frames whose 16x16 tiles do
 //  not fill the chip -- was measured slower on every frame and deleted in round 6: profiles/DROPPED_VARIANTS.md.)
 #ifndef PT_TILE4_WAVES
 #define PT_TILE4_WAVES 4  // waves per SIMD the register allocation aims at (5 / 6 measured: profiles/DROPPED_VARIANTS.md)
 #endif
+// SLDS: rounds of the staging copy, one 1 KiB chunk per wave and round.  6 rounds x 4 waves x 1 KiB = the 24 KB up to which the
+// plan stages (pt_plan.h: t4lds); the host refuses to launch the staged variant on a larger image.
+#define PT_TILE4_STAGE_ROUNDS 6
+#define PT_PIN_SGPR(x) asm volatile("" : "+s"(x))  // the value exists HERE, in a scalar register
 template <int RENDERER, bool SLDS = false>
 __global__ __launch_bounds__(PT_BLOCK) __attribute__((amdgpu_waves_per_eu(PT_TILE4_WAVES, 8))) void pt_tile4_kernel(const PtKArgs a) {
   constexpr int NPX = 4;  // pixels per lane: the four 8x8 quadrants of the tile
@@ -984,34 +989,85 @@ __global__ __launch_bounds__(PT_BLOCK) __attribute__((amdgpu_waves_per_eu(PT_TIL
 #else
 #define PT_T4(k) do { } while (0)
 #endif
-  int W, rows_local, npass;
-  bool dome_on, out_f32;
-  {
-    pt_kargs c = cold_args(a);
-    out_f32 = c->out_f32 != 0;
-    W = c->W;
-    rows_local = c->rows_local;
-    npass = c->npass;
-    dome_on = c->dome_shortcut != 0;
+  const int lane = threadIdx.x & 63, wib = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+  // ---- everything the front end reads from memory is asked for in ONE batch behind the kernel arguments: every field of
+  //      the cold block that cone, cull and shortcut need, the lane's bounding sphere, the staging copy ----
+  int W, rows_local, npass, n_ranks, row_block, rank, dome_sw, f32_sw, cam_kind;
+  ConeCam cam;
+  pt_kargs c0 = cold_args(a);
+  W = c0->W;
+  rows_local = c0->rows_local;
+  npass = c0->npass;
+  dome_sw = c0->dome_shortcut;
+  f32_sw = c0->out_f32;
+  n_ranks = c0->n_ranks;
+  row_block = c0->row_block;
+  rank = c0->rank;
+  cam_kind = c0->cam_kind;
+  for (int i = 0; i < 3; ++i) {
+    cam.d0[i] = c0->cone_d0[i];
+    cam.dx[i] = c0->cone_dx[i];
+    cam.dy[i] = c0->cone_dy[i];
+    cam.apex[i] = c0->cone_apex[i];
   }
-  const int lane = threadIdx.x & 63, wib = threadIdx.x >> 6;
+  const float4 b_first = a.bounds[lane < a.n_shapes ? lane : 0];
+  if constexpr (SLDS) {
+    // recs[] then aux[] into LDS, straight from global memory (no register in between), 16 bytes per lane: chunk c is the
+    // bytes [1024 c, 1024 c + 1024) of the image, wave w takes the chunks w, w + 4, ...  128 n is a multiple of 16, so no lane
+    // straddles the two tables; lanes past the image are switched off.  Nothing waits for these loads here: the one
+    // barrier in front of the shading retires them.
+    const int nrec = a.n_shapes * (int)sizeof(PtShapeRec), nimg = nrec + a.n_shapes * (int)sizeof(PtShapeAux);
+    const char *src_rec = (const char *)a.recs, *src_aux = (const char *)a.aux - nrec;
+#pragma unroll
+    for (int r = 0; r < PT_TILE4_STAGE_ROUNDS; ++r) {
+      const int cbase = (r * (PT_BLOCK / 64) + wib) * 1024, b = cbase + lane * 16;
+      if (b < nimg)
+        __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void *)((b < nrec ? src_rec : src_aux) + b),
+                                         (__attribute__((address_space(3))) void *)((char *)pt_lds_masks + cbase), 16, 0, 0);
+    }
+  }
+  // (pinned: the scalar loads above must not sink into the branches that use their results, where each would be a
+  //  dependent round trip of its own)
+  PT_PIN_SGPR(f32_sw);
+  PT_PIN_SGPR(n_ranks);
+  PT_PIN_SGPR(row_block);
+  PT_PIN_SGPR(rank);
+  PT_PIN_SGPR(W);
+  PT_PIN_SGPR(rows_local);
+  PT_PIN_SGPR(npass);
+  PT_PIN_SGPR(dome_sw);
+  PT_PIN_SGPR(cam_kind);
+  for (int i = 0; i < 3; ++i) {
+    PT_PIN_SGPR(cam.d0[i]);
+    PT_PIN_SGPR(cam.dx[i]);
+    PT_PIN_SGPR(cam.dy[i]);
+    PT_PIN_SGPR(cam.apex[i]);
+  }
+  cam.ortho = cam_kind != PT_CAMERA_PERSPECTIVE;
+  const bool dome_on = dome_sw != 0, out_f32 = f32_sw != 0;
   const int tx = blockIdx.x * 2 + (wib & 1), ty = blockIdx.y * 2 + (wib >> 1);
   unsigned long long nrays = 0, nres = 0;
   const bool valid = tx * 16 < W && ty * TH < rows_local;  // (wave-uniform; the ray count below needs every wave)
-  if (SLDS) {  // recs[] then aux[] into LDS (8-byte words; every wave of the workgroup takes part)
-    const unsigned long long *src = (const unsigned long long *)a.recs;
-    for (int k = threadIdx.x; k < a.n_shapes * 16; k += PT_BLOCK) pt_lds_masks[k] = src[k];
-    src = (const unsigned long long *)a.aux;
-    for (int k = threadIdx.x; k < a.n_shapes * 32; k += PT_BLOCK) pt_lds_masks[a.n_shapes * 16 + k] = src[k];
-    __syncthreads();  // (measured: placing this barrier before the shading instead, behind cone / cull / query, gains nothing)
-  }
+  // Every wave of the workgroup runs the same three phases: the front phase (cone, cull, then the shortcut or the query),
+  // ONE barrier, the shading phase.  `valid` and `shade` are wave-uniform and only ever skip a phase's WORK.
+  bool shade = false;
+  bool act[4];
+  long long pix[4];
+  V3 org, dir[4];
+  double bgx, bgy, bgz;
+  Hit4 h4;
+  const double tmin = 1.0e-5;
   if (valid) {
     // ---- cone + cull of the 16 x 16 tile ----
     const int lr0 = ty * TH, lr1 = (lr0 + TH - 1 < rows_local) ? lr0 + TH - 1 : rows_local - 1;
-    const int gr0 = global_row(a, lr0);  // the tile's rows are consecutive image rows (host: n_ranks == 1 or row_block % 16 == 0)
-    const float4 b_first = a.bounds[lane < a.n_shapes ? lane : 0];
+    // global_row(): the tile's rows are consecutive image rows (host: n_ranks == 1 or row_block % 16 == 0)
+    int gr0 = lr0;
+    if (n_ranks != 1) {
+      const int blk = lr0 / row_block;
+      gr0 = (blk * n_ranks + rank) * row_block + (lr0 - blk * row_block);
+    }
     PT_T4(0);
-    const TileCone tc = tile_cone(a, tx * 16, (tx * 16 + 16 < W) ? tx * 16 + 16 : W, gr0, gr0 + (lr1 - lr0));
+    const TileCone tc = tile_cone(cam, tx * 16, (tx * 16 + 16 < W) ? tx * 16 + 16 : W, gr0, gr0 + (lr1 - lr0));
     PT_T4(1);
     unsigned long long masks[4] = {0ULL, 0ULL, 0ULL, 0ULL};  // (npass <= 4: the host sends larger worlds elsewhere)
     int nsurv = 0, only = 0;
@@ -1039,10 +1095,16 @@ __global__ __launch_bounds__(PT_BLOCK) __attribute__((amdgpu_waves_per_eu(PT_TIL
     const int colA = tx * 16 + (lane & 7), colB = colA + 8;
     const int lrowA = lr0 + (lane >> 3), lrowB = lrowA + 8;
     const bool okcA = colA < W, okcB = colB < W, okrA = lrowA < rows_local, okrB = lrowB < rows_local;
-    const bool act[4] = {okcA && okrA, okcB && okrA, okcA && okrB, okcB && okrB};
+    act[0] = okcA && okrA;
+    act[1] = okcB && okrA;
+    act[2] = okcA && okrB;
+    act[3] = okcB && okrB;
     const int ccA = okcA ? colA : W - 1, ccB = okcB ? colB : W - 1;  // idle lanes stand on a real pixel
     const int crA = okrA ? lrowA : rows_local - 1, crB = okrB ? lrowB : rows_local - 1;
-    const long long pix[4] = {(long long)crA * W + ccA, (long long)crA * W + ccB, (long long)crB * W + ccA, (long long)crB * W + ccB};
+    pix[0] = (long long)crA * W + ccA;
+    pix[1] = (long long)crA * W + ccB;
+    pix[2] = (long long)crB * W + ccA;
+    pix[3] = (long long)crB * W + ccB;
     bool done = false;
     // ---- the dome shortcut (see pt_tile_kernel): one survivor, the camera well inside it, uniform pigments ----
     if (dome_on && nsurv == 1 && only < a.n_spheres) {
@@ -1076,8 +1138,6 @@ __global__ __launch_bounds__(PT_BLOCK) __attribute__((amdgpu_waves_per_eu(PT_TIL
     PT_T4(3);
     if (!done) {
       // ---- the four primary rays (imagetracer.py:48-58, camera.py:103-124) ----
-      V3 org, dir[4];
-      double bgx, bgy, bgz;
       {
         pt_kargs c = cold_args(a);
         const double dist = c->cam_dist, aspect = c->cam_aspect;
@@ -1109,8 +1169,6 @@ __global__ __launch_bounds__(PT_BLOCK) __attribute__((amdgpu_waves_per_eu(PT_TIL
       }
       PT_T4(4);
       // ---- World.ray_intersection over the survivors, four rays per visit ----
-      const double tmin = 1.0e-5;
-      Hit4 h4;
       bool fast = true;
 #pragma unroll
       for (int k = 0; k < NPX; ++k) {
@@ -1173,68 +1231,74 @@ __global__ __launch_bounds__(PT_BLOCK) __attribute__((amdgpu_waves_per_eu(PT_TIL
           }
         }
       }
-      PT_T4(5);
-      // ---- shade + store ----
+      shade = true;
+    }
+  }
+  // The one barrier of the kernel: every wave arrives here exactly once, whatever it did above.  __syncthreads() first lets
+  // each wave wait for the staging loads it issued itself, so behind it the whole image is in LDS for every wave.
+  if constexpr (SLDS) __syncthreads();
+  if (valid) PT_T4(5);  // (the wait at the barrier counts as query time; a wave without a tile reports no cycles, as before)
+  if (shade) {
+    // ---- shade + store ----
 #pragma unroll
-      for (int k = 0; k < NPX; ++k) {
-        V3 c = {bgx, bgy, bgz};
-        const int hit = h4.best[k];
-        if (RENDERER == PT_RENDERER_ONOFF) {  // render.py:52-53
-          if (hit >= 0) {
-            pt_kargs ca = cold_args(a);
-            c.x = ca->onoff[0];
-            c.y = ca->onoff[1];
-            c.z = ca->onoff[2];
-          }
-        } else if (hit >= 0) {  // render.py:65-74
-          Hit h;
-          h.u = 0.0;
-          h.v = 0.0;
-          Ray rk;
-          rk.o = org;
-          rk.d = dir[k];
-          rk.tmin = tmin;
-          V3 p1, p2;
-          // (a shape whose two pigments are uniform carries pigment + emitted, added at upload with the same fp64
-          //  addition, in pig_c2: pt_layout.h)
-          if constexpr (SLDS) {
-            const pt_lds_rec rec = (pt_lds_rec)(const void *)pt_lds_f64 + hit;
-            const pt_lds_aux ax = (pt_lds_aux)(const void *)(pt_lds_f64 + a.n_shapes * 16) + hit;
-            if (ax->needs_uv) {
-              hit_details(rec, ax, rk, h4.best_t[k], h, true);
-              p1 = brdf_pigment(a, ax, h.u, h.v);
-              p2 = emitted_pigment(a, ax, h.u, h.v);
-              c.x = p1.x + p2.x;
-              c.y = p1.y + p2.y;
-              c.z = p1.z + p2.z;
-            } else {
-              c.x = ax->pig_c2[0];
-              c.y = ax->pig_c2[1];
-              c.z = ax->pig_c2[2];
-            }
+    for (int k = 0; k < NPX; ++k) {
+      V3 c = {bgx, bgy, bgz};
+      const int hit = h4.best[k];
+      if (RENDERER == PT_RENDERER_ONOFF) {  // render.py:52-53
+        if (hit >= 0) {
+          pt_kargs ca = cold_args(a);
+          c.x = ca->onoff[0];
+          c.y = ca->onoff[1];
+          c.z = ca->onoff[2];
+        }
+      } else if (hit >= 0) {  // render.py:65-74
+        Hit h;
+        h.u = 0.0;
+        h.v = 0.0;
+        Ray rk;
+        rk.o = org;
+        rk.d = dir[k];
+        rk.tmin = tmin;
+        V3 p1, p2;
+        // (a shape whose two pigments are uniform carries pigment + emitted, added at upload with the same fp64
+        //  addition, in pig_c2: pt_layout.h)
+        if constexpr (SLDS) {
+          const pt_lds_rec rec = (pt_lds_rec)(const void *)pt_lds_f64 + hit;
+          const pt_lds_aux ax = (pt_lds_aux)(const void *)(pt_lds_f64 + a.n_shapes * 16) + hit;
+          if (ax->needs_uv) {
+            hit_details(rec, ax, rk, h4.best_t[k], h, true);
+            p1 = brdf_pigment(a, ax, h.u, h.v);
+            p2 = emitted_pigment(a, ax, h.u, h.v);
+            c.x = p1.x + p2.x;
+            c.y = p1.y + p2.y;
+            c.z = p1.z + p2.z;
           } else {
-            const PtShapeAux *ax = cold_args(a)->aux + hit;
-            if (ax->needs_uv) {
-              hit_details(a.recs + hit, ax, rk, h4.best_t[k], h, true);
-              p1 = brdf_pigment(a, ax, h.u, h.v);
-              p2 = emitted_pigment(a, ax, h.u, h.v);
-              c.x = p1.x + p2.x;
-              c.y = p1.y + p2.y;
-              c.z = p1.z + p2.z;
-            } else {
-              c.x = ax->pig_c2[0];
-              c.y = ax->pig_c2[1];
-              c.z = ax->pig_c2[2];
-            }
+            c.x = ax->pig_c2[0];
+            c.y = ax->pig_c2[1];
+            c.z = ax->pig_c2[2];
+          }
+        } else {
+          const PtShapeAux *ax = cold_args(a)->aux + hit;
+          if (ax->needs_uv) {
+            hit_details(a.recs + hit, ax, rk, h4.best_t[k], h, true);
+            p1 = brdf_pigment(a, ax, h.u, h.v);
+            p2 = emitted_pigment(a, ax, h.u, h.v);
+            c.x = p1.x + p2.x;
+            c.y = p1.y + p2.y;
+            c.z = p1.z + p2.z;
+          } else {
+            c.x = ax->pig_c2[0];
+            c.y = ax->pig_c2[1];
+            c.z = ax->pig_c2[2];
           }
         }
-        PT_T4(6);
-        if (act[k]) {
-          store_pixel(a, pix[k], c, out_f32);
-          nrays += 1ULL;
-        }
-        PT_T4(7);
       }
+      PT_T4(6);
+      if (act[k]) {
+        store_pixel(a, pix[k], c, out_f32);
+        nrays += 1ULL;
+      }
+      PT_T4(7);
     }
   }
 #ifdef PT_DEBUG_TIME

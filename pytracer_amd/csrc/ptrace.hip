@@ -751,9 +751,21 @@ static int launch(pt_scene *s, const pt_camera *cam, const pt_params *p, void *o
   } while (0)
     if (R == PT_RENDERER_ONOFF)
       PT_LAUNCH4(PT_RENDERER_ONOFF, false);
-    else if (pl.t4lds)
+    else if (pl.t4lds) {
+      // the staged variant copies recs[] and aux[] with 16-byte global -> LDS loads, in PT_TILE4_STAGE_ROUNDS unrolled rounds:
+      // both tables and the dynamic LDS block (it follows the kernel's static LDS) must be 16-byte aligned, the image must fit
+      static int static_lds = -1;  // (a property of the code: looked up once)
+      if (static_lds < 0) {
+        hipFuncAttributes fa;
+        HIP_TRY(hipFuncGetAttributes(&fa, (const void *)pt_tile4_kernel<PT_RENDERER_FLAT, true>));
+        static_lds = (int)fa.sharedSizeBytes;
+      }
+      if ((((uintptr_t)a.recs | (uintptr_t)a.aux) & 15) != 0 || (static_lds & 15) != 0)
+        return fail(PT_ERR_INVALID, "internal: pt_tile4_kernel<FLAT, LDS> needs 16-byte aligned shape tables and LDS");
+      if (pl.lds_main > (size_t)PT_TILE4_STAGE_ROUNDS * (PT_BLOCK / 64) * 1024)
+        return fail(PT_ERR_INVALID, "internal: scene image exceeds pt_tile4_kernel's staging copy");
       PT_LAUNCH4(PT_RENDERER_FLAT, true);
-    else
+    } else
       PT_LAUNCH4(PT_RENDERER_FLAT, false);
 #undef PT_LAUNCH4
   } else if (pl.tile || pl.path_tiled) {

@@ -52,7 +52,13 @@ TABLE = [  # (regex on the mnemonic, class, cycles or (low, high), rocprofv3 cla
     (r"v_cmp[x]?_\w+_(f64|f32|f16|i64|u64|i16|u16)", "cmp", 4, None),
     (r"v_cndmask_b32", "cndmask", 4, None),
     (r"v_(readlane|readfirstlane|writelane)_b32|v_mbcnt_(lo|hi)_u32_b32", "lane", 4, None),
-    (r"v_pk_(mul|add|fma)_f32", "pk_f32", 4, None),
+    # (packed fp32 lands in the fp32 class counters, once per instruction: calibrated on two builds of pt_tile4_kernel<FLAT, LDS>
+    #  with their own counters -- the one with the staging loops and the one with the asynchronous copy: with packed fp32 in no
+    #  class the second one's programme is infeasible under SQ_INSTS_VALU_TRANS_F32, with this mapping both are feasible under
+    #  all fifteen counters; ADD_F32 also stayed 172 960 per launch when three v_pk_add_f32 of the cone became v_add_f32)
+    (r"v_pk_add_f32", "pk_f32", 4, "SQ_INSTS_VALU_ADD_F32"),
+    (r"v_pk_mul_f32", "pk_f32", 4, "SQ_INSTS_VALU_MUL_F32"),
+    (r"v_pk_fma_f32", "pk_f32", 4, "SQ_INSTS_VALU_FMA_F32"),
     (r"v_pk_mov_b32", "mov", (2, 4), None),
     (r"v_(add|sub|subrev)_f32", "add_f32", 2, "SQ_INSTS_VALU_ADD_F32"),
     (r"v_mul_f32|v_mul_legacy_f32", "mul_f32", 2, "SQ_INSTS_VALU_MUL_F32"),
