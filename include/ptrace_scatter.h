@@ -31,7 +31,10 @@
  *     state, inc   n uint64 each: the record's generator (PCG-XSH-RR 64/32, pcg.py: `state` and `inc` as the class keeps them)
  * uv is ALWAYS required (a scene whose pigments are all uniform would not read it, but the library does not ask the scene).
  * A record is the caller's: nothing about it is assumed (non-finite values give the reference's non-finite results; an image
- * pigment's column and row are clamped into the texture, NaN to 0, as in ptrace_surface.h).
+ * pigment's column and row are clamped into the texture, NaN to 0, as in ptrace_surface.h; a checkered pigment whose
+ * u * steps or v * steps is not finite -- the reference raises -- answers one of its two colours by that header's definition:
+ * a NaN cell counts as odd, an infinite one as even).  The generator's words are the caller's too: every value of state and
+ * inc is legal input, an even inc included.
  *
  * Output: one buffer of pt_rays_scatter_bytes(n, channels) bytes, planar, n values per plane:
  *     status  n int32, padded to a multiple of 8 bytes:  -1 no hit (the caller's value: its background)

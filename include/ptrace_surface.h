@@ -24,7 +24,11 @@
  *     point   3 planes  HitRecord.world_point            normal  3 planes  HitRecord.normal
  *     uv      2 planes  HitRecord.surface_point          dir     3 planes  the direction of the ray that was traced
  * A record is the caller's: nothing about it is assumed (non-finite values give the reference's non-finite results; an image
- * pigment's column and row are clamped into the texture, NaN to 0).
+ * pigment's column and row are clamped into the texture, NaN to 0).  One case the reference does not define -- it raises: a
+ * checkered pigment whose u * steps (v * steps) is not finite.  The library's definition: such a cell counts as ODD where the
+ * product is NaN and as EVEN where it is +-inf, so the answer is one of the pigment's two colours, never anything else (NaN
+ * against a finite even cell: color2; NaN against NaN, +inf against -inf: color1).  Finite products of any size, negative ones
+ * included, take the parity of Python's exact int(floor(.)) % 2.  tests/test_gpu_hostile_records.py pins all of this.
  *
  * Slot table.  The scene's records are grouped spheres-first; the shape plane holds World.shapes indices.  The table maps an
  * index to its record and is the caller's to keep: make it once per scene handle, it stays valid as long as the handle.

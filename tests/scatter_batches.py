@@ -96,9 +96,12 @@ def state_drawing_one() -> int:
     return old
 
 
-def expected(orc, flat, rec, dirs, pcg, roulette: bool) -> dict:
+def expected(orc, flat, rec, dirs, pcg, roulette: bool, pigment=None) -> dict:
     """render.py:107-134 for one child of every record, through the oracle -> the planes a scatter batch holds:
-    {"status" [n] int32, "rays" [8, n], "pcg" [2, n] uint64, "weight" [n, 3], "emitted" [n, 3], "kind" [n] (BRDF kind, -1: no hit)}."""
+    {"status" [n] int32, "rays" [8, n], "pcg" [2, n] uint64, "weight" [n, 3], "emitted" [n, 3], "kind" [n] (BRDF kind, -1: no hit)}.
+    ``pigment``: the look-up ``(flat, shape, emitted, u, v) -> [3]`` (default: ``orc.pigment``; tests/hostile_records.py passes its
+    own, which is defined for a (u, v) the oracle's integer casts are not)."""
+    pigment = orc.pigment if pigment is None else pigment
     n = rec.n
     status, kind = np.full(n, -1, np.int32), np.full(n, -1, np.int32)
     rays = np.tile(DEAD_RAY[:, None], (1, n))
@@ -109,7 +112,7 @@ def expected(orc, flat, rec, dirs, pcg, roulette: bool) -> dict:
     for i in np.flatnonzero(rec.hit):
         s = int(rec.shape_index[i])
         u, v = float(uv[i, 0]), float(uv[i, 1])
-        hc, em = orc.pigment(flat, s, False, u, v), orc.pigment(flat, s, True, u, v)
+        hc, em = pigment(flat, s, False, u, v), pigment(flat, s, True, u, v)
         lum = max(max(float(hc[0]), float(hc[1])), float(hc[2]))
         g = orc.Pcg()
         g.st[0], g.st[1] = int(gen[0, i]), int(gen[1, i])
