@@ -1,4 +1,5 @@
-"""Build recipe for libptrace.so and its add-ons libptrace_rays.so, libptrace_surface.so and libptrace_scatter.so (HIP, gfx950 only).
+"""Build recipe for libptrace.so and its add-ons libptrace_rays.so, libptrace_surface.so, libptrace_scatter.so and
+libptrace_radiance.so (HIP, gfx950 only).
 
 ``hipcc --offload-arch=gfx950 -O3 -ffp-contract=off``: the parity kernels must not fuse a*b+c (the
 reference is Python: every operation rounds), and nothing enables fast-math.  The library is built
@@ -13,6 +14,9 @@ records) is the third, for the same reason once more: the exported symbols of li
 
 ``libptrace_scatter.so`` (csrc/ptrace_scatter.hip, include/ptrace_scatter.h: BRDF.scatter_ray and the Russian roulette for hit
 records) is the fourth: the exported symbols of libptrace_surface.so are pinned to its eleven as well.
+
+``libptrace_radiance.so`` (csrc/ptrace_radiance.hip, include/ptrace_radiance.h: the whole ``PathTracer`` recursion for ray
+batches) is the fifth: the exported symbols of libptrace_scatter.so are pinned to its seven.
 """
 from __future__ import annotations
 
@@ -31,12 +35,15 @@ SURFACE_LIB = os.path.join(HERE, "libptrace_surface.so")
 SURFACE_SOURCES = ["ptrace_surface.hip"]
 SCATTER_LIB = os.path.join(HERE, "libptrace_scatter.so")
 SCATTER_SOURCES = ["ptrace_scatter.hip"]
+RADIANCE_LIB = os.path.join(HERE, "libptrace_radiance.so")
+RADIANCE_SOURCES = ["ptrace_radiance.hip"]
 # every file the one translation unit includes: all of csrc/ (tests/test_host.py checks this list against the #include lines)
 DEPS = sorted(f for f in os.listdir(CSRC) if f.endswith((".hip", ".h"))) + [os.path.join("..", "..", "include", "ptrace.h"),
                                                                             os.path.join("..", "..", "include", "ptrace_debug.h"),
                                                                             os.path.join("..", "..", "include", "ptrace_rays.h"),
                                                                             os.path.join("..", "..", "include", "ptrace_surface.h"),
-                                                                            os.path.join("..", "..", "include", "ptrace_scatter.h")]
+                                                                            os.path.join("..", "..", "include", "ptrace_scatter.h"),
+                                                                            os.path.join("..", "..", "include", "ptrace_radiance.h")]
 FLAGS = ["--offload-arch=gfx950", "-O3", "-ffp-contract=off", "-fno-fast-math", "-std=c++17", "-fPIC",
          "-shared", "-Wall", "-Wno-unused-function", "-Wno-pass-failed",
          # a fixed compilation-unit id: by default clang derives it from the command line (paths included), which would make
@@ -45,6 +52,10 @@ FLAGS = ["--offload-arch=gfx950", "-O3", "-ffp-contract=off", "-fno-fast-math", 
 RAYS_FLAGS = FLAGS[:-1] + ["-cuid=libptrace_rays"]
 SURFACE_FLAGS = FLAGS[:-1] + ["-cuid=libptrace_surface"]
 SCATTER_FLAGS = FLAGS[:-1] + ["-cuid=libptrace_scatter"]
+RADIANCE_FLAGS = FLAGS[:-1] + ["-cuid=libptrace_radiance"]
+# every library the recipe makes, in build order: what build() and needs_build() walk
+TARGETS = ((FLAGS, LIB, SOURCES), (RAYS_FLAGS, RAYS_LIB, RAYS_SOURCES), (SURFACE_FLAGS, SURFACE_LIB, SURFACE_SOURCES),
+           (SCATTER_FLAGS, SCATTER_LIB, SCATTER_SOURCES), (RADIANCE_FLAGS, RADIANCE_LIB, RADIANCE_SOURCES))
 
 
 def code_hash(lib: str = LIB) -> str:
@@ -83,18 +94,17 @@ def _hipcc() -> str:
 
 
 def needs_build() -> bool:
-    libs = (LIB, RAYS_LIB, SURFACE_LIB, SCATTER_LIB)
+    libs = [lib for _, lib, _ in TARGETS]
     if not all(os.path.exists(lib) for lib in libs):
         return True
-    t = min(os.path.getmtime(lib) for lib in libs)  # (one list of files for all four: they share the headers)
+    t = min(os.path.getmtime(lib) for lib in libs)  # (one list of files for all five: they share the headers)
     return any(os.path.getmtime(os.path.join(CSRC, d)) > t for d in DEPS)
 
 
 def build(force: bool = False, verbose: bool = False) -> str:
     if not force and not needs_build():
         return LIB
-    for flags, lib, sources in ((FLAGS, LIB, SOURCES), (RAYS_FLAGS, RAYS_LIB, RAYS_SOURCES), (SURFACE_FLAGS, SURFACE_LIB, SURFACE_SOURCES),
-                                (SCATTER_FLAGS, SCATTER_LIB, SCATTER_SOURCES)):
+    for flags, lib, sources in TARGETS:
         cmd = [_hipcc()] + flags + ["-o", lib] + [os.path.join(CSRC, s) for s in sources]
         if verbose:
             print(" ".join(cmd), file=sys.stderr)

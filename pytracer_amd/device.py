@@ -388,6 +388,79 @@ class DeviceScene:
                                              buf.ctypes.data_as(C.c_void_p), buf.nbytes))
         return rb.ScatteredRays(buf, n, bits)
 
+    # -- the whole recursion (include/ptrace_radiance.h, libptrace_radiance.so): PathTracer.__call__ per ray, a generator per ray ---
+    def radiance_workspace_bytes(self, n: int, num_of_rays: int = 1, max_depth: int = 10, depth: int = 0) -> int:
+        """Bytes of the node-stack workspace ``radiance(device=True)`` needs for ``n`` rays (``pt_rays_radiance_workspace_bytes``:
+        sized by the lanes a launch keeps resident, not by ``n``)."""
+        from . import _radiance_lib
+
+        need = int(_radiance_lib.lib().pt_rays_radiance_workspace_bytes(self.device, int(n), int(num_of_rays), int(max_depth), int(depth)))
+        if need == 0:
+            raise ValueError(f"no workspace size for these arguments: {_radiance_lib.last_error()}")
+        return need
+
+    def radiance(self, rays, pcg, num_of_rays: int = 1, max_depth: int = 10, russian_roulette_limit: int = 3,
+                 background=(0.0, 0.0, 0.0), depth: int = 0, channels="all", device: bool = False, stream=None, out=None,
+                 workspace=None, n=None):
+        """``PathTracer(world, background, pcg_i, num_of_rays, max_depth, russian_roulette_limit)(ray_i)`` (render.py:99-139) for
+        every ray of the ``[8, n]`` block of :func:`pytracer_amd.rays.ray_planes`, with ``Ray.depth = depth`` and ``pcg``
+        (``uint64[2, n]``: state and increment per ray, :func:`pytracer_amd.rays.pcg_streams`) its generator: each ray is walked
+        depth-first on the device, in the reference's order of draws.  ``channels``: ``"pcg"``, ``"count"``, ``"all"``, ``"none"``
+        or ``PT_RAD_*`` bits -> :class:`pytracer_amd.rays.RayRadiance`.  ``device=True``: ``rays`` is a ``DeviceBuffer`` or device
+        tensor holding that block (or a raw address, then with ``n=``), ``pcg`` a buffer of ``[2, n]`` uint64 or a pair of plane
+        addresses; the batch is enqueued on ``stream`` with the node stacks in ``workspace`` (:meth:`radiance_workspace_bytes`
+        bytes of device memory; ``None``: a new buffer) -> the output ``DeviceBuffer`` (``out``, or a new one)."""
+        from . import _radiance_lib, rays as rb
+
+        L, block, bits = _radiance_lib.lib(), self.kernel_args(), rb.radiance_channels(channels)
+        par = _radiance_lib.params(num_of_rays, max_depth, russian_roulette_limit, depth, background)
+        if device:
+            from .devmem import DeviceBuffer
+
+            handle = getattr(stream, "handle", stream)
+            if n is None:
+                if not hasattr(rays, "nbytes"):
+                    raise ValueError("n= is needed when the rays are a raw device address")
+                n = int(rays.nbytes) // 64
+            n = int(n)
+            if isinstance(pcg, (tuple, list)):
+                state, inc = pcg
+            else:
+                base = int(self._plane_ptr(pcg, "pcg").value or 0)
+                state, inc = base, base + 8 * n
+            if out is None:
+                out = DeviceBuffer((max(rb.radiance_bytes(n, bits), 8),), np.uint8, self.device)
+            if workspace is None and n > 0:
+                # (0: arguments the library refuses -- the call below then says which, with its own error code)
+                need = int(L.pt_rays_radiance_workspace_bytes(self.device, n, par.num_of_rays, par.max_depth, par.depth0))
+                if need:
+                    workspace = DeviceBuffer((need,), np.uint8, self.device)
+                    out._radiance_workspace = workspace  # in flight on `stream` as long as the output is: freed with it
+            ptr = self._plane_ptr
+            _radiance_lib.check(L.pt_rays_radiance_device(self.device, block, len(block), None, ptr(rays, "rays"), ptr(state, "pcg state"),
+                                                          ptr(inc, "pcg inc"), n, C.byref(par), bits, ptr(workspace, "workspace"),
+                                                          int(workspace.nbytes) if workspace is not None else 0, ptr(out, "out"),
+                                                          int(out.nbytes), C.c_void_p(handle) if handle else None))
+            if hasattr(out, "rendered_on"):
+                out.rendered_on(stream)
+            if hasattr(workspace, "rendered_on"):
+                workspace.rendered_on(stream)
+            return out
+        if stream is not None or out is not None or n is not None or workspace is not None:
+            raise ValueError("stream=, out=, workspace= and n= go with device=True (host batches are staged and synchronous)")
+        rays = np.ascontiguousarray(rays, dtype=np.float64)
+        if rays.ndim != 2 or rays.shape[0] != 8:
+            raise ValueError(f"rays must be the [8, n] block of pytracer_amd.rays.ray_planes, not {rays.shape}")
+        n = rays.shape[1]
+        gen = np.ascontiguousarray(pcg, dtype=np.uint64)
+        if gen.shape != (2, n):
+            raise ValueError(f"pcg must be uint64[2, {n}] (state and increment per ray: pytracer_amd.rays.pcg_streams), not {gen.shape}")
+        buf = np.empty(rb.radiance_bytes(n, bits), dtype=np.uint8)
+        _radiance_lib.check(L.pt_rays_radiance(self.device, block, len(block), rays.ctypes.data_as(C.c_void_p),
+                                               gen[0].ctypes.data_as(C.c_void_p), gen[1].ctypes.data_as(C.c_void_p), n, C.byref(par), bits,
+                                               buf.ctypes.data_as(C.c_void_p), buf.nbytes))
+        return rb.RayRadiance(buf, n, bits)
+
     def cull_probe(self, cam: abi.Camera, width: int, height: int, x0: int, x1: int, row0: int, row1: int,
                    pixel=None) -> np.ndarray:
         """Diagnostics: which shapes (by ``World.shapes`` index) the conservative cull of the primary rays through

@@ -14,6 +14,10 @@ carried from bounce to bounce -- goes through ``DeviceScene.scatter`` (include/p
 ``WorldQueries.scatter``: :class:`ScatteredRays` views the answer, whose ray block goes straight back into ``trace_rays``.
 :func:`pcg_streams` makes the generators.
 
+Its fifth -- the whole recursion: ``PathTracer(world, background, pcg_i, ...)(ray_i)`` for every ray of a batch, walked
+depth-first on the device -- goes through ``DeviceScene.radiance`` (include/ptrace_radiance.h, libptrace_radiance.so) or
+``WorldQueries.path_radiance``: :class:`RayRadiance` views the answer.
+
 Layout: planar.  A batch is ``[8, n]`` float64 -- origin xyz, direction xyz, tmin, tmax, the fields of ``Ray`` (ray.py:29-50);
 a result is one buffer, the int32 shape plane first (padded to 8 bytes), then the selected fp64 planes of ``n`` values each.
 """
@@ -37,6 +41,10 @@ SCAT_WEIGHT, SCAT_EMITTED, SCAT_ALL = 1, 2, 3  # PT_SCAT_* of include/ptrace_sca
 SCAT_RAYS, SCAT_PCG = 4, 8  # plane selectors of scatter_plane_offset (always written: not channel bits)
 _SCAT_OF = {"weight": SCAT_WEIGHT, "emitted": SCAT_EMITTED}
 _PCG_MULT = 6364136223846793005
+
+
+RAD_PCG, RAD_COUNT, RAD_ALL = 1, 2, 3  # PT_RAD_* of include/ptrace_radiance.h
+_RAD_OF = {"pcg": RAD_PCG, "count": RAD_COUNT}
 
 
 def ray_channels(channels) -> int:
@@ -363,6 +371,102 @@ class ScatteredRays:
         return out
 
 
+def radiance_channels(channels) -> int:
+    """``PT_RAD_*`` bits from an int, names (``"pcg"``, ``"pcg,count"``), ``"all"`` or ``"none"``."""
+    if isinstance(channels, str):
+        names = [x.strip().lower() for x in channels.split(",") if x.strip()]
+        if names == ["all"]:
+            return RAD_ALL
+        if names == ["none"]:
+            return 0
+        unknown = [x for x in names if x not in _RAD_OF]
+        if unknown:
+            raise ValueError(f"a radiance batch has the channels pcg, count; not {', '.join(unknown)}")
+        return sum({_RAD_OF[x] for x in names})
+    bits = int(channels)
+    if bits < 0 or bits & ~RAD_ALL:
+        raise ValueError(f"a radiance batch has the channels pcg (1), count (2); not {bits:#x}")
+    return bits
+
+
+def radiance_bytes(n: int, channels: int) -> int:
+    """Mirror of ``pt_rays_radiance_bytes``: 0 for arguments the library refuses."""
+    if not (0 <= n <= MAX_RAYS and 0 <= channels <= RAD_ALL):
+        return 0
+    return n * 8 * (3 + (2 if channels & RAD_PCG else 0) + (1 if channels & RAD_COUNT else 0))
+
+
+def radiance_plane_offset(n: int, channels: int, channel: int, component: int = 0) -> int:
+    """Mirror of ``pt_rays_radiance_plane_offset`` (bytes; ``channel`` 0: the three radiance planes, ``RAD_PCG``: state and
+    increment, ``RAD_COUNT``; < 0: not selected)."""
+    if not (0 <= n <= MAX_RAYS and 0 <= channels <= RAD_ALL) or component < 0:
+        return -1
+    if channel == 0:
+        return n * 8 * component if component < 3 else -1
+    if channel == RAD_PCG and channels & RAD_PCG:
+        return n * 8 * (3 + component) if component < 2 else -1
+    if channel == RAD_COUNT and channels & RAD_COUNT:
+        return n * 8 * (3 + (2 if channels & RAD_PCG else 0)) if component < 1 else -1
+    return -1
+
+
+class RayRadiance:
+    """Views over the buffer of a radiance batch (``buf``: ``pt_rays_radiance_bytes`` bytes, contiguous ``uint8``).  Nothing
+    here copies.  ``radiance``: ``PathTracer(...)(ray)`` per ray with the component as last axis; ``pcg`` (``[2, n]``),
+    ``pcg_state`` / ``pcg_inc``: every ray's generator behind its draws; ``n_rays``: the rays handed to a world query for it
+    (``uint64``).  ``shape``: what the rays' axis is viewed as (a frame's ``[nsamp, rows, W]``); default ``[n]``."""
+
+    def __init__(self, buf, n: int, channels=RAD_ALL, shape=None):
+        self.channels = radiance_channels(channels)
+        self.n = int(n)
+        self.shape = (self.n,) if shape is None else tuple(int(x) for x in shape)
+        if int(np.prod(self.shape, dtype=np.int64)) != self.n:
+            raise ValueError(f"shape {self.shape} does not hold {self.n} rays")
+        self.nbytes = radiance_bytes(self.n, self.channels)
+        buf = np.asarray(buf)
+        if buf.dtype != np.uint8 or buf.ndim != 1:
+            buf = buf.reshape(-1).view(np.uint8)
+        if buf.nbytes < self.nbytes:
+            raise ValueError(f"radiance buffer too small: {buf.nbytes} < {self.nbytes} bytes")
+        self.buffer = buf
+        self.radiance = np.moveaxis(buf[: self.n * 24].view(np.float64).reshape((3,) + self.shape), 0, -1)
+
+    def _words(self, channel: int, count: int) -> np.ndarray:
+        if not self.channels & channel:
+            name = next(k for k, v in _RAD_OF.items() if v == channel)
+            raise KeyError(f"channel {name!r} was not selected for this radiance batch (channels = {self.channels:#x})")
+        off = radiance_plane_offset(self.n, self.channels, channel, 0)
+        return self.buffer[off: off + self.n * 8 * count].view(np.uint64).reshape(count, self.n)
+
+    def has(self, name: str) -> bool:
+        return bool(self.channels & _RAD_OF[name])
+
+    @property
+    def pcg(self) -> np.ndarray:
+        return self._words(RAD_PCG, 2)
+
+    @property
+    def pcg_state(self) -> np.ndarray:
+        return self.pcg[0].reshape(self.shape)
+
+    @property
+    def pcg_inc(self) -> np.ndarray:
+        return self.pcg[1].reshape(self.shape)
+
+    @property
+    def n_rays(self) -> np.ndarray:
+        return self._words(RAD_COUNT, 1)[0].reshape(self.shape)
+
+    def planes(self) -> dict:
+        """name -> view, for every selected channel (what the ``radiance`` command writes into its ``.npz``)."""
+        out = {"radiance": self.radiance}
+        if self.has("pcg"):
+            out["pcg_state"], out["pcg_inc"] = self.pcg_state, self.pcg_inc
+        if self.has("count"):
+            out["n_rays"] = self.n_rays
+        return out
+
+
 def pcg_streams(init_state, init_seqs, skip: int = 0) -> np.ndarray:
     """``uint64[2, n]``: state and increment of ``PCG(init_state, seq)`` (pcg.py:25-41; csrc/pt_math.h: pcg_seed) for every
     ``seq`` of ``init_seqs``, ``skip`` draws in -- the generators a scatter batch carries.  Every value of the 64-bit range is
@@ -446,3 +550,12 @@ class WorldQueries:
         bits = scatter_channels(channels)
         out = self.scene.scatter(hits.shape_index, hits.point, hits.normal, hits.uv, dirs, pcg, roulette, bits)
         return ScatteredRays(out.buffer, out.n, bits, shape=hits.shape_index.shape)
+
+    def path_radiance(self, rays, pcg, dirs=None, num_of_rays: int = 1, max_depth: int = 10, russian_roulette_limit: int = 3,
+                      background=(0.0, 0.0, 0.0), depth: int = 0, channels=RAD_ALL, tmin=1e-5, tmax=float("inf")) -> RayRadiance:
+        """``PathTracer(world, background, pcg_i, num_of_rays, max_depth, russian_roulette_limit)(ray_i)`` (render.py:99-139;
+        the defaults are ``PathTracer``'s) for ``[n, 8]`` rays (or ``[n, 3]`` origins and ``dirs``) with ``Ray.depth = depth``,
+        each drawing from its own generator (``pcg``: ``uint64[2, n]``, :func:`pcg_streams`), walked depth-first on the
+        device -> :class:`RayRadiance`."""
+        return self.scene.radiance(ray_planes(rays, dirs, tmin, tmax), pcg, num_of_rays, max_depth, russian_roulette_limit, background,
+                                   depth, channels)

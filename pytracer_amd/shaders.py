@@ -1,4 +1,4 @@
-"""Four worked hit shaders: renderers of a user's own that get the GPU for their tracing half.
+"""Five worked hit shaders: renderers of a user's own that get the GPU for their tracing half.
 
 A *hit shader* is any object with a ``world`` attribute and a method ``shade_hits(frame) -> [nsamp, H, W, 3]``:
 ``GpuImageTracer.fire_all_rays(shader)`` renders the hit-record frame of its camera on the device
@@ -18,6 +18,9 @@ the device), with nothing but arrays in between.
 trace, then per depth scatter (``WorldQueries.scatter``: pigments, Russian roulette and ``brdf.scatter_ray`` on the device, every
 sample's generator carried along) and trace again (``WorldQueries.ray_intersections`` on the scattered block), and at the end
 the recursion's sums in numpy.
+
+:class:`PathRadianceShader` is ``PathTracer`` with any number of rays per hit: the frame's primary rays go to one radiance
+query (``WorldQueries.path_radiance``), which walks every sample's tree depth-first on the device.
 """
 from __future__ import annotations
 
@@ -187,6 +190,35 @@ class PointLightShader(_HitShader):
         return Color(r, g, b)
 
 
+def sample_streams(pcg, frame) -> np.ndarray:
+    """``uint64[2, n]``: the generator of every sample of ``frame`` where its path starts -- sample ``k`` of pixel
+    ``i = row * W + col`` owns ``PCG(S0, Q0 + i * S**2 + k)`` with (S0, Q0) the seeds of ``pcg``, entered behind the sample's two
+    jitter draws when ``samples_per_side > 0`` (the fused path tracer's ``pcg_mode="sample"``)."""
+    from . import flatten
+    from .rays import pcg_streams
+
+    s0, q0 = flatten.recover_seeds(pcg, True)
+    p = frame.params
+    grow = np.asarray(abi.rows_for_rank(p.height, p.row_block, p.n_ranks, p.rank), dtype=np.uint64)
+    with np.errstate(over="ignore"):
+        pix = grow[:, None] * np.uint64(frame.width) + np.arange(frame.width, dtype=np.uint64)[None, :]
+        seq = np.uint64(q0 & (2 ** 64 - 1)) + pix[None] * np.uint64(frame.nsamp) + np.arange(frame.nsamp, dtype=np.uint64)[:, None, None]
+    return pcg_streams(s0, seq.reshape(-1), 2 if frame.samples_per_side > 0 else 0)
+
+
+def _check_sample_streams(shader_name: str, tracer, alternative: str) -> None:
+    """The ``pcg_mode`` combinations without a generator per sample, refused in ``PathTracerShader``'s words."""
+    if tracer is None:
+        return
+    mode, S = getattr(tracer, "pcg_mode", "sample"), int(getattr(tracer, "samples_per_side", 0))
+    if mode == "seq" or (mode == "auto" and S > 0):  # ("auto" jitters a hit-record frame from the serial stream)
+        raise ValueError(f'{shader_name} needs a generator per sample, not pcg_mode="{mode}" (one serial stream for the whole '
+                         f'frame): build the tracer with pcg_mode="sample", or {alternative}')
+    if mode == "pixel" and S > 1:
+        raise ValueError(f'{shader_name} needs a generator per sample, not pcg_mode="pixel" with {S * S} samples (a pixel\'s samples '
+                         f'share one stream in program order): build the tracer with pcg_mode="sample", or {alternative}')
+
+
 class PathTracerShader(_HitShader):
     """``PathTracer`` (render.py:99-139) with ``num_of_rays=1`` as a hit shader, breadth-first: all samples of the frame take
     their first bounce together, then their second, ... down to ``max_depth``; then the recursion unwinds in numpy with the
@@ -224,16 +256,7 @@ class PathTracerShader(_HitShader):
         self._check_tracer()
 
     def _check_tracer(self) -> None:
-        tracer = self.tracer
-        if tracer is None:
-            return
-        mode, S = getattr(tracer, "pcg_mode", "sample"), int(getattr(tracer, "samples_per_side", 0))
-        if mode == "seq" or (mode == "auto" and S > 0):  # ("auto" jitters a hit-record frame from the serial stream)
-            raise ValueError(f'PathTracerShader needs a generator per sample, not pcg_mode="{mode}" (one serial stream for the whole '
-                             f'frame): build the tracer with pcg_mode="sample", or {self._ALTERNATIVE}')
-        if mode == "pixel" and S > 1:
-            raise ValueError(f'PathTracerShader needs a generator per sample, not pcg_mode="pixel" with {S * S} samples (a pixel\'s samples '
-                             f'share one stream in program order): build the tracer with pcg_mode="sample", or {self._ALTERNATIVE}')
+        _check_sample_streams("PathTracerShader", self.tracer, self._ALTERNATIVE)
 
     def _queries(self):
         if self.tracer is None:
@@ -242,16 +265,7 @@ class PathTracerShader(_HitShader):
 
     def sample_streams(self, frame) -> np.ndarray:
         """``uint64[2, n]``: the generator of every sample of ``frame`` where its path starts (behind the two jitter draws)."""
-        from . import flatten
-        from .rays import pcg_streams
-
-        s0, q0 = flatten.recover_seeds(self.pcg, True)
-        p = frame.params
-        grow = np.asarray(abi.rows_for_rank(p.height, p.row_block, p.n_ranks, p.rank), dtype=np.uint64)
-        with np.errstate(over="ignore"):
-            pix = grow[:, None] * np.uint64(frame.width) + np.arange(frame.width, dtype=np.uint64)[None, :]
-            seq = np.uint64(q0 & (2 ** 64 - 1)) + pix[None] * np.uint64(frame.nsamp) + np.arange(frame.nsamp, dtype=np.uint64)[:, None, None]
-        return pcg_streams(s0, seq.reshape(-1), 2 if frame.samples_per_side > 0 else 0)
+        return sample_streams(self.pcg, frame)
 
     def shade_hits(self, frame) -> np.ndarray:
         from .rays import SCAT_ALL
@@ -315,6 +329,89 @@ class PathTracerShader(_HitShader):
             o, nd, tmin = scatter_ray(material.brdf, self.pcg, (d.x, d.y, d.z), (wp.x, wp.y, wp.z), (nrm.x, nrm.y, nrm.z))
             child = self._radiance(HitRay(Vec(*o), Vec(*nd), tmin, float("inf"), depth + 1), depth + 1)
             cr, cg, cb = cr + r * child.r, cg + g * child.g, cb + b * child.b
+        k = 1.0 / self.num_of_rays
+        return Color(em.r + cr * k, em.g + cg * k, em.b + cb * k)
+
+
+class PathRadianceShader(_HitShader):
+    """``PathTracer`` (render.py:99-139) with ANY ``num_of_rays >= 1`` as a hit shader, depth-first on the device:
+    ``shade_hits(frame)`` hands the frame's own primary rays (``ray_origin``, ``ray_dir``, ``tmin = 1e-5``, ``tmax = inf``) to
+    ``WorldQueries.path_radiance`` (include/ptrace_radiance.h), every sample with the generator :func:`sample_streams` gives it
+    -- the streams of :class:`PathTracerShader` and of the fused path tracer's ``pcg_mode="sample"``.  So, handed to a
+    ``GpuImageTracer(..., pcg=PCG(S0, Q0), pcg_mode="sample")``, the frame is the one ``fire_all_rays(PathTracer(world,
+    background_color, PCG(S0, Q0), num_of_rays, max_depth, limit))`` renders.
+
+    The radiance query RE-TRACES the primary ray: of the hit-record frame only the rays are read (``hit_channels`` asks for
+    nothing else), and the first hit is found a second time inside the walk.  Starting the walk from the records is a follow-up.
+
+    A tracer with ``pcg_mode="seq"``, or ``pcg_mode="pixel"`` with more than one sample, is refused as by
+    :class:`PathTracerShader`.  ``__call__(ray)`` is the same recursion in Python floats, drawing from ``pcg`` itself, on a
+    world that can intersect."""
+
+    hit_channels = abi.HIT_RAY
+    _ALTERNATIVE = PathTracerShader._ALTERNATIVE
+
+    def __init__(self, world, tracer=None, background_color: Color = BLACK, pcg=None, num_of_rays: int = 1, max_depth: int = 10,
+                 russian_roulette_limit: int = 3):
+        super().__init__(world, background_color)
+        from .hostmodel import PCG
+
+        if int(num_of_rays) < 1:
+            raise ValueError(f"PathRadianceShader needs num_of_rays >= 1, not {num_of_rays}")
+        if int(max_depth) < 0:
+            raise ValueError(f"PathRadianceShader needs max_depth >= 0, not {max_depth}")
+        self.tracer = tracer
+        self.pcg = pcg if pcg is not None else PCG()
+        self.num_of_rays, self.max_depth, self.russian_roulette_limit = int(num_of_rays), int(max_depth), int(russian_roulette_limit)
+        self.last_radiance = None  # the RayRadiance of the last shade_hits (its n_rays plane: the rays the walk traced)
+        _check_sample_streams("PathRadianceShader", tracer, self._ALTERNATIVE)
+
+    def shade_hits(self, frame) -> np.ndarray:
+        _check_sample_streams("PathRadianceShader", self.tracer, self._ALTERNATIVE)
+        if self.tracer is None:
+            raise TypeError("PathRadianceShader.shade_hits needs the tracer whose device scene holds the world: PathRadianceShader(world, tracer, ...)")
+        q = self.tracer.world_queries(self.world)
+        shape3 = frame.shape_index.shape
+        res = q.path_radiance(np.asarray(frame.ray_origin).reshape(-1, 3), sample_streams(self.pcg, frame), np.asarray(frame.ray_dir).reshape(-1, 3),
+                              self.num_of_rays, self.max_depth, self.russian_roulette_limit, self.background_color, 0, "all", 1e-5, float("inf"))
+        self.last_radiance = res
+        return np.asarray(res.radiance).reshape(shape3 + (3,))
+
+    # -- ray by ray ---------------------------------------------------------------------------------------------------------
+    def __call__(self, ray) -> Color:
+        if not callable(getattr(self.world, "ray_intersection", None)):
+            raise TypeError(f"{type(self.world).__name__} has no ray_intersection(ray): it is a parameter holder that cannot trace a ray.  "
+                            "Hand PathRadianceShader to GpuImageTracer.fire_all_rays (the device traces), or give it a pytracer World")
+        return self._radiance(ray, int(getattr(ray, "depth", 0)))
+
+    def _radiance(self, ray, depth: int) -> Color:
+        from .hits import HitRay
+        from .hostmodel import Vec
+
+        if depth > self.max_depth:
+            return Color(0.0, 0.0, 0.0)
+        record = self.world.ray_intersection(ray)
+        if record is None:
+            return self.background_color
+        material = getattr(record, "material", None) or self.world.shapes[record.shape_index].material
+        uv, wp, nrm = record.surface_point, record.world_point, record.normal
+        hc, em = pigment_color(material.brdf.pigment, uv), pigment_color(material.emitted_radiance, uv)
+        r, g, b = hc.r, hc.g, hc.b
+        lum = max(max(r, g), b)
+        if depth >= self.russian_roulette_limit:  # render.py:116-123
+            q = max(0.05, 1 - lum)
+            if self.pcg.random_float() > q:
+                f = 1.0 / (1.0 - q)
+                r, g, b = r * f, g * f, b * f
+            else:
+                return em
+        cr = cg = cb = 0.0
+        if lum > 0.0:
+            d = ray.dir
+            for _ in range(self.num_of_rays):  # render.py:126-137
+                o, nd, tmin = scatter_ray(material.brdf, self.pcg, (d.x, d.y, d.z), (wp.x, wp.y, wp.z), (nrm.x, nrm.y, nrm.z))
+                child = self._radiance(HitRay(Vec(*o), Vec(*nd), tmin, float("inf"), depth + 1), depth + 1)
+                cr, cg, cb = cr + r * child.r, cg + g * child.g, cb + b * child.b
         k = 1.0 / self.num_of_rays
         return Color(em.r + cr * k, em.g + cg * k, em.b + cb * k)
 

@@ -24,7 +24,15 @@ hit-record buffer in HBM, a generator per record, both channels, with ``roulette
 effective bandwidth from the bytes a record moves (112 B in, 132 B out; a record without a hit reads 20 B of them), beside the
 6.29 TB/s a float4 copy reaches on this chip.  Then the whole ``PathTracerShader`` route (hit-record frame, then per depth a
 scatter and a trace, the sums on the host) beside the fused ``PathTracer`` at ``num_of_rays=1, max_depth=3``: wall time of
-``fire_all_rays``, and whether the two frames are byte-identical."""
+``fire_all_rays``, and whether the two frames are byte-identical.
+
+    python tools/raybench.py --radiance [...]
+
+The radiance query (libptrace_radiance.so: pt_rays_radiance_device) on the C2 frame's primary rays, a generator per ray
+(``PCG(45, 54 + i)``: the fused path tracer's ``pcg_mode="sample"`` at ``samples_per_side=0``), ``max_depth=3``, limit 3, timed the
+same way with ``num_of_rays`` 1 and 10: rays traced per second, beside the fused path-tracer frame of the same parameters
+(``stats().kernel_ms``; the frames are compared byte for byte) and, at ``num_of_rays=1``, beside the chain in HBM that the four
+steps before it make: trace + 3 x (scatter + trace), every batch read in place out of the one before."""
 import argparse
 import ctypes as C
 import os
@@ -43,7 +51,10 @@ def main():
     ap.add_argument("--steps", type=int, default=10)
     ap.add_argument("--shade", action="store_true", help="time the surface queries instead of the ray batches")
     ap.add_argument("--scatter", action="store_true", help="time the bounce (roulette + scatter_ray) and the PathTracerShader route")
+    ap.add_argument("--radiance", action="store_true", help="time the radiance query beside the chain in HBM and the fused path tracer")
     args = ap.parse_args()
+    if args.radiance:
+        return radiance(args)
     if args.shade:
         return shade(args)
     if args.scatter:
@@ -233,6 +244,90 @@ def scatter(args):
     same = images["fused PathTracer"].tobytes() == images["PathTracerShader"].tobytes()
     print(f"the two frames are {'byte-identical' if same else 'DIFFERENT'}")
     return 0 if same else 1
+
+
+def radiance(args):
+    import torch
+
+    from pytracer_amd import abi, flatten, rays as rb, scenes
+    from pytracer_amd.device import DeviceScene
+    from pytracer_amd.devmem import DeviceBuffer, DeviceSpan
+
+    W, H = args.width, args.height
+    n = W * H
+    D, LIMIT, BG = 3, 3, (0.1, 0.2, 0.3)
+    flat = flatten.flatten_world(scenes.synthetic_world(32, with_plane=True))
+    cam = flatten.flatten_camera(scenes.synthetic_camera(W, H))
+    p_hits = abi.make_params(W, H, abi.RENDERER_FLAT, samples_per_side=0)
+    ok = True
+    with DeviceScene(flat) as ds:
+        frame = ds.render_hits(cam, p_hits, abi.HIT_RAY)
+        block = rb.ray_planes(frame.ray_origin.reshape(n, 3), frame.ray_dir.reshape(n, 3))
+        rays_dev = torch.from_numpy(block).cuda()
+        gen = rb.pcg_streams(45, 54 + np.arange(n, dtype=np.uint64))
+        pcg_dev = torch.from_numpy(gen.view(np.int64)).cuda()
+        stream = torch.cuda.Stream()
+        torch.cuda.synchronize()
+
+        def timed(go, steps):
+            for _ in range(args.warmup):
+                go()
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record(stream)
+            for _ in range(steps):
+                go()
+            e1.record(stream)
+            e1.synchronize()
+            return e0.elapsed_time(e1) / steps
+
+        print(f"C2 {W}x{H}: {n} primary rays, max_depth={D}, russian_roulette_limit={LIMIT}")
+        for N in (1, 10):
+            steps = args.steps if N == 1 else max(2, args.steps // 3)
+            ws = DeviceBuffer((ds.radiance_workspace_bytes(n, N, D),), np.uint8)
+            out = DeviceBuffer((rb.radiance_bytes(n, rb.RAD_ALL),), np.uint8)
+            ms = timed(lambda: ds.radiance(rays_dev, pcg_dev, N, D, LIMIT, BG, 0, "all", device=True, stream=stream.cuda_stream, out=out,
+                                           workspace=ws), steps)
+            res = rb.RayRadiance(out.numpy(), n)
+            traced = int(res.n_rays.sum())
+            par = abi.make_params(W, H, abi.RENDERER_PATHTRACER, samples_per_side=0, num_of_rays=N, max_depth=D, rr_limit=LIMIT,
+                                  pcg_mode=abi.PCG_SAMPLE, path_state=45, path_seq=54, background=BG)
+            fused_ms = []
+            for _ in range(args.warmup + steps):
+                img = ds.render(cam, par)
+                fused_ms.append(ds.stats().kernel_ms)
+            fused_ms = float(np.median(fused_ms[args.warmup:]))
+            same = np.ascontiguousarray(res.radiance).reshape(H, W, 3).tobytes() == np.ascontiguousarray(img, dtype=np.float64).tobytes()
+            ok = ok and same
+            print(f"radiance num_of_rays={N:2d}  {ms:9.3f} ms  {traced:9d} rays traced  {traced / ms / 1e3:8.1f} Mray/s  "
+                  f"workspace {ws.nbytes / 2 ** 20:.1f} MiB  | fused frame kernel(s) {fused_ms:9.3f} ms (kernel {ds.stats().kernel}, "
+                  f"{int(ds.stats().n_rays)} rays): the query takes {ms / fused_ms:.2f} x; frames {'byte-identical' if same else 'DIFFERENT'}")
+            if N != 1:
+                continue
+            # the chain of the four steps before, in HBM: trace, then per depth scatter and trace
+            ALL = rb.RAY_CHANNELS
+            hit_bufs = [DeviceBuffer((rb.rays_bytes(n, ALL),), np.uint8) for _ in range(2)]
+            scat_bufs = [DeviceBuffer((rb.scatter_bytes(n, rb.SCAT_ALL),), np.uint8) for _ in range(2)]
+            ds.slot_table()
+            soff = lambda sel, comp=0: rb.scatter_plane_offset(n, rb.SCAT_ALL, sel, comp)  # noqa: E731
+
+            def planes(buf):
+                base = buf.data_ptr()
+                return [base] + [base + rb.rays_plane_offset(n, ALL, False, ch, 0) for ch in (abi.HIT_POINT, abi.HIT_NORMAL, abi.HIT_UV)]
+
+            def chain():
+                st = stream.cuda_stream
+                hits = ds.trace_rays(rays_dev, ALL, device=True, stream=st, out=hit_bufs[0])
+                dirs, pcg = rays_dev.data_ptr() + 3 * n * 8, pcg_dev
+                for depth in range(D):
+                    sc = ds.scatter(*planes(hits), dirs, pcg, depth >= LIMIT, "all", device=True, stream=st, out=scat_bufs[depth & 1], n=n)
+                    hits = ds.trace_rays(DeviceSpan(sc, 64 * n, soff(rb.SCAT_RAYS)), ALL, device=True, stream=st, out=hit_bufs[(depth + 1) & 1])
+                    dirs = sc.data_ptr() + soff(rb.SCAT_RAYS, 3)
+                    pcg = (sc.data_ptr() + soff(rb.SCAT_PCG, 0), sc.data_ptr() + soff(rb.SCAT_PCG, 1))
+
+            chain_ms = timed(chain, steps)
+            print(f"chain in HBM: trace + {D} x (scatter + trace)  {chain_ms:9.3f} ms (7 launches; without the last depth's scatter and the "
+                  f"sums): the query takes {ms / chain_ms:.2f} x")
+    return 0 if ok else 1
 
 
 if __name__ == "__main__":
