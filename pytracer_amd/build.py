@@ -1,5 +1,5 @@
-"""Build recipe for libptrace.so and its add-ons libptrace_rays.so, libptrace_surface.so, libptrace_scatter.so and
-libptrace_radiance.so (HIP, gfx950 only).
+"""Build recipe for libptrace.so and its add-ons libptrace_rays.so, libptrace_surface.so, libptrace_scatter.so,
+libptrace_radiance.so and libptrace_gather.so (HIP, gfx950 only).
 
 ``hipcc --offload-arch=gfx950 -O3 -ffp-contract=off``: the parity kernels must not fuse a*b+c (the
 reference is Python: every operation rounds), and nothing enables fast-math.  The library is built
@@ -17,6 +17,9 @@ records) is the fourth: the exported symbols of libptrace_surface.so are pinned 
 
 ``libptrace_radiance.so`` (csrc/ptrace_radiance.hip, include/ptrace_radiance.h: the whole ``PathTracer`` recursion for ray
 batches) is the fifth: the exported symbols of libptrace_scatter.so are pinned to its seven.
+
+``libptrace_gather.so`` (csrc/ptrace_gather.hip, include/ptrace_gather.h: the mean radiance over the hemisphere of batches of
+surface points) is the sixth: the exported symbols of libptrace_radiance.so are pinned to its eight.
 """
 from __future__ import annotations
 
@@ -37,13 +40,16 @@ SCATTER_LIB = os.path.join(HERE, "libptrace_scatter.so")
 SCATTER_SOURCES = ["ptrace_scatter.hip"]
 RADIANCE_LIB = os.path.join(HERE, "libptrace_radiance.so")
 RADIANCE_SOURCES = ["ptrace_radiance.hip"]
+GATHER_LIB = os.path.join(HERE, "libptrace_gather.so")
+GATHER_SOURCES = ["ptrace_gather.hip"]
 # every file the one translation unit includes: all of csrc/ (tests/test_host.py checks this list against the #include lines)
 DEPS = sorted(f for f in os.listdir(CSRC) if f.endswith((".hip", ".h"))) + [os.path.join("..", "..", "include", "ptrace.h"),
                                                                             os.path.join("..", "..", "include", "ptrace_debug.h"),
                                                                             os.path.join("..", "..", "include", "ptrace_rays.h"),
                                                                             os.path.join("..", "..", "include", "ptrace_surface.h"),
                                                                             os.path.join("..", "..", "include", "ptrace_scatter.h"),
-                                                                            os.path.join("..", "..", "include", "ptrace_radiance.h")]
+                                                                            os.path.join("..", "..", "include", "ptrace_radiance.h"),
+                                                                            os.path.join("..", "..", "include", "ptrace_gather.h")]
 FLAGS = ["--offload-arch=gfx950", "-O3", "-ffp-contract=off", "-fno-fast-math", "-std=c++17", "-fPIC",
          "-shared", "-Wall", "-Wno-unused-function", "-Wno-pass-failed",
          # a fixed compilation-unit id: by default clang derives it from the command line (paths included), which would make
@@ -53,9 +59,11 @@ RAYS_FLAGS = FLAGS[:-1] + ["-cuid=libptrace_rays"]
 SURFACE_FLAGS = FLAGS[:-1] + ["-cuid=libptrace_surface"]
 SCATTER_FLAGS = FLAGS[:-1] + ["-cuid=libptrace_scatter"]
 RADIANCE_FLAGS = FLAGS[:-1] + ["-cuid=libptrace_radiance"]
+GATHER_FLAGS = FLAGS[:-1] + ["-cuid=libptrace_gather"]
 # every library the recipe makes, in build order: what build() and needs_build() walk
 TARGETS = ((FLAGS, LIB, SOURCES), (RAYS_FLAGS, RAYS_LIB, RAYS_SOURCES), (SURFACE_FLAGS, SURFACE_LIB, SURFACE_SOURCES),
-           (SCATTER_FLAGS, SCATTER_LIB, SCATTER_SOURCES), (RADIANCE_FLAGS, RADIANCE_LIB, RADIANCE_SOURCES))
+           (SCATTER_FLAGS, SCATTER_LIB, SCATTER_SOURCES), (RADIANCE_FLAGS, RADIANCE_LIB, RADIANCE_SOURCES),
+           (GATHER_FLAGS, GATHER_LIB, GATHER_SOURCES))
 
 
 def code_hash(lib: str = LIB) -> str:
@@ -97,7 +105,7 @@ def needs_build() -> bool:
     libs = [lib for _, lib, _ in TARGETS]
     if not all(os.path.exists(lib) for lib in libs):
         return True
-    t = min(os.path.getmtime(lib) for lib in libs)  # (one list of files for all five: they share the headers)
+    t = min(os.path.getmtime(lib) for lib in libs)  # (one list of files for all six: they share the headers)
     return any(os.path.getmtime(os.path.join(CSRC, d)) > t for d in DEPS)
 
 

@@ -340,7 +340,87 @@ def radiance(input_name, output, num_of_rays, max_depth, russian_roulette_limit,
     click.echo(f"{n} ray(s), {len(world.shapes)} shape(s), {int(res.n_rays.sum())} rays traced: wrote {output} ({', '.join(planes)})")
 
 
+@click.command("gather")
+@click.option("--input", "input_name", type=str, default=None,
+              help="An .npz holding `points` and `normals`, both [n, 3] (optionally `seqs`, [n]: the stream number of every record's "
+                   "sample 0).  Without it: the first hits of the scene's frame of --width x --height pixels")
+@click.option("--output", type=str, default="gather.npz", help="Name of the .npz file to create")
+@click.option("--samples", type=int, default=16, help="Hemisphere samples per record")
+@click.option("--num-of-rays", type=int, default=1, help="Number of rays departing from each surface point below the hemisphere's rays")
+@click.option("--max-depth", type=int, default=3, help="Maximum allowed ray depth")
+@click.option("--russian-roulette-limit", type=int, default=3, help="Depth from which on the Russian roulette runs")
+@click.option("--init-state", type=int, default=45, help="Initial seed of the generators (positive number)")
+@click.option("--init-seq", type=int, default=54,
+              help="Identifier of record 0's first sequence: sample k of record i draws from PCG(init_state, init_seq + i * samples + k)")
+@click.option("--depth", type=int, default=0, help="Ray.depth of the hemisphere's rays")
+@click.option("--width", type=int, default=640, help="Width of the frame (and what the scene's camera is built for)")
+@click.option("--height", type=int, default=480, help="Height of the frame")
+@click.option("--declare-float", "-d", type=str, multiple=True, help="Declare a variable: --declare-float=VAR:VALUE")
+@click.option("--device", type=int, default=0, help="GPU to trace on")
+@click.argument("input_scene_name", type=str, default="builtin:demo")
+def gather(input_name, output, samples, num_of_rays, max_depth, russian_roulette_limit, init_state, init_seq, depth, width, height,
+           declare_float, device, input_scene_name):
+    """The mean radiance arriving over the hemisphere of surface points (irradiance probes, light-map texels): per record
+    `samples` cosine-weighted rays, each followed by PathTracer(world, BLACK, its own generator, ...), averaged on the device in
+    sample order.  Writes an .npz of radiance [n, 3] and n_rays [n] -- for a frame [1, H, W(, 3)] beside its shape_index."""
+    import numpy as np
+
+    from . import abi
+    from . import rays as rb
+
+    try:
+        points = normals = seqs = None
+        if input_name is not None:
+            try:
+                batch = np.load(input_name)
+            except (OSError, ValueError) as e:
+                raise UsageError(f"--input {input_name}: {e}") from None
+            names = [] if isinstance(batch, np.ndarray) else list(batch.files)
+            if "points" not in names or "normals" not in names:
+                raise UsageError(f"--input {input_name}: expected an .npz holding `points` and `normals`, not {names or 'one array'}")
+            points, normals = np.asarray(batch["points"], dtype=np.float64), np.asarray(batch["normals"], dtype=np.float64)
+            if points.ndim != 2 or points.shape[1] != 3 or normals.shape != points.shape:
+                raise UsageError(f"--input {input_name}: points and normals must both be [n, 3], got {points.shape} and {normals.shape}")
+            if "seqs" in names:
+                seqs = np.asarray(batch["seqs"])
+                if seqs.shape != (points.shape[0],) or seqs.dtype.kind not in "iu":
+                    raise UsageError(f"--input {input_name}: seqs must be [n] integers, got {seqs.dtype} {seqs.shape}")
+        elif width < 1 or height < 1:
+            raise UsageError("--width and --height must be at least 1")
+        if samples < 1 or num_of_rays < 1 or max_depth < 0 or depth < 0:
+            raise UsageError("--samples and --num-of-rays must be at least 1, --max-depth and --depth not negative")
+        if max_depth - depth > 64:
+            raise UsageError(f"--max-depth {max_depth} with --depth {depth}: a gather query walks at most 64 levels")
+        n = points.shape[0] if points is not None else width * height
+        if n * samples > rb.MAX_RAYS:
+            raise UsageError(f"{n} records x {samples} samples: a gather takes at most 2^31 - 1 hemisphere rays (split the batch)")
+        world, camera, _ = _load_scene(input_scene_name, parse_float_overrides(declare_float), width, height)
+    except UsageError as e:
+        click.echo(f"pytracer_amd gather: {e}", err=True)
+        sys.exit(2)
+    from . import _lib, flatten
+    from .device import DeviceScene
+
+    _lib.standalone()  # (torch-free, like `render`)
+    kw = dict(num_of_rays=num_of_rays, max_depth=max_depth, russian_roulette_limit=russian_roulette_limit, background=(0.0, 0.0, 0.0),
+              depth=depth, channels="all", init_seq=init_seq)
+    if points is not None:
+        with DeviceScene(flatten.flatten_world(world), device) as scene:
+            res = rb.WorldQueries(scene).hemisphere_radiance(points, samples, init_state, seqs, normals=normals, **kw)
+        planes = res.planes()
+    else:
+        tracer = GpuImageTracer(image=hm.HdrImage(width, height), camera=camera, samples_per_side=0, device=device)
+        frame = tracer.fire_all_hits(world, abi.HIT_POINT | abi.HIT_NORMAL)
+        res = tracer.world_queries(world).hemisphere_radiance(frame, samples, init_state, None, **kw)
+        planes = dict(res.planes(), shape_index=np.asarray(frame.shape_index))
+        tracer.close()
+    np.savez(output, **planes)
+    click.echo(f"{res.n} record(s) x {samples} sample(s), {len(world.shapes)} shape(s), {int(res.n_rays.sum())} rays traced: "
+               f"wrote {output} ({', '.join(planes)})")
+
+
 cli.add_command(render)
 cli.add_command(hits)
 cli.add_command(rays)
 cli.add_command(radiance)
+cli.add_command(gather)

@@ -461,6 +461,83 @@ class DeviceScene:
                                                buf.ctypes.data_as(C.c_void_p), buf.nbytes))
         return rb.RayRadiance(buf, n, bits)
 
+    # -- the gather (include/ptrace_gather.h, libptrace_gather.so): mean hemisphere radiance per surface point, summed in sample order ---
+    def gather_workspace_bytes(self, n: int, samples: int, num_of_rays: int = 1, max_depth: int = 10, depth: int = 0) -> int:
+        """Bytes of the workspace ``gather(device=True)`` needs for ``n`` records of ``samples`` samples
+        (``pt_rays_gather_workspace_bytes``: the node stacks, sized by the lanes a launch keeps resident, and four 8-byte planes of
+        ``n * samples`` values for the samples' radiance and counts)."""
+        from . import _gather_lib
+
+        need = int(_gather_lib.lib().pt_rays_gather_workspace_bytes(self.device, int(n), int(samples), int(num_of_rays), int(max_depth),
+                                                                    int(depth)))
+        if need == 0:
+            raise ValueError(f"no workspace size for these arguments: {_gather_lib.last_error()}")
+        return need
+
+    def gather(self, points, normals, samples: int, init_state: int = 42, seqs=None, active=None, num_of_rays: int = 1,
+               max_depth: int = 10, russian_roulette_limit: int = 3, background=(0.0, 0.0, 0.0), depth: int = 0, channels="all",
+               init_seq: int = 54, device: bool = False, stream=None, out=None, workspace=None, n=None):
+        """Per record ``i`` of the planar ``[3, n]`` ``points`` and ``normals``: the mean over ``k < samples`` of
+        ``PathTracer(world, background, g, num_of_rays, max_depth, russian_roulette_limit)(DiffuseBRDF.scatter_ray(g, ., p_i, n_i,
+        depth))`` with ``g = PCG(init_state, seqs[i] + k)``, every sample on a lane of its own and the sum taken on the device
+        strictly in ``k`` order (include/ptrace_gather.h).  ``seqs``: ``uint64[n]``, or ``None``: ``init_seq + i * samples``.
+        ``active``: ``int32[n]`` (a ``shape_index`` plane as it is), negative = the record is skipped (radiance 0, count 0), or
+        ``None``.  ``channels``: ``"count"``, ``"all"``, ``"none"`` or ``PT_GATHER_*`` bits -> :class:`pytracer_amd.rays.GatheredRadiance`.
+        ``device=True``: ``points`` / ``normals`` (and ``seqs`` / ``active``) are ``DeviceBuffer`` s, device tensors or raw addresses
+        (then with ``n=``); the batch is enqueued on ``stream`` with ``workspace`` (:meth:`gather_workspace_bytes` bytes of device
+        memory; ``None``: a new buffer) -> the output ``DeviceBuffer`` (``out``, or a new one)."""
+        from . import _gather_lib, rays as rb
+
+        L, block, bits = _gather_lib.lib(), self.kernel_args(), rb.gather_channels(channels)
+        par = _gather_lib.params(samples, num_of_rays, max_depth, russian_roulette_limit, depth, init_state, init_seq, background)
+        if device:
+            from .devmem import DeviceBuffer
+
+            handle = getattr(stream, "handle", stream)
+            if n is None:
+                if not hasattr(points, "nbytes"):
+                    raise ValueError("n= is needed when the points are a raw device address")
+                n = int(points.nbytes) // 24
+            n = int(n)
+            if out is None:
+                out = DeviceBuffer((max(rb.gather_bytes(n, bits), 8),), np.uint8, self.device)
+            if workspace is None and n > 0:
+                # (0: arguments the library refuses -- the call below then says which, with its own error code)
+                need = int(L.pt_rays_gather_workspace_bytes(self.device, n, par.samples, par.num_of_rays, par.max_depth, par.depth0))
+                if need:
+                    workspace = DeviceBuffer((need,), np.uint8, self.device)
+                    out._gather_workspace = workspace  # in flight on `stream` as long as the output is: freed with it
+            ptr = self._plane_ptr
+            _gather_lib.check(L.pt_rays_gather_device(self.device, block, len(block), ptr(points, "points"), ptr(normals, "normals"),
+                                                      ptr(active, "active"), ptr(seqs, "seqs"), n, C.byref(par), bits,
+                                                      ptr(workspace, "workspace"), int(workspace.nbytes) if workspace is not None else 0,
+                                                      ptr(out, "out"), int(out.nbytes), C.c_void_p(handle) if handle else None))
+            if hasattr(out, "rendered_on"):
+                out.rendered_on(stream)
+            if hasattr(workspace, "rendered_on"):
+                workspace.rendered_on(stream)
+            return out
+        if stream is not None or out is not None or n is not None or workspace is not None:
+            raise ValueError("stream=, out=, workspace= and n= go with device=True (host batches are staged and synchronous)")
+        points = np.ascontiguousarray(points, dtype=np.float64)
+        normals = np.ascontiguousarray(normals, dtype=np.float64)
+        if points.ndim != 2 or points.shape[0] != 3 or normals.shape != points.shape:
+            raise ValueError(f"points and normals must both be planar [3, n] (pytracer_amd.rays.planar), not {points.shape} and {normals.shape}")
+        n = points.shape[1]
+        if seqs is not None:
+            seqs = rb.stream_numbers(seqs)
+            if seqs.shape != (n,):
+                raise ValueError(f"seqs must hold one stream number per record ({n}), not {seqs.shape}")
+        if active is not None:
+            active = np.ascontiguousarray(np.asarray(active).reshape(-1), dtype=np.int32)
+            if active.shape != (n,):
+                raise ValueError(f"active must hold one int32 per record ({n}), not {active.shape}")
+        buf = np.empty(rb.gather_bytes(n, bits), dtype=np.uint8)
+        p = lambda a: a.ctypes.data_as(C.c_void_p) if a is not None else None  # noqa: E731
+        _gather_lib.check(L.pt_rays_gather(self.device, block, len(block), p(points), p(normals), p(active), p(seqs), n, C.byref(par), bits,
+                                           p(buf), buf.nbytes))
+        return rb.GatheredRadiance(buf, n, bits)
+
     def cull_probe(self, cam: abi.Camera, width: int, height: int, x0: int, x1: int, row0: int, row1: int,
                    pixel=None) -> np.ndarray:
         """Diagnostics: which shapes (by ``World.shapes`` index) the conservative cull of the primary rays through

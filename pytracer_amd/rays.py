@@ -18,6 +18,11 @@ Its fifth -- the whole recursion: ``PathTracer(world, background, pcg_i, ...)(ra
 depth-first on the device -- goes through ``DeviceScene.radiance`` (include/ptrace_radiance.h, libptrace_radiance.so) or
 ``WorldQueries.path_radiance``: :class:`RayRadiance` views the answer.
 
+Its sixth -- the gather: the mean radiance arriving over the hemisphere of every record (an irradiance probe, a light-map
+texel), ``samples`` cosine-weighted rays per record made, walked and averaged on the device in a fixed order -- goes through
+``DeviceScene.gather`` (include/ptrace_gather.h, libptrace_gather.so) or ``WorldQueries.hemisphere_radiance``:
+:class:`GatheredRadiance` views the answer.
+
 Layout: planar.  A batch is ``[8, n]`` float64 -- origin xyz, direction xyz, tmin, tmax, the fields of ``Ray`` (ray.py:29-50);
 a result is one buffer, the int32 shape plane first (padded to 8 bytes), then the selected fp64 planes of ``n`` values each.
 """
@@ -45,6 +50,9 @@ _PCG_MULT = 6364136223846793005
 
 RAD_PCG, RAD_COUNT, RAD_ALL = 1, 2, 3  # PT_RAD_* of include/ptrace_radiance.h
 _RAD_OF = {"pcg": RAD_PCG, "count": RAD_COUNT}
+
+
+GATHER_COUNT, GATHER_ALL = 1, 1  # PT_GATHER_* of include/ptrace_gather.h
 
 
 def ray_channels(channels) -> int:
@@ -467,6 +475,90 @@ class RayRadiance:
         return out
 
 
+def gather_channels(channels) -> int:
+    """``PT_GATHER_*`` bits from an int, a name (``"count"``), ``"all"`` or ``"none"``."""
+    if isinstance(channels, str):
+        names = [x.strip().lower() for x in channels.split(",") if x.strip()]
+        if names == ["all"]:
+            return GATHER_ALL
+        if names == ["none"]:
+            return 0
+        unknown = [x for x in names if x != "count"]
+        if unknown:
+            raise ValueError(f"a gather batch has the channel count; not {', '.join(unknown)}")
+        return GATHER_COUNT if names else 0
+    bits = int(channels)
+    if bits < 0 or bits & ~GATHER_ALL:
+        raise ValueError(f"a gather batch has the channel count (1); not {bits:#x}")
+    return bits
+
+
+def gather_bytes(n: int, channels: int) -> int:
+    """Mirror of ``pt_rays_gather_bytes``: 0 for arguments the library refuses."""
+    if not (0 <= n <= MAX_RAYS and 0 <= channels <= GATHER_ALL):
+        return 0
+    return n * 8 * (3 + (1 if channels & GATHER_COUNT else 0))
+
+
+def gather_plane_offset(n: int, channels: int, channel: int, component: int = 0) -> int:
+    """Mirror of ``pt_rays_gather_plane_offset`` (bytes; ``channel`` 0: the three radiance planes, ``GATHER_COUNT``; < 0: not
+    selected)."""
+    if not (0 <= n <= MAX_RAYS and 0 <= channels <= GATHER_ALL) or component < 0:
+        return -1
+    if channel == 0:
+        return n * 8 * component if component < 3 else -1
+    if channel == GATHER_COUNT and channels & GATHER_COUNT:
+        return n * 24 if component < 1 else -1
+    return -1
+
+
+class GatheredRadiance:
+    """Views over the buffer of a gather batch (``buf``: ``pt_rays_gather_bytes`` bytes, contiguous ``uint8``).  Nothing here
+    copies.  ``radiance``: per record the mean of ``PathTracer(...)(ray)`` over its ``samples`` hemisphere rays, summed in sample
+    order, with the component as last axis; ``n_rays``: the rays handed to a world query for the record (``uint64``).  ``shape``:
+    what the records' axis is viewed as (a frame's ``[nsamp, rows, W]``); default ``[n]``."""
+
+    def __init__(self, buf, n: int, channels=GATHER_ALL, shape=None):
+        self.channels = gather_channels(channels)
+        self.n = int(n)
+        self.shape = (self.n,) if shape is None else tuple(int(x) for x in shape)
+        if int(np.prod(self.shape, dtype=np.int64)) != self.n:
+            raise ValueError(f"shape {self.shape} does not hold {self.n} records")
+        self.nbytes = gather_bytes(self.n, self.channels)
+        buf = np.asarray(buf)
+        if buf.dtype != np.uint8 or buf.ndim != 1:
+            buf = buf.reshape(-1).view(np.uint8)
+        if buf.nbytes < self.nbytes:
+            raise ValueError(f"gather buffer too small: {buf.nbytes} < {self.nbytes} bytes")
+        self.buffer = buf
+        self.radiance = np.moveaxis(buf[: self.n * 24].view(np.float64).reshape((3,) + self.shape), 0, -1)
+
+    def has(self, name: str) -> bool:
+        return name == "count" and bool(self.channels & GATHER_COUNT)
+
+    @property
+    def n_rays(self) -> np.ndarray:
+        if not self.channels & GATHER_COUNT:
+            raise KeyError(f"channel 'count' was not selected for this gather batch (channels = {self.channels:#x})")
+        off = gather_plane_offset(self.n, self.channels, GATHER_COUNT, 0)
+        return self.buffer[off: off + self.n * 8].view(np.uint64).reshape(self.shape)
+
+    def planes(self) -> dict:
+        """name -> view, for every selected channel (what the ``gather`` command writes into its ``.npz``)."""
+        out = {"radiance": self.radiance}
+        if self.has("count"):
+            out["n_rays"] = self.n_rays
+        return out
+
+
+def stream_numbers(seqs) -> np.ndarray:
+    """``uint64[n]`` from stream numbers of any size and sign, wrapped into the 64-bit range as :func:`pcg_streams` wraps them
+    (a signed array like the C cast; Python ints modulo 2^64): the ``seqs`` plane of a gather batch."""
+    if isinstance(seqs, np.ndarray) and seqs.dtype.kind in "iu":
+        return np.ascontiguousarray(seqs.astype(np.uint64).reshape(-1))
+    return np.array([int(x) & (2 ** 64 - 1) for x in np.atleast_1d(np.asarray(seqs, dtype=object)).reshape(-1)], dtype=np.uint64)
+
+
 def pcg_streams(init_state, init_seqs, skip: int = 0) -> np.ndarray:
     """``uint64[2, n]``: state and increment of ``PCG(init_state, seq)`` (pcg.py:25-41; csrc/pt_math.h: pcg_seed) for every
     ``seq`` of ``init_seqs``, ``skip`` draws in -- the generators a scatter batch carries.  Every value of the 64-bit range is
@@ -559,3 +651,28 @@ class WorldQueries:
         device -> :class:`RayRadiance`."""
         return self.scene.radiance(ray_planes(rays, dirs, tmin, tmax), pcg, num_of_rays, max_depth, russian_roulette_limit, background,
                                    depth, channels)
+
+    def hemisphere_radiance(self, hits, samples, init_state: int = 42, seqs=None, num_of_rays: int = 1, max_depth: int = 10,
+                            russian_roulette_limit: int = 3, background=(0.0, 0.0, 0.0), depth: int = 0, channels="all", normals=None,
+                            active=None, init_seq: int = 54) -> GatheredRadiance:
+        """The mean radiance arriving over the hemisphere of every record: ``samples`` rays per record, sample ``k`` of record
+        ``i`` being ``DiffuseBRDF.scatter_ray`` at the record's point and normal (``Ray.depth = depth``) drawn from
+        ``PCG(init_state, seqs[i] + k)`` and followed by ``PathTracer(world, background, that generator, num_of_rays, max_depth,
+        russian_roulette_limit)``; the mean is taken on the device, strictly in sample order.  ``hits``: a :class:`RayHits` or a
+        hit-record frame with ``point`` and ``normal`` -- its ``shape_index`` says which records are skipped (no hit: radiance 0,
+        count 0).  Or plain arrays: ``hits`` the ``[..., 3]`` points and ``normals=`` the ``[..., 3]`` normals (``active=``: an
+        optional int32 array, negative = skipped).  ``seqs=None``: record ``i`` starts at stream ``init_seq + i * samples``, which
+        keeps all streams disjoint -> :class:`GatheredRadiance`, shaped like the records."""
+        if normals is None:
+            if not (hasattr(hits, "point") and hasattr(hits, "normal")):
+                raise ValueError("hits must carry point and normal (a RayHits or a hit frame), or pass the points with normals=")
+            points, normals, shape = hits.point, hits.normal, np.asarray(hits.shape_index).shape
+            if active is None:
+                active = hits.shape_index
+        else:
+            points = np.asarray(hits, dtype=np.float64)
+            shape = points.shape[:-1]
+        bits = gather_channels(channels)
+        out = self.scene.gather(planar(points, 3), planar(normals, 3), samples, init_state, seqs, active, num_of_rays, max_depth,
+                                russian_roulette_limit, background, depth, bits, init_seq=init_seq)
+        return GatheredRadiance(out.buffer, out.n, bits, shape=shape)

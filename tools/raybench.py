@@ -32,7 +32,17 @@ The radiance query (libptrace_radiance.so: pt_rays_radiance_device) on the C2 fr
 (``PCG(45, 54 + i)``: the fused path tracer's ``pcg_mode="sample"`` at ``samples_per_side=0``), ``max_depth=3``, limit 3, timed the
 same way with ``num_of_rays`` 1 and 10: rays traced per second, beside the fused path-tracer frame of the same parameters
 (``stats().kernel_ms``; the frames are compared byte for byte) and, at ``num_of_rays=1``, beside the chain in HBM that the four
-steps before it make: trace + 3 x (scatter + trace), every batch read in place out of the one before."""
+steps before it make: trace + 3 x (scatter + trace), every batch read in place out of the one before.
+
+    python tools/raybench.py --gather [...]
+
+The gather query (libptrace_gather.so: pt_rays_gather_device) on the first hits of the C2 frame, ``max_depth=3``, limit 3, sample
+``k`` of record ``i`` drawing from ``PCG(45, 54 + i K + k)``: K = 16 and ``num_of_rays`` 1 on every record, K = 64 on every 8th, K = 16
+with ``num_of_rays`` 2.  Beside each, in the same process, the route a caller has without it, minus its host work: the ``n K`` sample
+rays and their generators made beforehand in HBM (the scatter query on records that name a diffuse shape; not timed), then
+``pt_rays_radiance_device`` on them, timed the same way; the host's sum of that output in sample order is compared with the gather's
+output bit for bit.  Last, the time of the radiance query with ``num_of_rays = K`` on ONE ray per record (the frame's primary ray):
+another estimator -- one generator per record, K children at every depth -- reported for comparison."""
 import argparse
 import ctypes as C
 import os
@@ -52,7 +62,10 @@ def main():
     ap.add_argument("--shade", action="store_true", help="time the surface queries instead of the ray batches")
     ap.add_argument("--scatter", action="store_true", help="time the bounce (roulette + scatter_ray) and the PathTracerShader route")
     ap.add_argument("--radiance", action="store_true", help="time the radiance query beside the chain in HBM and the fused path tracer")
+    ap.add_argument("--gather", action="store_true", help="time the gather query beside path_radiance on the same sample rays prepared in HBM")
     args = ap.parse_args()
+    if args.gather:
+        return gather(args)
     if args.radiance:
         return radiance(args)
     if args.shade:
@@ -327,6 +340,104 @@ def radiance(args):
             chain_ms = timed(chain, steps)
             print(f"chain in HBM: trace + {D} x (scatter + trace)  {chain_ms:9.3f} ms (7 launches; without the last depth's scatter and the "
                   f"sums): the query takes {ms / chain_ms:.2f} x")
+    return 0 if ok else 1
+
+
+def gather(args):
+    import torch
+
+    from pytracer_amd import abi, flatten, rays as rb, scenes
+    from pytracer_amd.device import DeviceScene
+    from pytracer_amd.devmem import DeviceBuffer, DeviceSpan
+
+    W, H = args.width, args.height
+    D, LIMIT, BG, S0, Q0 = 3, 3, (0.1, 0.2, 0.3), 45, 54
+    flat = flatten.flatten_world(scenes.synthetic_world(32, with_plane=True))
+    cam = flatten.flatten_camera(scenes.synthetic_camera(W, H))
+    p_hits = abi.make_params(W, H, abi.RENDERER_FLAT, samples_per_side=0)
+    ok = True
+    with DeviceScene(flat) as ds:
+        frame = ds.render_hits(cam, p_hits, abi.HIT_POINT | abi.HIT_NORMAL | abi.HIT_RAY)
+        hit = np.asarray(frame.hit).reshape(-1)
+        points, normals = np.asarray(frame.point).reshape(-1, 3)[hit], np.asarray(frame.normal).reshape(-1, 3)[hit]
+        origins, dirs = np.asarray(frame.ray_origin).reshape(-1, 3)[hit], np.asarray(frame.ray_dir).reshape(-1, 3)[hit]
+        # a shape whose BRDF is diffuse and whose pigment is not black: the scatter query, told that every record lies on it, makes
+        # DiffuseBRDF.scatter_ray at the record's own point and normal -- the gather's hemisphere ray
+        one = np.zeros((1, 3))
+        diffuse = next(s for s in range(flat.n_shapes)
+                       if (lambda sc: sc.status[0] == 1 and sc.rays[6, 0] == 1.0e-3)(ds.scatter([s], one, one + 1.0, np.zeros((1, 2)), one + 1.0,
+                                                                                                 rb.pcg_streams(S0, [Q0]), False, "none")))
+        stream = torch.cuda.Stream()
+        st = stream.cuda_stream
+
+        def timed(go, steps, warmup):
+            for _ in range(warmup):
+                go()
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record(stream)
+            for _ in range(steps):
+                go()
+            e1.record(stream)
+            e1.synchronize()
+            return e0.elapsed_time(e1) / steps
+
+        print(f"C2 {W}x{H}: {points.shape[0]} first hits, max_depth={D}, russian_roulette_limit={LIMIT}; sample k of record i draws from "
+              f"PCG({S0}, {Q0} + i K + k)")
+        for K, N, every in ((16, 1, 1), (64, 1, 8), (16, 2, 1)):
+            pts, nrm = np.ascontiguousarray(points[::every].T), np.ascontiguousarray(normals[::every].T)
+            m = pts.shape[1]
+            total = m * K
+            pts_dev, nrm_dev = torch.from_numpy(pts).cuda(), torch.from_numpy(nrm).cuda()
+            # -- the gather: records in, means out
+            ws = DeviceBuffer((ds.gather_workspace_bytes(m, K, N, D),), np.uint8)
+            out = DeviceBuffer((rb.gather_bytes(m, rb.GATHER_ALL),), np.uint8)
+            torch.cuda.synchronize()
+            ms = timed(lambda: ds.gather(pts_dev, nrm_dev, K, S0, None, None, N, D, LIMIT, BG, 0, "all", init_seq=Q0, device=True, stream=st,
+                                         out=out, workspace=ws), args.steps, args.warmup)
+            res = rb.GatheredRadiance(out.numpy(), m)
+            traced = int(res.n_rays.sum())
+            # -- today's route, its host work left out: the n K sample rays and generators prepared in HBM (not timed) ...
+            rep = lambda t: t.repeat_interleave(K, dim=1).contiguous()  # noqa: E731  (record-major: sample j = i K + k)
+            gen_dev = torch.from_numpy(rb.pcg_streams(S0, Q0 + np.arange(total, dtype=np.uint64)).view(np.int64)).cuda()
+            shape_dev = torch.full((total,), diffuse, dtype=torch.int32, device="cuda")
+            uv_dev = torch.zeros((2, total), dtype=torch.float64, device="cuda")
+            sample_pts, sample_nrm = rep(pts_dev), rep(nrm_dev)
+            torch.cuda.synchronize()
+            sc = ds.scatter(shape_dev, sample_pts, sample_nrm, uv_dev, sample_nrm, gen_dev, False, "none", device=True, stream=st, n=total)
+            soff = lambda sel, comp=0: rb.scatter_plane_offset(total, 0, sel, comp)  # noqa: E731
+            rays_span = DeviceSpan(sc, 64 * total, soff(rb.SCAT_RAYS))
+            pcg_pair = (sc.data_ptr() + soff(rb.SCAT_PCG, 0), sc.data_ptr() + soff(rb.SCAT_PCG, 1))
+            del shape_dev, uv_dev, sample_pts, sample_nrm, gen_dev
+            # ... then the radiance query on them, timed the same way
+            rws = DeviceBuffer((ds.radiance_workspace_bytes(total, N, D),), np.uint8)
+            rout = DeviceBuffer((rb.radiance_bytes(total, rb.RAD_COUNT),), np.uint8)
+            route_ms = timed(lambda: ds.radiance(rays_span, pcg_pair, N, D, LIMIT, BG, 0, "count", device=True, stream=st, out=rout,
+                                                 workspace=rws, n=total), args.steps, args.warmup)
+            rad = rb.RayRadiance(rout.numpy(), total, "count")
+            acc = np.zeros((m, 3))
+            per_sample = np.asarray(rad.radiance).reshape(m, K, 3)
+            for k in range(K):
+                acc = acc + per_sample[:, k, :]
+            same = (acc * (1.0 / K)).tobytes() == np.ascontiguousarray(res.radiance).tobytes() and \
+                np.array_equal(np.asarray(rad.n_rays).reshape(m, K).sum(axis=1, dtype=np.uint64), res.n_rays)
+            ok = ok and same
+            print(f"gather K={K:2d} num_of_rays={N}  {m:7d} records  {ms:9.3f} ms  {traced:10d} rays traced  {traced / ms / 1e3:8.1f} Mray/s  "
+                  f"workspace {ws.nbytes / 2 ** 20:.1f} MiB  | path_radiance on the same {total} sample rays in HBM {route_ms:9.3f} ms: the gather "
+                  f"takes {ms / route_ms:.2f} x; its output {'equals' if same else 'DIFFERS FROM'} the host's ordered sum of theirs bit for bit")
+            del sc, rout, rws, rad, per_sample
+            if N != 1:
+                continue
+            # -- for comparison: num_of_rays = K on the record's one primary ray (another estimator: one generator per record)
+            block = torch.from_numpy(rb.ray_planes(origins[::every], dirs[::every])).cuda()
+            one_gen = torch.from_numpy(rb.pcg_streams(S0, Q0 + np.arange(m, dtype=np.uint64)).view(np.int64)).cuda()
+            tws = DeviceBuffer((ds.radiance_workspace_bytes(m, K, D),), np.uint8)
+            tout = DeviceBuffer((rb.radiance_bytes(m, rb.RAD_COUNT),), np.uint8)
+            torch.cuda.synchronize()
+            tree_ms = timed(lambda: ds.radiance(block, one_gen, K, D, LIMIT, BG, 0, "count", device=True, stream=st, out=tout, workspace=tws),
+                            2, 1)
+            tree_rays = int(rb.RayRadiance(tout.numpy(), m, "count").n_rays.sum())
+            print(f"    radiance query, num_of_rays={K} on one primary ray per record (another estimator): {tree_ms:9.3f} ms, {tree_rays} rays "
+                  f"traced, {tree_rays / tree_ms / 1e3:.1f} Mray/s")
     return 0 if ok else 1
 
 
