@@ -46,15 +46,41 @@ PT_DEV bool tie_wins(const PtKArgs &a, int slot, int best) {
 
 // shapes.py:103-121 given the object-space ray (ox..dz, aa = |d'|^2, cc = |o'|^2 - 1): the first root
 // inside (tmin, tmax) is this shape's hit; it replaces the winner if closer (world.py:62).
-#define PT_SPHERE_ROOTS(SLOT)                                                         \
+//
+// INSIDE (PT_SPHERE_ROOTS_IN): the caller knows, from the hoisted c = |o'|^2 - 1 of a shape (one number per shape and
+// frame, in scalar registers), that the common origin of the primary rays lies well inside the sphere: c <= -0.5
+// (pt_origin_inside; the margin the dome shortcut trusts).  Then the first quotient is never accepted and its division is
+// left out; everything else runs in the same operations and order.  Why, for every ray with tmin >= 0 (primary rays:
+// tmin = 1e-5) -- no range of aa or bb is assumed, so the argument holds behind wave_guard's [1e-100, 1e100] on the
+// direction (the scale+translate path) and on the full-product path alike:
+//  * aa is a sum of squares: >= 0 or NaN, so den = fl(2 aa) >= 0 or NaN.  A NaN in aa, bb or cc makes delta NaN, and
+//    delta > 0 fails on both sides.
+//  * y = fl(fl(4 aa) cc) <= 0 (-0 and -inf included) since cc < 0, hence delta = fl(x - y) >= x = fl(bb bb): rounding is
+//    monotone and x is representable.
+//  * x normal: fl(sqrt(fl(b^2))) = |b| in radix 2 absent under- and overflow, and sqrt is correctly rounded, hence
+//    monotone: sd = fl(sqrt(delta)) >= fl(sqrt(x)) = |bb|.
+//  * bb bb below the normal range (|bb| < 2^-511) and aa > 0: x >= bb^2 - 2^-1075, and -y >= 2^-1073 because
+//    fl(4 aa) >= 2^-1072 and |cc| >= 0.5; x + 2^-1073 is representable, so delta >= x + 2^-1073 > bb^2 and again sd >= |bb|.
+//    (aa = 0: den = 0, the quotient is NaN or infinite, neither lies in (tmin, tmax).)
+//  * bb bb overflows: sd = inf, -bb - sd is -inf or NaN.
+//  So -bb - sd <= 0 (or NaN) over den >= 0 (or NaN): the quotient is <= 0, -inf, +-0 or NaN, never > tmin.
+//  tests/proofs/sphere_inside_roots.c runs both forms over 1e8 inputs, the corners above among them.
+PT_DEV bool pt_origin_inside(double hoisted_c) { return hoisted_c <= -0.5; }  // (NaN: false)
+
+#define PT_SPHERE_ROOTS(SLOT) PT_SPHERE_ROOTS_IN(SLOT, false)
+#define PT_SPHERE_ROOTS_IN(SLOT, INSIDE)                                              \
   do {                                                                                \
     const double bb = 2.0 * (ox * dx + oy * dy + oz * dz);                            \
     const double delta = bb * bb - 4.0 * aa * cc;                                     \
     if (active && delta > 0.0) {                                                      \
       const double sd = sqrt(delta);                                                  \
       const double den = 2.0 * aa;                                                    \
-      double t = (-bb - sd) / den;                                                    \
-      bool ok = (t > tmin) && (t < tmax);                                             \
+      double t = 0.0;                                                                 \
+      bool ok = false;                                                                \
+      if (!(INSIDE)) {                                                                \
+        t = (-bb - sd) / den;                                                         \
+        ok = (t > tmin) && (t < tmax);                                                \
+      }                                                                               \
       if (!ok) {                                                                      \
         t = (-bb + sd) / den;                                                         \
         ok = (t > tmin) && (t < tmax);                                                \

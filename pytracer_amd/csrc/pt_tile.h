@@ -311,7 +311,9 @@ PT_DEV int world_query_tile(const PtKArgs &a, const Ray &r, int mbase, int npass
           cc = (ox * ox + oy * oy + oz * oz) - 1.0;
         }
         const double aa = dx * dx + dy * dy + dz * dz;
-        PT_SPHERE_ROOTS(slot);
+        // (hoisted cc is a scalar: a wave-uniform branch, no lane-wise test.  A wave that is not `fast` keeps the old code.)
+        const bool inside = HOISTED && g.fast && pt_origin_inside(cc);
+        PT_SPHERE_ROOTS_IN(slot, inside);
       } else {
         pt_kdouble m = PT_KD(a.recs[slot].invm);
         const double dz = r.d.x * m[8] + r.d.y * m[9] + r.d.z * m[10];
@@ -958,11 +960,12 @@ struct Hit4 {
 };
 
 // shapes.py:103-121 for one ray given the object-space ray (PT_SPHERE_ROOTS as a function)
+// inside (wave-uniform): the shape's hoisted c says the camera is well inside it (pt_origin_inside) -- no first-root division
 template <bool ANYHIT>
-PT_DEV void sphere_roots1(const PtKArgs &a, int slot, bool active, double tmin, double ox, double oy, double oz, double dx,
-                          double dy, double dz, double aa, double cc, double &best_t, int &best) {
+PT_DEV void sphere_roots1(const PtKArgs &a, int slot, bool active, bool inside, double tmin, double ox, double oy, double oz,
+                          double dx, double dy, double dz, double aa, double cc, double &best_t, int &best) {
   const double tmax = INFINITY;
-  PT_SPHERE_ROOTS(slot);
+  PT_SPHERE_ROOTS_IN(slot, inside);
 }
 
 // SLDS (small worlds, Flat): the shapes' records (128 B + 256 B each) are staged in LDS by the workgroup and shading
@@ -1192,23 +1195,25 @@ __global__ __launch_bounds__(PT_BLOCK) __attribute__((amdgpu_waves_per_eu(PT_TIL
             if (slot < nd && fast) {
               pt_kdouble h = PT_KD(&a.hoist_diag[slot]);
               const double s0 = h[0], s1 = h[1], s2 = h[2], ox = h[3], oy = h[4], oz = h[5], cc = h[6];
+              const bool inside = pt_origin_inside(cc);  // (cc is a scalar: a wave-uniform branch; here the wave is `fast`)
 #pragma unroll
               for (int k = 0; k < NPX; ++k) {
                 const double dx = dir[k].x * s0, dy = dir[k].y * s1, dz = dir[k].z * s2;
                 const double aa = dx * dx + dy * dy + dz * dz;
-                sphere_roots1<ANYHIT>(a, slot, act[k], tmin, ox, oy, oz, dx, dy, dz, aa, cc, h4.best_t[k], h4.best[k]);
+                sphere_roots1<ANYHIT>(a, slot, act[k], inside, tmin, ox, oy, oz, dx, dy, dz, aa, cc, h4.best_t[k], h4.best[k]);
               }
             } else {
               pt_kdouble m = PT_KD(a.recs[slot].invm);
               pt_kdouble h = PT_KD(&a.hoist[slot]);
               const double ox = h[0], oy = h[1], oz = h[2], cc = h[3];
+              const bool inside = fast && pt_origin_inside(cc);  // (a wave that is not `fast` keeps the old code)
 #pragma unroll
               for (int k = 0; k < NPX; ++k) {
                 const double dx = dir[k].x * m[0] + dir[k].y * m[1] + dir[k].z * m[2];
                 const double dy = dir[k].x * m[4] + dir[k].y * m[5] + dir[k].z * m[6];
                 const double dz = dir[k].x * m[8] + dir[k].y * m[9] + dir[k].z * m[10];
                 const double aa = dx * dx + dy * dy + dz * dz;
-                sphere_roots1<ANYHIT>(a, slot, act[k], tmin, ox, oy, oz, dx, dy, dz, aa, cc, h4.best_t[k], h4.best[k]);
+                sphere_roots1<ANYHIT>(a, slot, act[k], inside, tmin, ox, oy, oz, dx, dy, dz, aa, cc, h4.best_t[k], h4.best[k]);
               }
             }
           } else {

@@ -19,6 +19,16 @@ nw = ((ds.stats().grid + 63) // 64) * 4  # sampled workgroups only
 if ds.stats().kernel == abi.KERNEL_TILE4:  # 16x16 tiles, one per wave; every 16th workgroup reports
     names = ["prologue", "cone", "cull", "dome tile", "four rays", "query", "shade", "store"]
     nw = ((ds.stats().grid + 15) // 16) * 4
+# a -DPT_DEBUG_HEAVY=<cycles> build sums the waves above that many cycles only, of every 4th workgroup: give the same number as the
+# second argument and the sums are divided by the number of THOSE waves (from the per-wave log of the same frame)
+HEAVY = int(sys.argv[2]) if len(sys.argv) > 2 else 0
+if HEAVY and ds.stats().kernel == abi.KERNEL_TILE4:
+    n = ds.stats().grid * 4
+    buf = (C.c_ulonglong * (8 * n))()
+    _lib.lib().pt_debug_read_unitlog(buf, n)
+    tot = np.frombuffer(buf, dtype=np.uint64).reshape(n, 8)[:, 0]
+    nw = max(1, int(((((np.arange(n) // 4) & 3) == 0) & (tot > HEAVY)).sum()))
+    print(f"waves above {HEAVY} cycles among those of every 4th workgroup: {nw}")
 print("kernel ms", ds.stats().kernel_ms, "sampled waves", nw, "tiles/wave", 14400 / (ds.stats().grid * 4))
 for n, v in zip(names, t):
     print(f"{n:26s} {v / nw:10.0f} cycles/wave  {100 * v / t.sum():5.1f} %")
