@@ -1,18 +1,10 @@
-"""Loader for libptrace_gather.so (include/ptrace_gather.h: the mean radiance over the hemisphere of batches of surface points).
-
-Like the other add-ons the library links to nothing of the project's and loads nothing itself: it is handed the scene's
-argument block (``_rays_lib.scene_args``; all six libraries come from one build of the tree, and each refuses a block of
-another size).  Fails loudly: there is no CPU fallback."""
+"""Loader for libptrace_gather.so (include/ptrace_gather.h: the mean radiance over the hemisphere of batches of surface
+points): its table for ``_addon.Addon``, and its params structure."""
 from __future__ import annotations
 
 import ctypes as C
-import os
 
-from . import _lib
-
-# PTRACE_GATHER_LIB: an alternative build of the same C-ABI library (mutation runs; as PTRACE_RADIANCE_LIB for libptrace_radiance.so)
-_LIB_PATH = os.environ.get("PTRACE_GATHER_LIB") or os.path.join(os.path.dirname(os.path.abspath(__file__)), "libptrace_gather.so")
-_gat = None
+from . import _addon
 
 # every symbol include/ptrace_gather.h declares
 EXPORTS = ("pt_rays_gather_version", "pt_rays_gather_args_bytes", "pt_rays_gather_last_error", "pt_rays_gather_bytes",
@@ -28,61 +20,24 @@ class GatherParams(C.Structure):
 
 
 def params(samples, num_of_rays, max_depth, rr_limit, depth0, init_state, init_seq, background) -> GatherParams:
-    bg = (background.r, background.g, background.b) if hasattr(background, "r") else tuple(background)
-    if len(bg) != 3:
-        raise ValueError("background must be a Color or three numbers")
-
-    def c_int(x, what):
-        x = int(x)
-        if not -2 ** 31 <= x < 2 ** 31:
-            raise ValueError(f"{what}={x} does not fit a C int")
-        return x
-
+    bg, c_int = _addon.background3(background), _addon.c_int
     mask = 2 ** 64 - 1  # (every value of the 64-bit range is legal and wraps, as pcg_streams has it)
     return GatherParams(c_int(samples, "samples"), c_int(num_of_rays, "num_of_rays"), c_int(max_depth, "max_depth"),
-                        c_int(rr_limit, "russian_roulette_limit"), c_int(depth0, "depth"), int(init_state) & mask, int(init_seq) & mask,
-                        (C.c_double * 3)(*[float(x) for x in bg]))
+                        c_int(rr_limit, "russian_roulette_limit"), c_int(depth0, "depth"), int(init_state) & mask, int(init_seq) & mask, bg)
 
 
-def lib_path() -> str:
-    return _LIB_PATH
-
-
-def lib():
-    """The loaded library; raises if it has not been built (``python -m pytracer_amd.build``)."""
-    global _gat
-    if _gat is None:
-        if not os.path.exists(_LIB_PATH):
-            raise ImportError(f"{_LIB_PATH} is missing: the HIP extension has not been built. "
-                              "Run `python -m pytracer_amd.build` (needs hipcc); there is no CPU fallback.")
-        _lib.lib()  # first: ONE HIP runtime per process, the one libptrace.so bound to (shared with torch unless standalone())
-        L = C.CDLL(_LIB_PATH)
-        vp, ll, sz, i = C.c_void_p, C.c_longlong, C.c_size_t, C.c_int
-        pp = C.POINTER(GatherParams)
-        L.pt_rays_gather_version.restype, L.pt_rays_gather_version.argtypes = i, []
-        L.pt_rays_gather_args_bytes.restype, L.pt_rays_gather_args_bytes.argtypes = sz, []
-        L.pt_rays_gather_last_error.restype, L.pt_rays_gather_last_error.argtypes = i, [C.c_char_p, sz]
-        L.pt_rays_gather_bytes.restype, L.pt_rays_gather_bytes.argtypes = sz, [ll, i]
-        L.pt_rays_gather_plane_offset.restype, L.pt_rays_gather_plane_offset.argtypes = ll, [ll, i, i, i]
-        L.pt_rays_gather_workspace_bytes.restype, L.pt_rays_gather_workspace_bytes.argtypes = sz, [i, ll, i, i, i, i]
-        L.pt_rays_gather_device.restype = i
-        L.pt_rays_gather_device.argtypes = [i, vp, sz, vp, vp, vp, vp, ll, pp, i, vp, sz, vp, sz, vp]
-        L.pt_rays_gather.restype = i
-        L.pt_rays_gather.argtypes = [i, vp, sz, vp, vp, vp, vp, ll, pp, i, vp, sz]
-        ver = int(L.pt_rays_gather_version())
-        if ver >> 16 != ABI_MAJOR or (ver & 0xFFFF) < ABI_MINOR:
-            raise ImportError(f"{_LIB_PATH} implements ray-library interface {ver >> 16}.{ver & 0xFFFF}; this package needs "
-                              f"{ABI_MAJOR}.{ABI_MINOR} or later: rebuild with `python -m pytracer_amd.build --force`")
-        _gat = L
-    return _gat
-
-
-def last_error() -> str:
-    buf = C.create_string_buffer(512)
-    lib().pt_rays_gather_last_error(buf, 512)
-    return buf.value.decode("utf-8", "replace")
-
-
-def check(rc: int) -> None:
-    if rc != 0:
-        raise _lib.PtraceError(rc, last_error())
+_vp, _ll, _sz, _i, _pp = C.c_void_p, C.c_longlong, C.c_size_t, C.c_int, C.POINTER(GatherParams)
+_SIGNATURES = (
+    ("pt_rays_gather_version", _i, []),
+    ("pt_rays_gather_args_bytes", _sz, []),
+    ("pt_rays_gather_last_error", _i, [C.c_char_p, _sz]),
+    ("pt_rays_gather_bytes", _sz, [_ll, _i]),
+    ("pt_rays_gather_plane_offset", _ll, [_ll, _i, _i, _i]),
+    ("pt_rays_gather_workspace_bytes", _sz, [_i, _ll, _i, _i, _i, _i]),
+    ("pt_rays_gather_device", _i, [_i, _vp, _sz, _vp, _vp, _vp, _vp, _ll, _pp, _i, _vp, _sz, _vp, _sz, _vp]),
+    ("pt_rays_gather", _i, [_i, _vp, _sz, _vp, _vp, _vp, _vp, _ll, _pp, _i, _vp, _sz]),
+)
+# PTRACE_GATHER_LIB: an alternative build of the same C-ABI library
+_ADDON = _addon.Addon("libptrace_gather.so", "PTRACE_GATHER_LIB", "ray-library interface", "pt_rays_gather_version",
+                      "pt_rays_gather_last_error", ABI_MAJOR, ABI_MINOR, _SIGNATURES)
+lib, lib_path, last_error, check = _ADDON.lib, _ADDON.lib_path, _ADDON.last_error, _ADDON.check

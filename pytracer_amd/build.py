@@ -1,25 +1,19 @@
-"""Build recipe for libptrace.so and its add-ons libptrace_rays.so, libptrace_surface.so, libptrace_scatter.so,
-libptrace_radiance.so and libptrace_gather.so (HIP, gfx950 only).
+"""Build recipe for libptrace.so and its add-on libraries (HIP, gfx950 only).
 
 ``hipcc --offload-arch=gfx950 -O3 -ffp-contract=off``: the parity kernels must not fuse a*b+c (the
-reference is Python: every operation rounds), and nothing enables fast-math.  The library is built
-in-tree (``pytracer_amd/libptrace.so``) so it travels to the GPU box with the repository snapshot.
+reference is Python: every operation rounds), and nothing enables fast-math.  The libraries are built
+in-tree (``pytracer_amd/lib*.so``) so they travel to the GPU box with the repository snapshot.
 
-``libptrace_rays.so`` (csrc/ptrace_rays.hip, include/ptrace_rays.h: ray batches) is a second translation unit and a second
-shared object ON PURPOSE: ``code_hash()`` of libptrace.so is what ties every ``profiles/pmc_*.json`` to the kernels it
-measured, and a kernel added to ptrace.hip would change it.  Same flags, its own ``-cuid``; built after libptrace.so.
+Every add-on is a translation unit and a shared object of its own ON PURPOSE: ``code_hash()`` of libptrace.so is what ties
+every ``profiles/pmc_*.json`` to the kernels it measured, and a kernel added to ptrace.hip would change it; the exported
+symbols of every add-on already released are pinned to its interface in the same way.  Same flags, its own ``-cuid``; built
+after libptrace.so, in the order of ``ADDONS`` (csrc/ptrace_NAME.hip, include/ptrace_NAME.h -> libptrace_NAME.so):
 
-``libptrace_surface.so`` (csrc/ptrace_surface.hip, include/ptrace_surface.h: materials and point-light shading of hit
-records) is the third, for the same reason once more: the exported symbols of libptrace_rays.so are its interface 1.0's.
-
-``libptrace_scatter.so`` (csrc/ptrace_scatter.hip, include/ptrace_scatter.h: BRDF.scatter_ray and the Russian roulette for hit
-records) is the fourth: the exported symbols of libptrace_surface.so are pinned to its eleven as well.
-
-``libptrace_radiance.so`` (csrc/ptrace_radiance.hip, include/ptrace_radiance.h: the whole ``PathTracer`` recursion for ray
-batches) is the fifth: the exported symbols of libptrace_scatter.so are pinned to its seven.
-
-``libptrace_gather.so`` (csrc/ptrace_gather.hip, include/ptrace_gather.h: the mean radiance over the hemisphere of batches of
-surface points) is the sixth: the exported symbols of libptrace_radiance.so are pinned to its eight.
+* rays: closest-hit and any-hit queries for a caller's own rays
+* surface: materials and point-light shading of hit records
+* scatter: BRDF.scatter_ray and the Russian roulette for hit records
+* radiance: the whole ``PathTracer`` recursion for ray batches
+* gather: the mean radiance over the hemisphere of batches of surface points
 """
 from __future__ import annotations
 
@@ -32,38 +26,21 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(HERE, "libptrace.so")
 SOURCES = ["ptrace.hip"]
-RAYS_LIB = os.path.join(HERE, "libptrace_rays.so")
-RAYS_SOURCES = ["ptrace_rays.hip"]
-SURFACE_LIB = os.path.join(HERE, "libptrace_surface.so")
-SURFACE_SOURCES = ["ptrace_surface.hip"]
-SCATTER_LIB = os.path.join(HERE, "libptrace_scatter.so")
-SCATTER_SOURCES = ["ptrace_scatter.hip"]
-RADIANCE_LIB = os.path.join(HERE, "libptrace_radiance.so")
-RADIANCE_SOURCES = ["ptrace_radiance.hip"]
-GATHER_LIB = os.path.join(HERE, "libptrace_gather.so")
-GATHER_SOURCES = ["ptrace_gather.hip"]
-# every file the one translation unit includes: all of csrc/ (tests/test_host.py checks this list against the #include lines)
-DEPS = sorted(f for f in os.listdir(CSRC) if f.endswith((".hip", ".h"))) + [os.path.join("..", "..", "include", "ptrace.h"),
-                                                                            os.path.join("..", "..", "include", "ptrace_debug.h"),
-                                                                            os.path.join("..", "..", "include", "ptrace_rays.h"),
-                                                                            os.path.join("..", "..", "include", "ptrace_surface.h"),
-                                                                            os.path.join("..", "..", "include", "ptrace_scatter.h"),
-                                                                            os.path.join("..", "..", "include", "ptrace_radiance.h"),
-                                                                            os.path.join("..", "..", "include", "ptrace_gather.h")]
 FLAGS = ["--offload-arch=gfx950", "-O3", "-ffp-contract=off", "-fno-fast-math", "-std=c++17", "-fPIC",
          "-shared", "-Wall", "-Wno-unused-function", "-Wno-pass-failed",
          # a fixed compilation-unit id: by default clang derives it from the command line (paths included), which would make
          # code_hash() depend on WHERE the library was built
          "-cuid=libptrace"]
-RAYS_FLAGS = FLAGS[:-1] + ["-cuid=libptrace_rays"]
-SURFACE_FLAGS = FLAGS[:-1] + ["-cuid=libptrace_surface"]
-SCATTER_FLAGS = FLAGS[:-1] + ["-cuid=libptrace_scatter"]
-RADIANCE_FLAGS = FLAGS[:-1] + ["-cuid=libptrace_radiance"]
-GATHER_FLAGS = FLAGS[:-1] + ["-cuid=libptrace_gather"]
+# the add-ons, in build order: name -> (sources, library, cuid)
+ADDONS = {name: ([f"ptrace_{name}.hip"], os.path.join(HERE, f"libptrace_{name}.so"), f"libptrace_{name}")
+          for name in ("rays", "surface", "scatter", "radiance", "gather")}
 # every library the recipe makes, in build order: what build() and needs_build() walk
-TARGETS = ((FLAGS, LIB, SOURCES), (RAYS_FLAGS, RAYS_LIB, RAYS_SOURCES), (SURFACE_FLAGS, SURFACE_LIB, SURFACE_SOURCES),
-           (SCATTER_FLAGS, SCATTER_LIB, SCATTER_SOURCES), (RADIANCE_FLAGS, RADIANCE_LIB, RADIANCE_SOURCES),
-           (GATHER_FLAGS, GATHER_LIB, GATHER_SOURCES))
+TARGETS = ((FLAGS, LIB, SOURCES),) + tuple((FLAGS[:-1] + [f"-cuid={cuid}"], lib, sources) for sources, lib, cuid in ADDONS.values())
+(_, (RAYS_FLAGS, RAYS_LIB, RAYS_SOURCES), (SURFACE_FLAGS, SURFACE_LIB, SURFACE_SOURCES), (SCATTER_FLAGS, SCATTER_LIB, SCATTER_SOURCES),
+ (RADIANCE_FLAGS, RADIANCE_LIB, RADIANCE_SOURCES), (GATHER_FLAGS, GATHER_LIB, GATHER_SOURCES)) = TARGETS  # (the rows by name)
+# every file the translation units include: all of csrc/ (tests/test_host.py checks this list against the #include lines)
+DEPS = sorted(f for f in os.listdir(CSRC) if f.endswith((".hip", ".h"))) + [
+    os.path.join("..", "..", "include", h) for h in ["ptrace.h", "ptrace_debug.h"] + [f"ptrace_{name}.h" for name in ADDONS]]
 
 
 def code_hash(lib: str = LIB) -> str:

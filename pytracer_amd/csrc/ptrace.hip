@@ -24,6 +24,7 @@
 #include "pt_scene_build.h"
 #include "pt_hits_plan.h"
 #include "pt_post.h"
+#include "pt_host_common.h"  // g_err, fail, HIP_TRY, copy_last_error, device_ok
 
 // major << 16 | minor.  The minor grows whenever a struct of include/ptrace.h grows or an entry point is added (minor 2:
 // pt_stats gained `kernel` + `_reserved`, pt_scene_clone / pt_image_sparse_* arrived; minor 3: PT_PCG_SEQ accepted for
@@ -38,24 +39,6 @@
 // CALLER's choice: the HIP runtime reads the variable when it initialises, and a library that edited the process environment
 // at load time would change HIP for every other user of the runtime in the process.  pytracer_amd.prefer_device_kernargs(),
 // the `render` command and bench.py set it before their first HIP call; pt_device_kernargs() reports what is in effect.)
-
-static thread_local char g_err[512] = "";
-
-static int fail(int code, const char *fmt, ...) {
-  va_list ap;
-  va_start(ap, fmt);
-  vsnprintf(g_err, sizeof g_err, fmt, ap);
-  va_end(ap);
-  return code;
-}
-
-#define HIP_TRY(expr)                                                                        \
-  do {                                                                                       \
-    hipError_t _e = (expr);                                                                  \
-    if (_e != hipSuccess)                                                                    \
-      return fail(PT_ERR_HIP, "%s failed: %s (%s:%d)", #expr, hipGetErrorString(_e), __FILE__, \
-                  __LINE__);                                                                 \
-  } while (0)
 
 // What pt_scene_upload makes of a scene and no launch changes: the tables in HBM and every scalar of the analysis.  One
 // block per uploaded scene, shared by all its handles (pt_scene_clone); the last handle to be freed frees it.
@@ -151,15 +134,7 @@ extern "C" int pt_device_kernargs(void) {
   return v && atoi(v) != 0 ? 1 : 0;
 }
 
-extern "C" int pt_last_error(char *buf, size_t n) {
-  const size_t len = strlen(g_err);
-  if (buf && n) {
-    const size_t c = std::min(len, n - 1);
-    memcpy(buf, g_err, c);
-    buf[c] = 0;
-  }
-  return (int)len;
-}
+extern "C" int pt_last_error(char *buf, size_t n) { return copy_last_error(buf, n); }
 
 extern "C" int pt_device_count(void) {
   int n = 0;
@@ -1124,13 +1099,6 @@ extern "C" int pt_host_free(void *p) {
 // ---- device memory and streams for callers WITHOUT a GPU framework of their own (ABI 1.5) ----
 // The `render` command leaves its frame in HBM (pt_render_device) and post-processes it there (pt_image_*): with these it needs
 // no torch for the buffer.  Thin and error-coded; a caller that owns device tensors keeps passing their pointers.
-static int device_ok(int device) {
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return fail(PT_ERR_NODEVICE, "no HIP device visible");
-  if (device < 0 || device >= ndev) return fail(PT_ERR_INVALID, "device %d out of range (%d visible)", device, ndev);
-  return PT_OK;
-}
-
 extern "C" int pt_device_alloc(int device, size_t bytes, void **out) {
   if (!out) return fail(PT_ERR_INVALID, "null output pointer");
   *out = nullptr;
@@ -1268,12 +1236,12 @@ static bool is_device_ptr(const void *p) {
 
 // Image and output buffers may be device memory (a frame left in HBM by pt_render_device) or plain host
 // memory (an HdrImage's array); host buffers are staged through a temporary device copy.
-struct Staged {
+struct StagedImage {
   void *dev = nullptr;
   void *host = nullptr;
   size_t bytes = 0;
   bool owned = false;
-  ~Staged() {
+  ~StagedImage() {
     if (owned && dev) (void)hipFree(dev);
   }
   int in(const void *p, size_t n, bool copy_in, hipStream_t st) {
@@ -1304,7 +1272,7 @@ extern "C" int pt_image_pack_pfm(int device, const void *img, int fmt, int width
   if (!out) return fail(PT_ERR_INVALID, "null output");
   hipStream_t st = (hipStream_t)stream;
   const long long n = (long long)width * height * 3;
-  Staged si, so;
+  StagedImage si, so;
   if ((rc = si.in(img, (size_t)n * (fmt == PT_OUT_F32 ? 4 : 8), true, st))) return rc;
   if ((rc = so.in(out, (size_t)n * 4, false, st))) return rc;
   hipLaunchKernelGGL(pt_post_pfm_kernel, dim3(post_grid(n)), dim3(256), 0, st, si.dev, fmt == PT_OUT_F32 ? 1 : 0,
@@ -1418,7 +1386,7 @@ extern "C" int pt_image_average_luminosity(int device, const void *img, int fmt,
   if (!out) return fail(PT_ERR_INVALID, "null output");
   hipStream_t st = (hipStream_t)stream;
   const long long npix = (long long)width * height;
-  Staged si;
+  StagedImage si;
   if ((rc = si.in(img, (size_t)npix * 3 * (fmt == PT_OUT_F32 ? 4 : 8), true, st))) return rc;
   const int nblocks = (int)((npix + PT_POST_CHUNK - 1) / PT_POST_CHUNK);
   double *partials = nullptr;
@@ -1442,7 +1410,7 @@ extern "C" int pt_image_tonemap(int device, void *img, int fmt, int width, int h
   if (rgb8 && !(gamma > 0.0)) return fail(PT_ERR_INVALID, "gamma must be positive");
   hipStream_t st = (hipStream_t)stream;
   const long long n = (long long)width * height * 3;
-  Staged si, so;
+  StagedImage si, so;
   if ((rc = si.in(img, (size_t)n * (fmt == PT_OUT_F32 ? 4 : 8), true, st))) return rc;
   if (rgb8 && (rc = so.in(rgb8, (size_t)n, false, st))) return rc;
   hipLaunchKernelGGL(pt_post_tonemap_kernel, dim3(post_grid(n)), dim3(256), 0, st, si.dev, fmt == PT_OUT_F32 ? 1 : 0, n,

@@ -10,49 +10,20 @@
 // out, there is no link dependency, nothing is loaded from here.
 #include <hip/hip_runtime.h>
 
-#include <algorithm>
-#include <cstdarg>
-#include <cstdio>
-#include <cstdlib>
-#include <cstring>
-
 #include "../../include/ptrace_gather.h"
 #define PT_QUERY_PARTS_ONLY
 #include "pt_kernels.h"
 #include "pt_gather.h"
+#include "pt_host_common.h"
 
 #define PT_GAT_VERSION ((1 << 16) | 4)
 #define PT_GAT_MAX_N 2147483647LL
-
-static thread_local char g_err[512] = "";
-
-static int fail(int code, const char *fmt, ...) {
-  va_list ap;
-  va_start(ap, fmt);
-  vsnprintf(g_err, sizeof g_err, fmt, ap);
-  va_end(ap);
-  return code;
-}
-
-#define HIP_TRY(expr)                                                                                          \
-  do {                                                                                                         \
-    hipError_t _e = (expr);                                                                                    \
-    if (_e != hipSuccess) return fail(PT_ERR_HIP, "%s failed: %s (%s:%d)", #expr, hipGetErrorString(_e), __FILE__, __LINE__); \
-  } while (0)
 
 extern "C" int pt_rays_gather_version(void) { return PT_GAT_VERSION; }
 
 extern "C" size_t pt_rays_gather_args_bytes(void) { return sizeof(PtKArgs); }
 
-extern "C" int pt_rays_gather_last_error(char *buf, size_t n) {
-  const size_t len = strlen(g_err);
-  if (buf && n) {
-    const size_t c = std::min(len, n - 1);
-    memcpy(buf, g_err, c);
-    buf[c] = 0;
-  }
-  return (int)len;
-}
+extern "C" int pt_rays_gather_last_error(char *buf, size_t n) { return copy_last_error(buf, n); }
 
 // ---- sizes ------------------------------------------------------------------------------------------------------------------
 static bool shape_ok(long long n, int channels) { return n >= 0 && n <= PT_GAT_MAX_N && channels >= 0 && !(channels & ~PT_GATHER_ALL); }
@@ -91,14 +62,7 @@ static int check_args(int device, const void *scene_args, size_t scene_args_byte
   if (!p) return fail(PT_ERR_INVALID, "null pt_gather_params");
   if (int rc = check_params(n, p->samples, p->num_of_rays, p->max_depth, p->depth0)) return rc;
   if (channels < 0 || (channels & ~PT_GATHER_ALL)) return fail(PT_ERR_INVALID, "channel bits %#x: a gather batch has PT_GATHER_COUNT", channels);
-  if (device < 0) return fail(PT_ERR_INVALID, "device %d", device);
-  if (!scene_args) return fail(PT_ERR_INVALID, "null scene argument block");
-  if (scene_args_bytes != sizeof(PtKArgs))
-    return fail(PT_ERR_INVALID, "scene argument block of %zu bytes, this library's has %zu: all libraries must come from one build",
-                scene_args_bytes, sizeof(PtKArgs));
-  const PtKArgs *a = (const PtKArgs *)scene_args;
-  if (!a->cold) return fail(PT_ERR_INVALID, "scene argument block without its device copy (not from pt_scene_kernel_args?)");
-  if (a->n_shapes < 0) return fail(PT_ERR_INVALID, "scene argument block with %d shapes", a->n_shapes);
+  if (int rc = check_scene_block(device, scene_args, scene_args_bytes, PT_BLOCK_SHAPES)) return rc;
   need = pt_rays_gather_bytes(n, channels);
   if (n == 0) return PT_OK;
   if (!points || !normals) return fail(PT_ERR_INVALID, "null record planes (points, normals)");
@@ -107,33 +71,11 @@ static int check_args(int device, const void *scene_args, size_t scene_args_byte
   return PT_OK;
 }
 
-static int device_ok(int device) {
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return fail(PT_ERR_NODEVICE, "no HIP device visible");
-  if (device >= ndev) return fail(PT_ERR_INVALID, "device %d out of range (%d visible)", device, ndev);
-  return PT_OK;
-}
-
 // ---- the launch's shape -------------------------------------------------------------------------------------------------------
-// Lanes the walk's launch keeps resident on `device`: compute units x the workgroups of the kernel one of them holds x 256, no
-// more than the n * K samples need, no more than PTRACE_GATHER_LANES allows.  Always a positive multiple of 256.  (No wave ever
-// waits for another: a grid that is not fully resident is merely dispatched in turns.)
+// lanes the walk's launch keeps resident: no more than the n * K samples need, no more than PTRACE_GATHER_LANES allows
 static int lanes_of(int device, long long total, bool many, unsigned long long &lanes) {
-  int cus = 0, per_cu = 0;
-  HIP_TRY(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, device));
-  if (many)
-    HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, pt_gather_kernel<true>, PT_BLOCK, 0));
-  else
-    HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, pt_gather_kernel<false>, PT_BLOCK, 0));
-  unsigned long long cap = (unsigned long long)std::max(cus, 1) * (unsigned long long)std::max(per_cu, 1) * PT_BLOCK;
-  if (const char *e = getenv("PTRACE_GATHER_LANES")) {
-    char *end = nullptr;
-    const unsigned long long v = strtoull(e, &end, 10);
-    if (end != e && *end == 0) cap = std::min(cap, std::max<unsigned long long>(v / PT_BLOCK, 1) * PT_BLOCK);
-  }
-  const unsigned long long want = ((unsigned long long)std::max<long long>(total, 1) + PT_BLOCK - 1) / PT_BLOCK * PT_BLOCK;
-  lanes = std::min(cap, want);
-  return PT_OK;
+  const void *kernel = many ? (const void *)pt_gather_kernel<true> : (const void *)pt_gather_kernel<false>;
+  return resident_lanes(device, total, kernel, "PTRACE_GATHER_LANES", lanes);
 }
 
 static size_t stacks_of(unsigned long long lanes, const pt_gather_params &p) {
@@ -159,8 +101,7 @@ extern "C" size_t pt_rays_gather_workspace_bytes(int device, long long n, int sa
 static int enqueue(const void *scene_args, const double *points_dev, const double *normals_dev, const int *active_dev,
                    const unsigned long long *seq_dev, long long n, const pt_gather_params &p, int channels, unsigned long long lanes,
                    void *ws_dev, void *out_dev, hipStream_t st) {
-  PtKArgs a;
-  memcpy(&a, scene_args, sizeof a);
+  const PtKArgs a = scene_block(scene_args);
   PtGatK K;
   K.samples = p.samples;
   K.N = p.num_of_rays;
@@ -188,8 +129,7 @@ static int enqueue(const void *scene_args, const double *points_dev, const doubl
                        samples);
   HIP_TRY(hipGetLastError());
   // the mean: behind the walk on the same stream, one lane per record
-  const dim3 mean_grid((unsigned)((n + PT_BLOCK - 1) / PT_BLOCK));
-  hipLaunchKernelGGL(pt_gather_mean_kernel, mean_grid, dim3(PT_BLOCK), 0, st, (const double *)samples, active_dev, n, total, K, out_dev);
+  hipLaunchKernelGGL(pt_gather_mean_kernel, grid_of(n), dim3(PT_BLOCK), 0, st, (const double *)samples, active_dev, n, total, K, out_dev);
   HIP_TRY(hipGetLastError());
   return PT_OK;
 }
@@ -220,11 +160,6 @@ extern "C" int pt_rays_gather_device(int device, const void *scene_args, size_t 
 }
 
 // ---- host form: one device allocation holds the input planes, the workspace and the output -------------------------------------
-struct Staged {
-  char *dev = nullptr;
-  ~Staged() { (void)hipFree(dev); }
-};
-
 extern "C" int pt_rays_gather(int device, const void *scene_args, size_t scene_args_bytes, const double *points_host, const double *normals_host,
                               const int *active_host, const unsigned long long *seq_host, long long n, const pt_gather_params *params,
                               int channels, void *out_host, size_t out_bytes) {
@@ -238,8 +173,7 @@ extern "C" int pt_rays_gather(int device, const void *scene_args, size_t scene_a
   const size_t plane = (size_t)n * 8, ws_b = workspace_of(lanes, n, *params);
   const size_t total = 8 * plane + ws_b + need;  // points 3, normals 3, seq 1, active 1 (int32, padded)
   Staged s;
-  hipError_t e = hipMalloc((void **)&s.dev, total);
-  if (e != hipSuccess) return fail(e == hipErrorOutOfMemory ? PT_ERR_NOMEM : PT_ERR_HIP, "hipMalloc(%zu) failed: %s", total, hipGetErrorString(e));
+  if ((rc = s.alloc(total))) return rc;
   char *points_d = s.dev, *normals_d = points_d + 3 * plane, *seq_d = normals_d + 3 * plane, *act_d = seq_d + plane, *ws_d = act_d + plane,
        *out_d = ws_d + ws_b;
   HIP_TRY(hipMemcpy(points_d, points_host, 3 * plane, hipMemcpyHostToDevice));

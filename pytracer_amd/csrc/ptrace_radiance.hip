@@ -10,49 +10,20 @@
 // the argument block pt_scene_kernel_args (ptrace.h, ABI 1.7) hands out, there is no link dependency, nothing is loaded from here.
 #include <hip/hip_runtime.h>
 
-#include <algorithm>
-#include <cstdarg>
-#include <cstdio>
-#include <cstdlib>
-#include <cstring>
-
 #include "../../include/ptrace_radiance.h"
 #define PT_QUERY_PARTS_ONLY
 #include "pt_kernels.h"
 #include "pt_radiance.h"
+#include "pt_host_common.h"
 
 #define PT_RAD_VERSION ((1 << 16) | 3)
 #define PT_RAD_MAX_N 2147483647LL
-
-static thread_local char g_err[512] = "";
-
-static int fail(int code, const char *fmt, ...) {
-  va_list ap;
-  va_start(ap, fmt);
-  vsnprintf(g_err, sizeof g_err, fmt, ap);
-  va_end(ap);
-  return code;
-}
-
-#define HIP_TRY(expr)                                                                                          \
-  do {                                                                                                         \
-    hipError_t _e = (expr);                                                                                    \
-    if (_e != hipSuccess) return fail(PT_ERR_HIP, "%s failed: %s (%s:%d)", #expr, hipGetErrorString(_e), __FILE__, __LINE__); \
-  } while (0)
 
 extern "C" int pt_rays_radiance_version(void) { return PT_RAD_VERSION; }
 
 extern "C" size_t pt_rays_radiance_args_bytes(void) { return sizeof(PtKArgs); }
 
-extern "C" int pt_rays_radiance_last_error(char *buf, size_t n) {
-  const size_t len = strlen(g_err);
-  if (buf && n) {
-    const size_t c = std::min(len, n - 1);
-    memcpy(buf, g_err, c);
-    buf[c] = 0;
-  }
-  return (int)len;
-}
+extern "C" int pt_rays_radiance_last_error(char *buf, size_t n) { return copy_last_error(buf, n); }
 
 // ---- sizes ------------------------------------------------------------------------------------------------------------------
 static bool shape_ok(long long n, int channels) { return n >= 0 && n <= PT_RAD_MAX_N && channels >= 0 && !(channels & ~PT_RAD_ALL); }
@@ -92,14 +63,7 @@ static int check_args(int device, const void *scene_args, size_t scene_args_byte
   if (int rc = check_params(n, p->num_of_rays, p->max_depth, p->depth0)) return rc;
   if (channels < 0 || (channels & ~PT_RAD_ALL))
     return fail(PT_ERR_INVALID, "channel bits %#x: a radiance batch has PT_RAD_PCG | PT_RAD_COUNT", channels);
-  if (device < 0) return fail(PT_ERR_INVALID, "device %d", device);
-  if (!scene_args) return fail(PT_ERR_INVALID, "null scene argument block");
-  if (scene_args_bytes != sizeof(PtKArgs))
-    return fail(PT_ERR_INVALID, "scene argument block of %zu bytes, this library's has %zu: all libraries must come from one build",
-                scene_args_bytes, sizeof(PtKArgs));
-  const PtKArgs *a = (const PtKArgs *)scene_args;
-  if (!a->cold) return fail(PT_ERR_INVALID, "scene argument block without its device copy (not from pt_scene_kernel_args?)");
-  if (a->n_shapes < 0) return fail(PT_ERR_INVALID, "scene argument block with %d shapes", a->n_shapes);
+  if (int rc = check_scene_block(device, scene_args, scene_args_bytes, PT_BLOCK_SHAPES)) return rc;
   need = pt_rays_radiance_bytes(n, channels);
   if (n == 0) return PT_OK;
   if (!rays) return fail(PT_ERR_INVALID, "null ray planes");
@@ -109,32 +73,11 @@ static int check_args(int device, const void *scene_args, size_t scene_args_byte
   return PT_OK;
 }
 
-static int device_ok(int device) {
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return fail(PT_ERR_NODEVICE, "no HIP device visible");
-  if (device >= ndev) return fail(PT_ERR_INVALID, "device %d out of range (%d visible)", device, ndev);
-  return PT_OK;
-}
-
 // ---- the launch's shape -------------------------------------------------------------------------------------------------------
-// Lanes one launch keeps resident on `device`: compute units x the workgroups of this kernel one of them holds x 256, no more
-// than the batch needs, no more than PTRACE_RADIANCE_LANES allows.  Always a positive multiple of 256.
+// lanes one launch keeps resident: no more than the batch needs, no more than PTRACE_RADIANCE_LANES allows
 static int lanes_of(int device, long long n, bool many, unsigned long long &lanes) {
-  int cus = 0, per_cu = 0;
-  HIP_TRY(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, device));
-  if (many)
-    HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, pt_radiance_kernel<true>, PT_BLOCK, 0));
-  else
-    HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, pt_radiance_kernel<false>, PT_BLOCK, 0));
-  unsigned long long cap = (unsigned long long)std::max(cus, 1) * (unsigned long long)std::max(per_cu, 1) * PT_BLOCK;
-  if (const char *e = getenv("PTRACE_RADIANCE_LANES")) {
-    char *end = nullptr;
-    const unsigned long long v = strtoull(e, &end, 10);
-    if (end != e && *end == 0) cap = std::min(cap, std::max<unsigned long long>(v / PT_BLOCK, 1) * PT_BLOCK);
-  }
-  const unsigned long long want = ((unsigned long long)std::max<long long>(n, 1) + PT_BLOCK - 1) / PT_BLOCK * PT_BLOCK;
-  lanes = std::min(cap, want);
-  return PT_OK;
+  const void *kernel = many ? (const void *)pt_radiance_kernel<true> : (const void *)pt_radiance_kernel<false>;
+  return resident_lanes(device, n, kernel, "PTRACE_RADIANCE_LANES", lanes);
 }
 
 static size_t workspace_of(unsigned long long lanes, const pt_radiance_params &p) {
@@ -156,8 +99,7 @@ extern "C" size_t pt_rays_radiance_workspace_bytes(int device, long long n, int 
 static int enqueue(const void *scene_args, const double *rays_dev, const unsigned long long *state_dev, const unsigned long long *inc_dev,
                    long long n, const pt_radiance_params &p, int channels, unsigned long long lanes, void *ws_dev, void *out_dev,
                    hipStream_t st) {
-  PtKArgs a;
-  memcpy(&a, scene_args, sizeof a);
+  const PtKArgs a = scene_block(scene_args);
   PtRadK K;
   K.N = p.num_of_rays;
   const long long levels = (long long)p.max_depth - p.depth0;
@@ -201,11 +143,6 @@ extern "C" int pt_rays_radiance_device(int device, const void *scene_args, size_
 }
 
 // ---- host form: one device allocation holds the input planes, the workspace and the output -------------------------------------
-struct Staged {
-  char *dev = nullptr;
-  ~Staged() { (void)hipFree(dev); }
-};
-
 extern "C" int pt_rays_radiance(int device, const void *scene_args, size_t scene_args_bytes, const double *rays_host,
                                 const unsigned long long *pcg_state_host, const unsigned long long *pcg_inc_host, long long n,
                                 const pt_radiance_params *params, int channels, void *out_host, size_t out_bytes) {
@@ -219,8 +156,7 @@ extern "C" int pt_rays_radiance(int device, const void *scene_args, size_t scene
   const size_t plane = (size_t)n * 8, ws_b = workspace_of(lanes, *params);
   const size_t total = 10 * plane + ws_b + need;
   Staged s;
-  hipError_t e = hipMalloc((void **)&s.dev, total);
-  if (e != hipSuccess) return fail(e == hipErrorOutOfMemory ? PT_ERR_NOMEM : PT_ERR_HIP, "hipMalloc(%zu) failed: %s", total, hipGetErrorString(e));
+  if ((rc = s.alloc(total))) return rc;
   char *rays_d = s.dev, *state_d = rays_d + 8 * plane, *inc_d = state_d + plane, *ws_d = inc_d + plane, *out_d = ws_d + ws_b;
   HIP_TRY(hipMemcpy(rays_d, rays_host, 8 * plane, hipMemcpyHostToDevice));
   HIP_TRY(hipMemcpy(state_d, pcg_state_host, plane, hipMemcpyHostToDevice));

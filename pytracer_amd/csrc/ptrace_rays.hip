@@ -11,14 +11,10 @@
 // the two, nothing is loaded from here.
 #include <hip/hip_runtime.h>
 
-#include <algorithm>
-#include <cstdarg>
-#include <cstdio>
-#include <cstring>
-
 #include "../../include/ptrace_rays.h"
 #define PT_QUERY_PARTS_ONLY
 #include "pt_kernels.h"
+#include "pt_host_common.h"
 
 #define PT_RAYS_VERSION ((1 << 16) | 1)  // 1.1: the block also feeds the surface queries (include/ptrace_surface.h)
 #define PT_RAYS_CHANNELS (PT_HIT_T | PT_HIT_POINT | PT_HIT_NORMAL | PT_HIT_UV)
@@ -96,35 +92,11 @@ __global__ __launch_bounds__(PT_BLOCK) void pt_rays_kernel(const PtKArgs a, cons
   }
 }
 
-static thread_local char g_err[512] = "";
-
-static int fail(int code, const char *fmt, ...) {
-  va_list ap;
-  va_start(ap, fmt);
-  vsnprintf(g_err, sizeof g_err, fmt, ap);
-  va_end(ap);
-  return code;
-}
-
-#define HIP_TRY(expr)                                                                                          \
-  do {                                                                                                         \
-    hipError_t _e = (expr);                                                                                    \
-    if (_e != hipSuccess) return fail(PT_ERR_HIP, "%s failed: %s (%s:%d)", #expr, hipGetErrorString(_e), __FILE__, __LINE__); \
-  } while (0)
-
 extern "C" int pt_rays_version(void) { return PT_RAYS_VERSION; }
 
 extern "C" size_t pt_rays_args_bytes(void) { return sizeof(PtKArgs); }
 
-extern "C" int pt_rays_last_error(char *buf, size_t n) {
-  const size_t len = strlen(g_err);
-  if (buf && n) {
-    const size_t c = std::min(len, n - 1);
-    memcpy(buf, g_err, c);
-    buf[c] = 0;
-  }
-  return (int)len;
-}
+extern "C" int pt_rays_last_error(char *buf, size_t n) { return copy_last_error(buf, n); }
 
 static int planes_of(int channel) {
   switch (channel) {
@@ -170,12 +142,7 @@ static int check_args(int device, const void *scene_args, size_t scene_args_byte
   if (channels < 0 || (channels & ~PT_RAYS_CHANNELS))
     return fail(PT_ERR_INVALID, "channel bits %#x: a ray batch has PT_HIT_T | PT_HIT_POINT | PT_HIT_NORMAL | PT_HIT_UV", channels);
   if (anyhit && channels != 0) return fail(PT_ERR_INVALID, "any-hit writes the blocked / free plane only: channels must be 0, not %#x", channels);
-  if (device < 0) return fail(PT_ERR_INVALID, "device %d", device);
-  if (!scene_args) return fail(PT_ERR_INVALID, "null scene argument block");
-  if (scene_args_bytes != sizeof(PtKArgs))
-    return fail(PT_ERR_INVALID, "scene argument block of %zu bytes, this library's has %zu: both libraries must come from one build",
-                scene_args_bytes, sizeof(PtKArgs));
-  if (!((const PtKArgs *)scene_args)->cold) return fail(PT_ERR_INVALID, "scene argument block without its device copy (not from pt_scene_kernel_args?)");
+  if (int rc = check_scene_block(device, scene_args, scene_args_bytes, 0)) return rc;
   need = pt_rays_bytes(n, channels, anyhit);
   if (n == 0) return PT_OK;
   if (!rays || !out) return fail(PT_ERR_INVALID, "null ray or output buffer");
@@ -183,17 +150,9 @@ static int check_args(int device, const void *scene_args, size_t scene_args_byte
   return PT_OK;
 }
 
-static int device_ok(int device) {
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return fail(PT_ERR_NODEVICE, "no HIP device visible");
-  if (device >= ndev) return fail(PT_ERR_INVALID, "device %d out of range (%d visible)", device, ndev);
-  return PT_OK;
-}
-
 static int enqueue(const void *scene_args, const double *rays_dev, long long n, int channels, int anyhit, void *out_dev, hipStream_t st) {
-  PtKArgs a;
-  memcpy(&a, scene_args, sizeof a);
-  const dim3 grid((unsigned)((n + PT_BLOCK - 1) / PT_BLOCK));
+  const PtKArgs a = scene_block(scene_args);
+  const dim3 grid = grid_of(n);
   if (anyhit)
     hipLaunchKernelGGL(pt_rays_kernel<true>, grid, dim3(PT_BLOCK), 0, st, a, rays_dev, n, channels, out_dev);
   else
@@ -222,22 +181,14 @@ extern "C" int pt_rays_trace(int device, const void *scene_args, size_t scene_ar
   if ((rc = device_ok(device))) return rc;
   HIP_TRY(hipSetDevice(device));
   const size_t ray_bytes = (size_t)n * 8 * sizeof(double);
-  double *rd = nullptr;
-  void *od = nullptr;
-  hipError_t e = hipMalloc((void **)&rd, ray_bytes);
-  if (e == hipSuccess) e = hipMalloc(&od, need);
-  if (e != hipSuccess) {
-    (void)hipFree(rd);
-    return fail(e == hipErrorOutOfMemory ? PT_ERR_NOMEM : PT_ERR_HIP, "hipMalloc(%zu + %zu) failed: %s", ray_bytes, need, hipGetErrorString(e));
-  }
-  e = hipMemcpy(rd, rays_host, ray_bytes, hipMemcpyHostToDevice);
+  Staged s;
+  if ((rc = s.alloc(ray_bytes + need))) return rc;
+  char *rays_d = s.dev, *out_d = rays_d + ray_bytes;
+  hipError_t e = hipMemcpy(rays_d, rays_host, ray_bytes, hipMemcpyHostToDevice);
   if (e == hipSuccess) {
-    rc = enqueue(scene_args, rd, n, channels, anyhit, od, nullptr);
-    if (!rc) e = hipMemcpy(out_host, od, need, hipMemcpyDeviceToHost);  // (the null stream: behind the kernel)
+    if ((rc = enqueue(scene_args, (const double *)rays_d, n, channels, anyhit, out_d, nullptr))) return rc;
+    e = hipMemcpy(out_host, out_d, need, hipMemcpyDeviceToHost);  // (the null stream: behind the kernel)
   }
-  (void)hipFree(rd);
-  (void)hipFree(od);
-  if (rc) return rc;
   if (e != hipSuccess) return fail(PT_ERR_HIP, "staging a ray batch failed: %s", hipGetErrorString(e));
   return PT_OK;
 }

@@ -10,48 +10,20 @@
 // pt_scene_kernel_args (ptrace.h, ABI 1.7) hands out, there is no link dependency, nothing is loaded from here.
 #include <hip/hip_runtime.h>
 
-#include <algorithm>
-#include <cstdarg>
-#include <cstdio>
-#include <cstring>
-
 #include "../../include/ptrace_scatter.h"
 #define PT_QUERY_PARTS_ONLY
 #include "pt_kernels.h"
 #include "pt_scatter.h"
+#include "pt_host_common.h"
 
 #define PT_SCAT_VERSION ((1 << 16) | 2)
 #define PT_SCAT_MAX_N 2147483647LL  // the grid is n / 256 blocks in x
-
-static thread_local char g_err[512] = "";
-
-static int fail(int code, const char *fmt, ...) {
-  va_list ap;
-  va_start(ap, fmt);
-  vsnprintf(g_err, sizeof g_err, fmt, ap);
-  va_end(ap);
-  return code;
-}
-
-#define HIP_TRY(expr)                                                                                          \
-  do {                                                                                                         \
-    hipError_t _e = (expr);                                                                                    \
-    if (_e != hipSuccess) return fail(PT_ERR_HIP, "%s failed: %s (%s:%d)", #expr, hipGetErrorString(_e), __FILE__, __LINE__); \
-  } while (0)
 
 extern "C" int pt_rays_scatter_version(void) { return PT_SCAT_VERSION; }
 
 extern "C" size_t pt_rays_scatter_args_bytes(void) { return sizeof(PtKArgs); }
 
-extern "C" int pt_rays_scatter_last_error(char *buf, size_t n) {
-  const size_t len = strlen(g_err);
-  if (buf && n) {
-    const size_t c = std::min(len, n - 1);
-    memcpy(buf, g_err, c);
-    buf[c] = 0;
-  }
-  return (int)len;
-}
+extern "C" int pt_rays_scatter_last_error(char *buf, size_t n) { return copy_last_error(buf, n); }
 
 // ---- sizes ------------------------------------------------------------------------------------------------------------------
 static bool shape_ok(long long n, int channels) { return n >= 0 && n <= PT_SCAT_MAX_N && channels >= 0 && !(channels & ~PT_SCAT_ALL); }
@@ -86,14 +58,7 @@ static int check_args(int device, const void *scene_args, size_t scene_args_byte
   if (roulette != 0 && roulette != 1) return fail(PT_ERR_INVALID, "roulette must be 0 or 1, not %d", roulette);
   if (channels < 0 || (channels & ~PT_SCAT_ALL))
     return fail(PT_ERR_INVALID, "channel bits %#x: a scatter batch has PT_SCAT_WEIGHT | PT_SCAT_EMITTED", channels);
-  if (device < 0) return fail(PT_ERR_INVALID, "device %d", device);
-  if (!scene_args) return fail(PT_ERR_INVALID, "null scene argument block");
-  if (scene_args_bytes != sizeof(PtKArgs))
-    return fail(PT_ERR_INVALID, "scene argument block of %zu bytes, this library's has %zu: all libraries must come from one build",
-                scene_args_bytes, sizeof(PtKArgs));
-  const PtKArgs *a = (const PtKArgs *)scene_args;
-  if (!a->cold) return fail(PT_ERR_INVALID, "scene argument block without its device copy (not from pt_scene_kernel_args?)");
-  if (a->n_shapes < 0) return fail(PT_ERR_INVALID, "scene argument block with %d shapes", a->n_shapes);
+  if (int rc = check_scene_block(device, scene_args, scene_args_bytes, PT_BLOCK_SHAPES)) return rc;
   need = pt_rays_scatter_bytes(n, channels);
   if (n == 0) return PT_OK;
   if (need_slots && !slots) return fail(PT_ERR_INVALID, "null slot table (pt_rays_slots_device makes it)");
@@ -104,19 +69,9 @@ static int check_args(int device, const void *scene_args, size_t scene_args_byte
   return PT_OK;
 }
 
-static int device_ok(int device) {
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return fail(PT_ERR_NODEVICE, "no HIP device visible");
-  if (device >= ndev) return fail(PT_ERR_INVALID, "device %d out of range (%d visible)", device, ndev);
-  return PT_OK;
-}
-
 // ---- launches ---------------------------------------------------------------------------------------------------------------
-static dim3 grid_of(long long n) { return dim3((unsigned)((n + PT_BLOCK - 1) / PT_BLOCK)); }
-
 static int enqueue_slots(const void *scene_args, void *slots_dev, hipStream_t st) {
-  PtKArgs a;
-  memcpy(&a, scene_args, sizeof a);
+  const PtKArgs a = scene_block(scene_args);
   if (a.n_shapes == 0) return PT_OK;
   hipLaunchKernelGGL(pt_scatter_slots_kernel, grid_of(a.n_shapes), dim3(PT_BLOCK), 0, st, a, (int *)slots_dev);
   HIP_TRY(hipGetLastError());
@@ -126,8 +81,7 @@ static int enqueue_slots(const void *scene_args, void *slots_dev, hipStream_t st
 static int enqueue_scatter(const void *scene_args, const void *slots_dev, const int *shape_dev, const double *point_dev, const double *normal_dev,
                            const double *uv_dev, const double *dir_dev, const unsigned long long *state_dev, const unsigned long long *inc_dev,
                            long long n, int roulette, int channels, void *out_dev, hipStream_t st) {
-  PtKArgs a;
-  memcpy(&a, scene_args, sizeof a);
+  const PtKArgs a = scene_block(scene_args);
   hipLaunchKernelGGL(pt_scatter_kernel, grid_of(n), dim3(PT_BLOCK), 0, st, a, (const int *)slots_dev, shape_dev, point_dev, normal_dev, uv_dev,
                      dir_dev, state_dev, inc_dev, n, roulette, channels, out_dev);
   HIP_TRY(hipGetLastError());
@@ -153,13 +107,6 @@ extern "C" int pt_rays_scatter_device(int device, const void *scene_args, size_t
 }
 
 // ---- host form: one device allocation holds the slot table, the input planes and the output -------------------------------------
-struct Staged {
-  char *dev = nullptr;
-  ~Staged() { (void)hipFree(dev); }
-};
-
-static size_t up8(size_t x) { return (x + 7) & ~(size_t)7; }
-
 extern "C" int pt_rays_scatter(int device, const void *scene_args, size_t scene_args_bytes, const int *shape_host, const double *point_host,
                                const double *normal_host, const double *uv_host, const double *dir_host,
                                const unsigned long long *pcg_state_host, const unsigned long long *pcg_inc_host, long long n, int roulette,
@@ -174,8 +121,7 @@ extern "C" int pt_rays_scatter(int device, const void *scene_args, size_t scene_
                plane = (size_t)n * 8;
   const size_t total = slots_b + shape_b + 13 * plane + need;
   Staged s;
-  hipError_t e = hipMalloc((void **)&s.dev, total);
-  if (e != hipSuccess) return fail(e == hipErrorOutOfMemory ? PT_ERR_NOMEM : PT_ERR_HIP, "hipMalloc(%zu) failed: %s", total, hipGetErrorString(e));
+  if ((rc = s.alloc(total))) return rc;
   char *slots_d = s.dev, *shape_d = slots_d + slots_b, *point_d = shape_d + shape_b, *normal_d = point_d + 3 * plane, *uv_d = normal_d + 3 * plane,
        *dir_d = uv_d + 2 * plane, *state_d = dir_d + 3 * plane, *inc_d = state_d + plane, *out_d = inc_d + plane;
   HIP_TRY(hipMemcpy(shape_d, shape_host, (size_t)n * 4, hipMemcpyHostToDevice));

@@ -10,48 +10,20 @@
 // block pt_scene_kernel_args (ptrace.h, ABI 1.7) hands out, there is no link dependency, nothing is loaded from here.
 #include <hip/hip_runtime.h>
 
-#include <algorithm>
-#include <cstdarg>
-#include <cstdio>
-#include <cstring>
-
 #include "../../include/ptrace_surface.h"
 #define PT_QUERY_PARTS_ONLY
 #include "pt_kernels.h"
 #include "pt_surface.h"
+#include "pt_host_common.h"
 
 #define PT_SURF_VERSION ((1 << 16) | 1)
 #define PT_SURF_MAX_N 2147483647LL  // the grid is n / 256 blocks in x
-
-static thread_local char g_err[512] = "";
-
-static int fail(int code, const char *fmt, ...) {
-  va_list ap;
-  va_start(ap, fmt);
-  vsnprintf(g_err, sizeof g_err, fmt, ap);
-  va_end(ap);
-  return code;
-}
-
-#define HIP_TRY(expr)                                                                                          \
-  do {                                                                                                         \
-    hipError_t _e = (expr);                                                                                    \
-    if (_e != hipSuccess) return fail(PT_ERR_HIP, "%s failed: %s (%s:%d)", #expr, hipGetErrorString(_e), __FILE__, __LINE__); \
-  } while (0)
 
 extern "C" int pt_rays_surface_version(void) { return PT_SURF_VERSION; }
 
 extern "C" size_t pt_rays_surface_args_bytes(void) { return sizeof(PtKArgs); }
 
-extern "C" int pt_rays_surface_last_error(char *buf, size_t n) {
-  const size_t len = strlen(g_err);
-  if (buf && n) {
-    const size_t c = std::min(len, n - 1);
-    memcpy(buf, g_err, c);
-    buf[c] = 0;
-  }
-  return (int)len;
-}
+extern "C" int pt_rays_surface_last_error(char *buf, size_t n) { return copy_last_error(buf, n); }
 
 // ---- sizes ------------------------------------------------------------------------------------------------------------------
 static bool block_ok(const void *scene_args, size_t scene_args_bytes) {
@@ -82,15 +54,7 @@ extern "C" long long pt_rays_surface_plane_offset(long long n, int channels, int
 
 // ---- checks: every argument, before any HIP call ------------------------------------------------------------------------------
 static int check_block(int device, const void *scene_args, size_t scene_args_bytes) {
-  if (device < 0) return fail(PT_ERR_INVALID, "device %d", device);
-  if (!scene_args) return fail(PT_ERR_INVALID, "null scene argument block");
-  if (scene_args_bytes != sizeof(PtKArgs))
-    return fail(PT_ERR_INVALID, "scene argument block of %zu bytes, this library's has %zu: all libraries must come from one build",
-                scene_args_bytes, sizeof(PtKArgs));
-  const PtKArgs *a = (const PtKArgs *)scene_args;
-  if (!a->cold) return fail(PT_ERR_INVALID, "scene argument block without its device copy (not from pt_scene_kernel_args?)");
-  if (a->n_shapes < 0 || a->n_lights < 0) return fail(PT_ERR_INVALID, "scene argument block with %d shapes and %d lights", a->n_shapes, a->n_lights);
-  return PT_OK;
+  return check_scene_block(device, scene_args, scene_args_bytes, PT_BLOCK_SHAPES | PT_BLOCK_LIGHTS);
 }
 
 static int check_count(long long n) {
@@ -132,19 +96,9 @@ static int check_lights(int device, const void *scene_args, size_t scene_args_by
   return PT_OK;
 }
 
-static int device_ok(int device) {
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return fail(PT_ERR_NODEVICE, "no HIP device visible");
-  if (device >= ndev) return fail(PT_ERR_INVALID, "device %d out of range (%d visible)", device, ndev);
-  return PT_OK;
-}
-
 // ---- launches ---------------------------------------------------------------------------------------------------------------
-static dim3 grid_of(long long n) { return dim3((unsigned)((n + PT_BLOCK - 1) / PT_BLOCK)); }
-
 static int enqueue_slots(const void *scene_args, void *slots_dev, hipStream_t st) {
-  PtKArgs a;
-  memcpy(&a, scene_args, sizeof a);
+  const PtKArgs a = scene_block(scene_args);
   if (a.n_shapes == 0) return PT_OK;
   hipLaunchKernelGGL(pt_slots_kernel, grid_of(a.n_shapes), dim3(PT_BLOCK), 0, st, a, (int *)slots_dev);
   HIP_TRY(hipGetLastError());
@@ -153,8 +107,7 @@ static int enqueue_slots(const void *scene_args, void *slots_dev, hipStream_t st
 
 static int enqueue_surface(const void *scene_args, const void *slots_dev, const int *shape_dev, const double *uv_dev, long long n, int channels,
                            void *out_dev, hipStream_t st) {
-  PtKArgs a;
-  memcpy(&a, scene_args, sizeof a);
+  const PtKArgs a = scene_block(scene_args);
   hipLaunchKernelGGL(pt_surface_kernel, grid_of(n), dim3(PT_BLOCK), 0, st, a, (const int *)slots_dev, shape_dev, uv_dev, n, channels, out_dev);
   HIP_TRY(hipGetLastError());
   return PT_OK;
@@ -163,8 +116,7 @@ static int enqueue_surface(const void *scene_args, const void *slots_dev, const 
 static int enqueue_lights(const void *scene_args, const void *slots_dev, const int *shape_dev, const double *point_dev, const double *normal_dev,
                           const double *uv_dev, const double *dir_dev, long long n, const double *ambient, const double *background,
                           void *out_dev, hipStream_t st) {
-  PtKArgs a;
-  memcpy(&a, scene_args, sizeof a);
+  const PtKArgs a = scene_block(scene_args);
   const V3 amb = {ambient[0], ambient[1], ambient[2]}, bg = {background[0], background[1], background[2]};
   hipLaunchKernelGGL(pt_shade_lights_kernel, grid_of(n), dim3(PT_BLOCK), 0, st, a, (const int *)slots_dev, shape_dev, point_dev, normal_dev, uv_dev,
                      dir_dev, n, amb, bg, (double *)out_dev);
@@ -218,13 +170,6 @@ extern "C" int pt_rays_shade_lights_device(int device, const void *scene_args, s
 }
 
 // ---- host forms: one device allocation holds the slot table, the input planes and the output -------------------------------------
-struct Staged {
-  char *dev = nullptr;
-  ~Staged() { (void)hipFree(dev); }
-};
-
-static size_t up8(size_t x) { return (x + 7) & ~(size_t)7; }
-
 extern "C" int pt_rays_surface(int device, const void *scene_args, size_t scene_args_bytes, const int *shape_host, const double *uv_host,
                                long long n, int channels, void *out_host, size_t out_bytes) {
   size_t need;
@@ -234,9 +179,7 @@ extern "C" int pt_rays_surface(int device, const void *scene_args, size_t scene_
   HIP_TRY(hipSetDevice(device));
   const size_t slots_b = std::max<size_t>(slots_need(scene_args), 8), shape_b = up8((size_t)n * 4), uv_b = channels ? (size_t)n * 16 : 0;
   Staged s;
-  hipError_t e = hipMalloc((void **)&s.dev, slots_b + shape_b + uv_b + need);
-  if (e != hipSuccess)
-    return fail(e == hipErrorOutOfMemory ? PT_ERR_NOMEM : PT_ERR_HIP, "hipMalloc(%zu) failed: %s", slots_b + shape_b + uv_b + need, hipGetErrorString(e));
+  if ((rc = s.alloc(slots_b + shape_b + uv_b + need))) return rc;
   char *slots_d = s.dev, *shape_d = slots_d + slots_b, *uv_d = shape_d + shape_b, *out_d = uv_d + uv_b;
   HIP_TRY(hipMemcpy(shape_d, shape_host, (size_t)n * 4, hipMemcpyHostToDevice));
   if (uv_b) HIP_TRY(hipMemcpy(uv_d, uv_host, uv_b, hipMemcpyHostToDevice));
@@ -258,8 +201,7 @@ extern "C" int pt_rays_shade_lights(int device, const void *scene_args, size_t s
   const size_t slots_b = std::max<size_t>(slots_need(scene_args), 8), shape_b = up8((size_t)n * 4), plane = (size_t)n * 8;
   const size_t total = slots_b + shape_b + 11 * plane + need;
   Staged s;
-  hipError_t e = hipMalloc((void **)&s.dev, total);
-  if (e != hipSuccess) return fail(e == hipErrorOutOfMemory ? PT_ERR_NOMEM : PT_ERR_HIP, "hipMalloc(%zu) failed: %s", total, hipGetErrorString(e));
+  if ((rc = s.alloc(total))) return rc;
   char *slots_d = s.dev, *shape_d = slots_d + slots_b, *point_d = shape_d + shape_b, *normal_d = point_d + 3 * plane, *uv_d = normal_d + 3 * plane,
        *dir_d = uv_d + 2 * plane, *out_d = dir_d + 3 * plane;
   HIP_TRY(hipMemcpy(shape_d, shape_host, (size_t)n * 4, hipMemcpyHostToDevice));

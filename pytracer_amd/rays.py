@@ -53,6 +53,61 @@ _RAD_OF = {"pcg": RAD_PCG, "count": RAD_COUNT}
 
 
 GATHER_COUNT, GATHER_ALL = 1, 1  # PT_GATHER_* of include/ptrace_gather.h
+_GATHER_OF = {"count": GATHER_COUNT}
+
+
+def _parse_channels(channels, names_to_bits, all_bits, what) -> int:
+    """The channel bits of a ``what`` batch from an int, names (``"a"``, ``"a,b"``), ``"all"`` or ``"none"``."""
+    has = f"a {what} batch has the channel{'s' if len(names_to_bits) > 1 else ''}"
+    if isinstance(channels, str):
+        names = [x.strip().lower() for x in channels.split(",") if x.strip()]
+        if names == ["all"]:
+            return all_bits
+        if names == ["none"]:
+            return 0
+        unknown = [x for x in names if x not in names_to_bits]
+        if unknown:
+            raise ValueError(f"{has} {', '.join(names_to_bits)}; not {', '.join(unknown)}")
+        return sum({names_to_bits[x] for x in names})
+    bits = int(channels)
+    if bits < 0 or bits & ~all_bits:
+        raise ValueError(f"{has} {', '.join(f'{k} ({v})' for k, v in names_to_bits.items())}; not {bits:#x}")
+    return bits
+
+
+class _BatchViews:
+    """What the views over an add-on's result buffer share: the constructor's checks, the look-up of a selected channel's
+    planes, and ``has``.  A subclass names its channels (``_names``, ``_all``), itself (``_what``; ``_unit``: what it counts) and
+    the two mirrors of its library's size functions (``_bytes``, ``_offset``)."""
+    _unit = "records"
+
+    def __init__(self, buf, n: int, channels, shape):
+        self.channels = _parse_channels(channels, self._names, self._all, self._what)
+        self.n = int(n)
+        self.shape = (self.n,) if shape is None else tuple(int(x) for x in shape)
+        if int(np.prod(self.shape, dtype=np.int64)) != self.n:
+            raise ValueError(f"shape {self.shape} does not hold {self.n} {self._unit}")
+        self.nbytes = self._bytes(self.n, self.channels)
+        buf = np.asarray(buf)
+        if buf.dtype != np.uint8 or buf.ndim != 1:
+            buf = buf.reshape(-1).view(np.uint8)
+        if buf.nbytes < self.nbytes:
+            raise ValueError(f"{self._what} buffer too small: {buf.nbytes} < {self.nbytes} bytes")
+        self.buffer = buf
+
+    def _plane_views(self, channel: int, count: int, dtype) -> np.ndarray:
+        """``[count, n]``: the planes of a selected channel."""
+        if not self.channels & channel:
+            name = next(k for k, v in self._names.items() if v == channel)
+            raise KeyError(f"channel {name!r} was not selected for this {self._what} batch (channels = {self.channels:#x})")
+        off = self._offset(self.n, self.channels, channel, 0)
+        return self.buffer[off: off + self.n * 8 * count].view(dtype).reshape(count, self.n)
+
+    def _colour(self, channel: int) -> np.ndarray:
+        return np.moveaxis(self._plane_views(channel, 3, np.float64).reshape((3,) + self.shape), 0, -1)
+
+    def has(self, name: str) -> bool:
+        return bool(self.channels & self._names[name])
 
 
 def ray_channels(channels) -> int:
@@ -182,20 +237,7 @@ class RayHits:
 
 def surface_channels(channels) -> int:
     """``PT_SURF_*`` bits from an int, names (``"emitted"``, ``"brdf_color,emitted"``), ``"all"`` or ``"none"``."""
-    if isinstance(channels, str):
-        names = [x.strip().lower() for x in channels.split(",") if x.strip()]
-        if names == ["all"]:
-            return SURF_ALL
-        if names == ["none"]:
-            return 0
-        unknown = [x for x in names if x not in _SURF_OF]
-        if unknown:
-            raise ValueError(f"a surface batch has the channels brdf_color, emitted; not {', '.join(unknown)}")
-        return sum({_SURF_OF[x] for x in names})
-    bits = int(channels)
-    if bits < 0 or bits & ~SURF_ALL:
-        raise ValueError(f"a surface batch has the channels brdf_color (1), emitted (2); not {bits:#x}")
-    return bits
+    return _parse_channels(channels, _SURF_OF, SURF_ALL, "surface")
 
 
 def surface_bytes(n: int, channels: int) -> int:
@@ -217,37 +259,18 @@ def surface_plane_offset(n: int, channels: int, channel: int, component: int = 0
     return ((n * 4 + 7) & ~7) + n * 8 * (before + component)
 
 
-class SurfaceColors:
+class SurfaceColors(_BatchViews):
     """Views over the buffer of a surface batch (``buf``: ``pt_rays_surface_bytes`` bytes, contiguous ``uint8``): the BRDF kind
     of every record's material (``abi.BRDF_*``; -1 where nothing was hit) and the selected colours.  Nothing here copies:
     ``brdf_color`` and ``emitted`` are strided views with the component as last axis.  ``shape``: what the records' axis is
     viewed as (a frame's ``[nsamp, rows, W]``); default ``[n]``."""
 
+    _names, _all, _what = _SURF_OF, SURF_ALL, "surface"
+    _bytes, _offset = staticmethod(surface_bytes), staticmethod(surface_plane_offset)
+
     def __init__(self, buf, n: int, channels=SURF_ALL, shape=None):
-        self.channels = surface_channels(channels)
-        self.n = int(n)
-        self.shape = (self.n,) if shape is None else tuple(int(x) for x in shape)
-        if int(np.prod(self.shape, dtype=np.int64)) != self.n:
-            raise ValueError(f"shape {self.shape} does not hold {self.n} records")
-        self.nbytes = surface_bytes(self.n, self.channels)
-        buf = np.asarray(buf)
-        if buf.dtype != np.uint8 or buf.ndim != 1:
-            buf = buf.reshape(-1).view(np.uint8)
-        if buf.nbytes < self.nbytes:
-            raise ValueError(f"surface buffer too small: {buf.nbytes} < {self.nbytes} bytes")
-        self.buffer = buf
-        self.brdf_kind = buf[: self.n * 4].view(np.int32).reshape(self.shape)
-
-    def _colour(self, channel: int) -> np.ndarray:
-        if not self.channels & channel:
-            name = next(k for k, v in _SURF_OF.items() if v == channel)
-            raise KeyError(f"channel {name!r} was not selected for this surface batch (channels = {self.channels:#x})")
-        off = surface_plane_offset(self.n, self.channels, channel, 0)
-        planes = self.buffer[off: off + self.n * 24].view(np.float64).reshape((3,) + self.shape)
-        return np.moveaxis(planes, 0, -1)
-
-    def has(self, name: str) -> bool:
-        return bool(self.channels & _SURF_OF[name])
+        super().__init__(buf, n, channels, shape)
+        self.brdf_kind = self.buffer[: self.n * 4].view(np.int32).reshape(self.shape)
 
     @property
     def hit(self) -> np.ndarray:
@@ -273,20 +296,7 @@ class SurfaceColors:
 
 def scatter_channels(channels) -> int:
     """``PT_SCAT_*`` bits from an int, names (``"weight"``, ``"weight,emitted"``), ``"all"`` or ``"none"``."""
-    if isinstance(channels, str):
-        names = [x.strip().lower() for x in channels.split(",") if x.strip()]
-        if names == ["all"]:
-            return SCAT_ALL
-        if names == ["none"]:
-            return 0
-        unknown = [x for x in names if x not in _SCAT_OF]
-        if unknown:
-            raise ValueError(f"a scatter batch has the channels weight, emitted; not {', '.join(unknown)}")
-        return sum({_SCAT_OF[x] for x in names})
-    bits = int(channels)
-    if bits < 0 or bits & ~SCAT_ALL:
-        raise ValueError(f"a scatter batch has the channels weight (1), emitted (2); not {bits:#x}")
-    return bits
+    return _parse_channels(channels, _SCAT_OF, SCAT_ALL, "scatter")
 
 
 def scatter_bytes(n: int, channels: int) -> int:
@@ -316,43 +326,25 @@ def scatter_plane_offset(n: int, channels: int, channel: int, component: int = 0
     return pad + n * 8 * (10 + before + component)
 
 
-class ScatteredRays:
+class ScatteredRays(_BatchViews):
     """Views over the buffer of a scatter batch (``buf``: ``pt_rays_scatter_bytes`` bytes, contiguous ``uint8``).  Nothing here
     copies.  ``status``: -1 no hit, 0 terminated (by the roulette or a black BRDF pigment: the record's value is ``emitted``),
     1 scattered; ``rays``: the ``[8, n]`` block ``trace_rays`` reads (a dead ray where ``status != 1``: it hits nothing);
     ``pcg_state`` / ``pcg_inc``: every record's generator behind its draws; ``weight`` (the BRDF pigment's colour behind the
     roulette's compensation) and ``emitted`` with the component as last axis.  ``shape``: what the records' axis is viewed as."""
 
+    _names, _all, _what = _SCAT_OF, SCAT_ALL, "scatter"
+    _bytes, _offset = staticmethod(scatter_bytes), staticmethod(scatter_plane_offset)
+
     def __init__(self, buf, n: int, channels=SCAT_ALL, shape=None):
-        self.channels = scatter_channels(channels)
-        self.n = int(n)
-        self.shape = (self.n,) if shape is None else tuple(int(x) for x in shape)
-        if int(np.prod(self.shape, dtype=np.int64)) != self.n:
-            raise ValueError(f"shape {self.shape} does not hold {self.n} records")
-        self.nbytes = scatter_bytes(self.n, self.channels)
-        buf = np.asarray(buf)
-        if buf.dtype != np.uint8 or buf.ndim != 1:
-            buf = buf.reshape(-1).view(np.uint8)
-        if buf.nbytes < self.nbytes:
-            raise ValueError(f"scatter buffer too small: {buf.nbytes} < {self.nbytes} bytes")
-        self.buffer = buf
+        super().__init__(buf, n, channels, shape)
+        buf = self.buffer
         self.status = buf[: self.n * 4].view(np.int32).reshape(self.shape)
         off = scatter_plane_offset(self.n, self.channels, SCAT_RAYS, 0)
         self.rays = buf[off: off + self.n * 64].view(np.float64).reshape(8, self.n)
         pcg = buf[off + self.n * 64: off + self.n * 80].view(np.uint64).reshape(2, self.n)
         self.pcg = pcg  # [2, n]: what the next scatter takes as it is
         self.pcg_state, self.pcg_inc = pcg[0].reshape(self.shape), pcg[1].reshape(self.shape)
-
-    def _colour(self, channel: int) -> np.ndarray:
-        if not self.channels & channel:
-            name = next(k for k, v in _SCAT_OF.items() if v == channel)
-            raise KeyError(f"channel {name!r} was not selected for this scatter batch (channels = {self.channels:#x})")
-        off = scatter_plane_offset(self.n, self.channels, channel, 0)
-        planes = self.buffer[off: off + self.n * 24].view(np.float64).reshape((3,) + self.shape)
-        return np.moveaxis(planes, 0, -1)
-
-    def has(self, name: str) -> bool:
-        return bool(self.channels & _SCAT_OF[name])
 
     @property
     def scattered(self) -> np.ndarray:
@@ -381,20 +373,7 @@ class ScatteredRays:
 
 def radiance_channels(channels) -> int:
     """``PT_RAD_*`` bits from an int, names (``"pcg"``, ``"pcg,count"``), ``"all"`` or ``"none"``."""
-    if isinstance(channels, str):
-        names = [x.strip().lower() for x in channels.split(",") if x.strip()]
-        if names == ["all"]:
-            return RAD_ALL
-        if names == ["none"]:
-            return 0
-        unknown = [x for x in names if x not in _RAD_OF]
-        if unknown:
-            raise ValueError(f"a radiance batch has the channels pcg, count; not {', '.join(unknown)}")
-        return sum({_RAD_OF[x] for x in names})
-    bits = int(channels)
-    if bits < 0 or bits & ~RAD_ALL:
-        raise ValueError(f"a radiance batch has the channels pcg (1), count (2); not {bits:#x}")
-    return bits
+    return _parse_channels(channels, _RAD_OF, RAD_ALL, "radiance")
 
 
 def radiance_bytes(n: int, channels: int) -> int:
@@ -418,40 +397,22 @@ def radiance_plane_offset(n: int, channels: int, channel: int, component: int = 
     return -1
 
 
-class RayRadiance:
+class RayRadiance(_BatchViews):
     """Views over the buffer of a radiance batch (``buf``: ``pt_rays_radiance_bytes`` bytes, contiguous ``uint8``).  Nothing
     here copies.  ``radiance``: ``PathTracer(...)(ray)`` per ray with the component as last axis; ``pcg`` (``[2, n]``),
     ``pcg_state`` / ``pcg_inc``: every ray's generator behind its draws; ``n_rays``: the rays handed to a world query for it
     (``uint64``).  ``shape``: what the rays' axis is viewed as (a frame's ``[nsamp, rows, W]``); default ``[n]``."""
 
+    _names, _all, _what, _unit = _RAD_OF, RAD_ALL, "radiance", "rays"
+    _bytes, _offset = staticmethod(radiance_bytes), staticmethod(radiance_plane_offset)
+
     def __init__(self, buf, n: int, channels=RAD_ALL, shape=None):
-        self.channels = radiance_channels(channels)
-        self.n = int(n)
-        self.shape = (self.n,) if shape is None else tuple(int(x) for x in shape)
-        if int(np.prod(self.shape, dtype=np.int64)) != self.n:
-            raise ValueError(f"shape {self.shape} does not hold {self.n} rays")
-        self.nbytes = radiance_bytes(self.n, self.channels)
-        buf = np.asarray(buf)
-        if buf.dtype != np.uint8 or buf.ndim != 1:
-            buf = buf.reshape(-1).view(np.uint8)
-        if buf.nbytes < self.nbytes:
-            raise ValueError(f"radiance buffer too small: {buf.nbytes} < {self.nbytes} bytes")
-        self.buffer = buf
-        self.radiance = np.moveaxis(buf[: self.n * 24].view(np.float64).reshape((3,) + self.shape), 0, -1)
-
-    def _words(self, channel: int, count: int) -> np.ndarray:
-        if not self.channels & channel:
-            name = next(k for k, v in _RAD_OF.items() if v == channel)
-            raise KeyError(f"channel {name!r} was not selected for this radiance batch (channels = {self.channels:#x})")
-        off = radiance_plane_offset(self.n, self.channels, channel, 0)
-        return self.buffer[off: off + self.n * 8 * count].view(np.uint64).reshape(count, self.n)
-
-    def has(self, name: str) -> bool:
-        return bool(self.channels & _RAD_OF[name])
+        super().__init__(buf, n, channels, shape)
+        self.radiance = np.moveaxis(self.buffer[: self.n * 24].view(np.float64).reshape((3,) + self.shape), 0, -1)
 
     @property
     def pcg(self) -> np.ndarray:
-        return self._words(RAD_PCG, 2)
+        return self._plane_views(RAD_PCG, 2, np.uint64)
 
     @property
     def pcg_state(self) -> np.ndarray:
@@ -463,7 +424,7 @@ class RayRadiance:
 
     @property
     def n_rays(self) -> np.ndarray:
-        return self._words(RAD_COUNT, 1)[0].reshape(self.shape)
+        return self._plane_views(RAD_COUNT, 1, np.uint64)[0].reshape(self.shape)
 
     def planes(self) -> dict:
         """name -> view, for every selected channel (what the ``radiance`` command writes into its ``.npz``)."""
@@ -477,20 +438,7 @@ class RayRadiance:
 
 def gather_channels(channels) -> int:
     """``PT_GATHER_*`` bits from an int, a name (``"count"``), ``"all"`` or ``"none"``."""
-    if isinstance(channels, str):
-        names = [x.strip().lower() for x in channels.split(",") if x.strip()]
-        if names == ["all"]:
-            return GATHER_ALL
-        if names == ["none"]:
-            return 0
-        unknown = [x for x in names if x != "count"]
-        if unknown:
-            raise ValueError(f"a gather batch has the channel count; not {', '.join(unknown)}")
-        return GATHER_COUNT if names else 0
-    bits = int(channels)
-    if bits < 0 or bits & ~GATHER_ALL:
-        raise ValueError(f"a gather batch has the channel count (1); not {bits:#x}")
-    return bits
+    return _parse_channels(channels, _GATHER_OF, GATHER_ALL, "gather")
 
 
 def gather_bytes(n: int, channels: int) -> int:
@@ -512,36 +460,25 @@ def gather_plane_offset(n: int, channels: int, channel: int, component: int = 0)
     return -1
 
 
-class GatheredRadiance:
+class GatheredRadiance(_BatchViews):
     """Views over the buffer of a gather batch (``buf``: ``pt_rays_gather_bytes`` bytes, contiguous ``uint8``).  Nothing here
     copies.  ``radiance``: per record the mean of ``PathTracer(...)(ray)`` over its ``samples`` hemisphere rays, summed in sample
     order, with the component as last axis; ``n_rays``: the rays handed to a world query for the record (``uint64``).  ``shape``:
     what the records' axis is viewed as (a frame's ``[nsamp, rows, W]``); default ``[n]``."""
 
-    def __init__(self, buf, n: int, channels=GATHER_ALL, shape=None):
-        self.channels = gather_channels(channels)
-        self.n = int(n)
-        self.shape = (self.n,) if shape is None else tuple(int(x) for x in shape)
-        if int(np.prod(self.shape, dtype=np.int64)) != self.n:
-            raise ValueError(f"shape {self.shape} does not hold {self.n} records")
-        self.nbytes = gather_bytes(self.n, self.channels)
-        buf = np.asarray(buf)
-        if buf.dtype != np.uint8 or buf.ndim != 1:
-            buf = buf.reshape(-1).view(np.uint8)
-        if buf.nbytes < self.nbytes:
-            raise ValueError(f"gather buffer too small: {buf.nbytes} < {self.nbytes} bytes")
-        self.buffer = buf
-        self.radiance = np.moveaxis(buf[: self.n * 24].view(np.float64).reshape((3,) + self.shape), 0, -1)
+    _names, _all, _what = _GATHER_OF, GATHER_ALL, "gather"
+    _bytes, _offset = staticmethod(gather_bytes), staticmethod(gather_plane_offset)
 
-    def has(self, name: str) -> bool:
-        return name == "count" and bool(self.channels & GATHER_COUNT)
+    def __init__(self, buf, n: int, channels=GATHER_ALL, shape=None):
+        super().__init__(buf, n, channels, shape)
+        self.radiance = np.moveaxis(self.buffer[: self.n * 24].view(np.float64).reshape((3,) + self.shape), 0, -1)
+
+    def has(self, name: str) -> bool:  # (any other name is a channel this batch does not have, not an error)
+        return name in _GATHER_OF and super().has(name)
 
     @property
     def n_rays(self) -> np.ndarray:
-        if not self.channels & GATHER_COUNT:
-            raise KeyError(f"channel 'count' was not selected for this gather batch (channels = {self.channels:#x})")
-        off = gather_plane_offset(self.n, self.channels, GATHER_COUNT, 0)
-        return self.buffer[off: off + self.n * 8].view(np.uint64).reshape(self.shape)
+        return self._plane_views(GATHER_COUNT, 1, np.uint64)[0].reshape(self.shape)
 
     def planes(self) -> dict:
         """name -> view, for every selected channel (what the ``gather`` command writes into its ``.npz``)."""
