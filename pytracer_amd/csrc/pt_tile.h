@@ -987,6 +987,8 @@ __global__ __launch_bounds__(PT_BLOCK) __attribute__((amdgpu_waves_per_eu(PT_TIL
   constexpr bool ANYHIT = RENDERER == PT_RENDERER_ONOFF;
 #ifdef PT_DEBUG_TIME
   // cycles of this wave in: 0 prologue, 1 cone, 2 cull, 3 dome tile, 4 rays, 5 query, 6 shade, 7 store
+  // (Flat: 6 is the uniform pixels and the loop over the wave's patterned winners with their stores, 7 the per-pixel
+  //  remainder behind the loop)
   unsigned long long tsum[8] = {0, 0, 0, 0, 0, 0, 0, 0}, tprev = __builtin_amdgcn_s_memtime();
 #define PT_T4(k) do { const unsigned long long tn = __builtin_amdgcn_s_memtime(); tsum[k] += tn - tprev; tprev = tn; } while (0)
 #else
@@ -1245,63 +1247,176 @@ __global__ __launch_bounds__(PT_BLOCK) __attribute__((amdgpu_waves_per_eu(PT_TIL
   if (valid) PT_T4(5);  // (the wait at the barrier counts as query time; a wave without a tile reports no cycles, as before)
   if (shade) {
     // ---- shade + store ----
+    if constexpr (RENDERER == PT_RENDERER_ONOFF) {  // render.py:52-53
+      pt_kargs ca = cold_args(a);
+      const V3 on = {ca->onoff[0], ca->onoff[1], ca->onoff[2]}, bg = {bgx, bgy, bgz};
+      PT_T4(6);
 #pragma unroll
-    for (int k = 0; k < NPX; ++k) {
-      V3 c = {bgx, bgy, bgz};
-      const int hit = h4.best[k];
-      if (RENDERER == PT_RENDERER_ONOFF) {  // render.py:52-53
-        if (hit >= 0) {
-          pt_kargs ca = cold_args(a);
-          c.x = ca->onoff[0];
-          c.y = ca->onoff[1];
-          c.z = ca->onoff[2];
+      for (int k = 0; k < NPX; ++k)
+        if (act[k]) {
+          store_pixel(a, pix[k], h4.best[k] >= 0 ? on : bg, out_f32);
+          nrays += 1ULL;
         }
-      } else if (hit >= 0) {  // render.py:65-74
-        Hit h;
-        h.u = 0.0;
-        h.v = 0.0;
-        Ray rk;
-        rk.o = org;
-        rk.d = dir[k];
-        rk.tmin = tmin;
-        V3 p1, p2;
-        // (a shape whose two pigments are uniform carries pigment + emitted, added at upload with the same fp64
-        //  addition, in pig_c2: pt_layout.h)
-        if constexpr (SLDS) {
-          const pt_lds_rec rec = (pt_lds_rec)(const void *)pt_lds_f64 + hit;
-          const pt_lds_aux ax = (pt_lds_aux)(const void *)(pt_lds_f64 + a.n_shapes * 16) + hit;
-          if (ax->needs_uv) {
-            hit_details(rec, ax, rk, h4.best_t[k], h, true);
-            p1 = brdf_pigment(a, ax, h.u, h.v);
-            p2 = emitted_pigment(a, ax, h.u, h.v);
-            c.x = p1.x + p2.x;
-            c.y = p1.y + p2.y;
-            c.z = p1.z + p2.z;
-          } else {
-            c.x = ax->pig_c2[0];
-            c.y = ax->pig_c2[1];
-            c.z = ax->pig_c2[2];
+      PT_T4(7);
+    } else {
+      // render.py:65-74, once per WINNING SHAPE of the wave instead of once per pixel.  A tile has few distinct winners (C2's
+      // heavy bottom rows: the ground plane and the sphere around the camera), so their records are wave-uniform: each
+      // round takes one winner s, reads its records through the scalar cache, and serves every pixel of the wave that s
+      // won -- the lane's four side by side, four independent fp64 chains.  (a) Shapes whose two pigments are uniform
+      // (pig_c2 carries pigment + emitted, added at upload with the same fp64 addition: pt_layout.h) need no round: one
+      // gather per lane serves them.  (b) The loop shades planes whose pigments are uniform or checkered; a patterned
+      // sphere (atan2 / acos) or an image pigment goes to `left` and through the per-pixel code behind the loop (with
+      // those inside, the kernel spills: profiles/DROPPED_VARIANTS.md).  Every value still comes out of hit_details' /
+      // pigment_color's operations in their order: a.hoist[s] IS xf_point(invm, origin) (pt_prep_hoist), the object-space
+      // origin the query already used.
+      int pend[NPX], left[NPX];  // the winner still to shade in the loop / left to the code behind it; -1: none
+      const V3 bg = {bgx, bgy, bgz};
+#pragma unroll
+      for (int k = 0; k < NPX; ++k) {
+        const int hit = h4.best[k];
+        pend[k] = (act[k] && hit >= 0) ? hit : -1;
+        left[k] = -1;
+        if (act[k]) {
+          if (hit < 0) store_pixel(a, pix[k], bg, out_f32);
+          nrays += 1ULL;
+        }
+      }
+      // (a) per lane, the four pixels side by side: two gathers (needs_uv, then pig_c2) and their two waits serve all four
+      //     pixels and every uniform winner at once.  (Taken through the loop, one round trip per winner, a tile among C2's
+      //     spheres with ten winners lost 4 kcycles against the per-pixel code: profiles/r09_tile4_winners_ab.txt.)
+      //     A pixel without a winner reads record 0 and stores nothing.
+      {
+        double cu[NPX][3];
+        int uv[NPX];
+#pragma unroll
+        for (int k = 0; k < NPX; ++k) {
+          const int hit = pend[k] >= 0 ? pend[k] : 0;
+          if constexpr (SLDS)
+            uv[k] = ((pt_lds_aux)(const void *)(pt_lds_f64 + a.n_shapes * 16) + hit)->needs_uv;
+          else
+            uv[k] = a.aux[hit].needs_uv;
+        }
+#pragma unroll
+        for (int k = 0; k < NPX; ++k) {
+          const int hit = pend[k] >= 0 ? pend[k] : 0;
+#pragma unroll
+          for (int q = 0; q < 3; ++q) {
+            if constexpr (SLDS)
+              cu[k][q] = ((pt_lds_aux)(const void *)(pt_lds_f64 + a.n_shapes * 16) + hit)->pig_c2[q];
+            else
+              cu[k][q] = a.aux[hit].pig_c2[q];
+          }
+        }
+#pragma unroll
+        for (int k = 0; k < NPX; ++k)
+          if (pend[k] >= 0 && uv[k] == 0) {
+            const V3 c = {cu[k][0], cu[k][1], cu[k][2]};
+            store_pixel(a, pix[k], c, out_f32);
+            pend[k] = -1;
+          }
+      }
+      // (b) the winners with a pattern, one per round
+      bool any_left = false;  // (wave-uniform)
+      for (;;) {
+        const int mine = max(max(pend[0], pend[1]), max(pend[2], pend[3]));
+        const unsigned long long open = __ballot(mine >= 0);
+        if (!open) break;
+        const int s = __builtin_amdgcn_readlane(mine, __ffsll((long long)open) - 1);
+        typedef const __attribute__((address_space(4))) PtShapeAux *pt_kaux;
+        const pt_kaux ax = (pt_kaux)(const void *)(a.aux + s);
+        // one batch of scalar loads per round: what the plane path needs is asked for before the branch on the kinds
+        // (pinned, or each load sinks into the branch that uses it and becomes a round trip of its own)
+        int pk = ax->pig_kind, ek = ax->emi_kind;
+        pt_kdouble m = PT_KD(a.recs[s].invm);
+        pt_kdouble ho = PT_KD(&a.hoist[s]);
+        double ox = ho[0], oy = ho[1], m0 = m[0], m1 = m[1], m2 = m[2], m4 = m[4], m5 = m[5], m6 = m[6];
+        double psteps = ax->pig_steps, esteps = ax->emi_steps;
+        PT_PIN_SGPR(pk);
+        PT_PIN_SGPR(ek);
+        PT_PIN_SGPR(ox);
+        PT_PIN_SGPR(oy);
+        PT_PIN_SGPR(m0);
+        PT_PIN_SGPR(m1);
+        PT_PIN_SGPR(m2);
+        PT_PIN_SGPR(m4);
+        PT_PIN_SGPR(m5);
+        PT_PIN_SGPR(m6);
+        PT_PIN_SGPR(psteps);
+        PT_PIN_SGPR(esteps);
+        if (s >= a.n_spheres && pk != PT_PIGMENT_IMAGE && ek != PT_PIGMENT_IMAGE) {
+          const V3 p_c1 = {ax->pig_c1[0], ax->pig_c1[1], ax->pig_c1[2]}, p_c2 = {ax->pig_c2[0], ax->pig_c2[1], ax->pig_c2[2]};
+          const V3 e_c1 = {ax->emi_c1[0], ax->emi_c1[1], ax->emi_c1[2]}, e_c2 = {ax->emi_c2[0], ax->emi_c2[1], ax->emi_c2[2]};
+#pragma unroll
+          for (int k = 0; k < NPX; ++k) {
+            // hit_details for a plane: hp = o + t * xf_vec(invm, d), (u, v) = hp - floor(hp)   (a pixel of another winner
+            // or of none computes on its own t, possibly inf: no address is formed from the result, and nothing is stored)
+            const double t = h4.best_t[k];
+            const double dx = dir[k].x * m0 + dir[k].y * m1 + dir[k].z * m2;
+            const double dy = dir[k].x * m4 + dir[k].y * m5 + dir[k].z * m6;
+            const double hx = ox + t * dx, hy = oy + t * dy;
+            const double u = hx - floor(hx), v = hy - floor(hy);
+            // pigment_color's checker, written out (materials.py:96-100; the parity by halving is explained there)
+            bool p_first = true, e_first = true;
+            if (pk == PT_PIGMENT_CHECKERED) {
+              const double tu = floor(u * psteps), tv = floor(v * psteps);
+              const bool odd_u = floor(tu * 0.5) * 2.0 != tu, odd_v = floor(tv * 0.5) * 2.0 != tv;
+              p_first = odd_u == odd_v;
+            }
+            if (ek == PT_PIGMENT_CHECKERED) {
+              const double tu = floor(u * esteps), tv = floor(v * esteps);
+              const bool odd_u = floor(tu * 0.5) * 2.0 != tu, odd_v = floor(tv * 0.5) * 2.0 != tv;
+              e_first = odd_u == odd_v;
+            }
+            V3 c;
+            c.x = (p_first ? p_c1.x : p_c2.x) + (e_first ? e_c1.x : e_c2.x);
+            c.y = (p_first ? p_c1.y : p_c2.y) + (e_first ? e_c1.y : e_c2.y);
+            c.z = (p_first ? p_c1.z : p_c2.z) + (e_first ? e_c1.z : e_c2.z);
+            if (pend[k] == s) {
+              store_pixel(a, pix[k], c, out_f32);
+              pend[k] = -1;
+            }
           }
         } else {
-          const PtShapeAux *ax = cold_args(a)->aux + hit;
-          if (ax->needs_uv) {
-            hit_details(a.recs + hit, ax, rk, h4.best_t[k], h, true);
-            p1 = brdf_pigment(a, ax, h.u, h.v);
-            p2 = emitted_pigment(a, ax, h.u, h.v);
-            c.x = p1.x + p2.x;
-            c.y = p1.y + p2.y;
-            c.z = p1.z + p2.z;
-          } else {
-            c.x = ax->pig_c2[0];
-            c.y = ax->pig_c2[1];
-            c.z = ax->pig_c2[2];
-          }
+#pragma unroll
+          for (int k = 0; k < NPX; ++k)
+            if (pend[k] == s) {
+              left[k] = s;
+              pend[k] = -1;
+            }
+          any_left = true;
         }
       }
       PT_T4(6);
-      if (act[k]) {
-        store_pixel(a, pix[k], c, out_f32);
-        nrays += 1ULL;
+      if (any_left) {
+        // ---- the remainder: patterned spheres and image pigments, per pixel, as before the loop existed ----
+#pragma unroll
+        for (int k = 0; k < NPX; ++k) {
+          const int hit = left[k];
+          if (hit >= 0) {  // (needs_uv != 0, or the loop would have taken it)
+            Hit h;
+            h.u = 0.0;
+            h.v = 0.0;
+            Ray rk;
+            rk.o = org;
+            rk.d = dir[k];
+            rk.tmin = tmin;
+            V3 p1, p2;
+            if constexpr (SLDS) {
+              const pt_lds_rec rec = (pt_lds_rec)(const void *)pt_lds_f64 + hit;
+              const pt_lds_aux ax = (pt_lds_aux)(const void *)(pt_lds_f64 + a.n_shapes * 16) + hit;
+              hit_details(rec, ax, rk, h4.best_t[k], h, true);
+              p1 = brdf_pigment(a, ax, h.u, h.v);
+              p2 = emitted_pigment(a, ax, h.u, h.v);
+            } else {
+              const PtShapeAux *ax = cold_args(a)->aux + hit;
+              hit_details(a.recs + hit, ax, rk, h4.best_t[k], h, true);
+              p1 = brdf_pigment(a, ax, h.u, h.v);
+              p2 = emitted_pigment(a, ax, h.u, h.v);
+            }
+            const V3 c = {p1.x + p2.x, p1.y + p2.y, p1.z + p2.z};
+            store_pixel(a, pix[k], c, out_f32);
+          }
+        }
       }
       PT_T4(7);
     }
