@@ -23,6 +23,7 @@
 #include "pt_plan.h"
 #include "pt_scene_build.h"
 #include "pt_hits_plan.h"
+#include "pt_frame_args.h"
 #include "pt_post.h"
 #include "pt_host_common.h"  // g_err, fail, HIP_TRY, copy_last_error, device_ok
 
@@ -363,80 +364,38 @@ static hipError_t path_lds_limit(const void *kernel, size_t bytes) {
   return hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)PT_LDS_BUDGET);
 }
 
-// The fp32 model of the primary rays that the culling cones are built from (tile_cone, pixel_cone):
-// camera.py:116-124 + imagetracer.py:56-58 folded into d(x, y) = d0 + x * dx + y * dy (perspective: directions,
-// common origin in `apex`; orthogonal, camera.py:59-78: the same affine model describes the ORIGINS and the
-// "apex" slot carries the common direction).
-static void fill_cone_model(PtKArgs &a, const pt_camera *cam, int width, int height) {
-  const double *m = cam->m, dist = cam->screen_distance, asp = cam->aspect_ratio;
-  for (int r = 0; r < 3; ++r) {
-    a.cone_d0[r] = (float)(m[r * 4 + 0] * dist + m[r * 4 + 1] * asp + m[r * 4 + 2]);
-    a.cone_dx[r] = (float)(m[r * 4 + 1] * (-2.0 * asp / width));
-    a.cone_dy[r] = (float)(m[r * 4 + 2] * (-2.0 / height));
-    a.cone_apex[r] = (float)(m[r * 4 + 0] * -dist + m[r * 4 + 3]);
-    if (cam->kind != PT_CAMERA_PERSPECTIVE) {
-      a.cone_d0[r] = (float)(-m[r * 4 + 0] + m[r * 4 + 1] * asp + m[r * 4 + 2] + m[r * 4 + 3]);
-      a.cone_apex[r] = (float)m[r * 4 + 0];
-    }
-  }
-  a.cam_kind = cam->kind;
-}
-
-// Launch a kernel of the frame on `st`; the LAST one is the render kernel proper (pt_stats.vgprs).  Timing: the
-// frame's first launch carries the start event and its last one the stop event IN the dispatch itself
-// (hipExtLaunchKernelGGL: the events take the kernel's own begin / end timestamps), so a timed frame costs no
-// barrier packet on the stream and the interval holds the frame's kernels, not the launch gaps around them.
 #ifndef PT_WAVES_POINTLIGHT
 #define PT_WAVES_POINTLIGHT 3  // waves per SIMD pt_tile_kernel<POINTLIGHT> is compiled for (register budget 512 / that)
 #endif
-#define PT_LAUNCH(KERNEL, GRID, LDS, LAST, ...)                                                              \
-  do {                                                                                                       \
-    main_fn = (const void *)(KERNEL);                                                                        \
-    hipExtLaunchKernelGGL((KERNEL), dim3(GRID), dim3(PT_BLOCK), LDS, st, ev_started ? nullptr : ev_a,        \
-                          (LAST) ? ev_b : nullptr, 0, __VA_ARGS__);                                          \
-    ev_started = true;                                                                                       \
-  } while (0)
 
-// the scene's tables as the kernels see them (launch(); the probes of ptrace_debug.h)
-static void fill_scene_args(const pt_scene *s, PtKArgs &a) {
+// the shapes' tables alone: what a query of the whole world shape by shape reads (the probes of ptrace_debug.h)
+static void fill_shape_tables(const pt_scene *s, PtKArgs &a) {
   const PtSceneShared &sh = *s->sh;
-  const PtSceneScalars &sc = sh.sc;
   a.recs = sh.recs;
   a.aux = sh.aux;
-  a.hoist = s->hoist;
   a.diag = sh.diag;
+  a.bounds = sh.bounds;
+  pt_fill_shape_counts(a, sh.sc);
+}
+
+// the scene as the kernels see it (launch(), pt_scene_kernel_args, pt_debug_lanes_probe): the tables here, the scalars from
+// pt_frame_args.h
+static void fill_scene_args(const pt_scene *s, PtKArgs &a) {
+  const PtSceneShared &sh = *s->sh;
+  fill_shape_tables(s, a);
+  a.hoist = s->hoist;
   a.hoist_diag = s->hoist_diag;
   a.queue = s->queue;
-  a.bounds = sh.bounds;
   a.bsoa = sh.bsoa;
-  a.bs_stride = sc.bs_stride;
-  for (int q = 0; q < 3; ++q) a.bs_rmax[q] = sc.bs_rmax[q];
-  a.gs_stride = sc.gs_stride;
-  a.cs_stride = sc.cs_stride;
-  a.bs_levels = sc.bs_levels && sc.n_spheres >= pt_tuning().levels_min;
   a.grid_cells = sh.grid_cells;
   a.grid_occ = sh.grid_occ;
   a.grid_balls = sh.grid_balls;
   a.grid_slots = sh.grid_slots;
   a.grid_always = sh.grid_always;
-  a.grid_n_always = sc.grid_n_always;
-  a.grid_far_eo = sc.grid_far_eo;
-  a.grid_occ_lds = -1;
-  a.scene_lds = -1;
-  for (int q = 0; q < 3; ++q) {
-    a.grid_res[q] = sc.grid_res[q];
-    a.grid_min[q] = sc.grid_min[q];
-    a.grid_max[q] = sc.grid_max[q];
-    a.grid_cell[q] = sc.grid_cell[q];
-    a.grid_inv[q] = sc.grid_inv[q];
-  }
-  a.n_diag = sc.n_diag;
   a.lights = sh.lights;
   a.tex = sh.tex;
   a.tex_data = sh.tex_data;
-  a.n_shapes = sc.n_shapes;
-  a.n_spheres = sc.n_spheres;
-  a.n_lights = sc.n_lights;
+  pt_fill_scene_scalars(a, sh.sc, pt_tuning());
 }
 
 // The scene's block for a library of kernels built from this tree but linked into another shared object (ptrace_rays.hip:
@@ -497,8 +456,264 @@ static int refresh_cold(ColdArgs &c, const PtKArgs &a, hipStream_t st) {
   return PT_OK;
 }
 
+// ---- a frame's launches -------------------------------------------------------------------------------------------------------
+// The kernels of one frame on its stream; the LAST one launched is the render kernel proper (pt_stats.vgprs).  Timing: the
+// frame's first launch carries the start event and its last one the stop event IN the dispatch itself (hipExtLaunchKernel,
+// the call hipExtLaunchKernelGGL makes: the events take the kernel's own begin / end timestamps), so a timed frame costs no
+// barrier packet on the stream and the interval holds the frame's kernels, not the launch gaps around them.
+struct FrameLaunches {
+  hipStream_t st;
+  hipEvent_t ev_a, ev_b;  // null: the frame is not timed
+  bool started = false;
+  const void *main_fn = nullptr;
+  void operator()(const void *fn, dim3 grid, size_t lds, bool last, void **args) {
+    main_fn = fn;
+    (void)hipExtLaunchKernel(fn, grid, dim3(PT_BLOCK), args, lds, st, started ? nullptr : ev_a, last ? ev_b : nullptr, 0);
+    started = true;
+  }
+};
+
+// The variants of a kernel by what the plan names (one or two of its fields); the last row is the one for everything else.
+// The tables stand where the frame launches from them, in the order the variants were always named in: the order in which
+// this file first names its kernels is the order of the device code (build.code_hash).
+struct KernelRow {
+  int a, b;
+  const void *fn;
+  template <typename F>
+  KernelRow(int a_, int b_, F *f) : a(a_), b(b_), fn((const void *)f) {}
+};
+template <size_t N>
+static const void *pick(const KernelRow (&rows)[N], int a, int b = 0) {
+  for (size_t i = 0; i + 1 < N; ++i)
+    if (rows[i].a == a && rows[i].b == b) return rows[i].fn;
+  return rows[N - 1].fn;
+}
+
+// the per-shape constants of a perspective camera's primary rays, unless the handle holds this camera's already
+static void enqueue_hoist(pt_scene *s, const pt_camera *cam, const PtKArgs &a, hipStream_t st) {
+  if (s->hoist_valid && s->hoist_stream == st && memcmp(&s->hoist_cam, cam, sizeof(pt_camera)) == 0) return;
+  double o[3];
+  pt_hoist_origin(cam, o);
+  const V3 w = {o[0], o[1], o[2]};
+  hipLaunchKernelGGL(pt_prep_hoist, dim3((a.n_shapes + 255) / 256), dim3(256), 0, st, a.recs, s->hoist, s->hoist_diag, a.n_shapes, a.n_diag, w);
+  s->hoist_cam = *cam;
+  s->hoist_valid = true;
+  s->hoist_stream = st;
+}
+
+// render.py:100-101: every primary call returns Color(0, 0, 0) without a world query
+static int enqueue_zero_frame(pt_scene *s, const pt_params *p, void *out_dev, hipStream_t st) {
+  HIP_TRY(hipEventRecord(s->ev0, st));
+  HIP_TRY(hipMemsetAsync(out_dev, 0, pt_output_bytes(p), st));
+  HIP_TRY(hipEventRecord(s->ev1, st));
+  if (s->count_rays) {
+    HIP_TRY(hipMemsetAsync(s->ray_counter, 0, 2 * sizeof(unsigned long long), st));
+    HIP_TRY(hipMemcpyAsync(s->ray_counter_host, s->ray_counter, 2 * sizeof(unsigned long long), hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipEventRecord(s->ev_count, st));
+    s->count_pending = true;
+  }
+  return PT_OK;
+}
+
+// The handle's buffers as this frame needs them (grow-only), and their pointers in the block.  The workspace (argument block
+// copy, hoisted constants, region/cell tables, frame stack, ray partials) is shared by all launches of a handle.
+static int frame_buffers(pt_scene *s, const pt_params *p, const PtPlan &pl, PtKArgs &a, hipStream_t st) {
+  if (s->count_rays) {
+    size_t have = (size_t)s->ray_partials_n * 2;
+    int rc = ensure(&s->ray_partials, &have, (size_t)(pl.grid + pl.grid_first + pl.grid_q) * 2, st);
+    s->ray_partials_n = (int)(have / 2);
+    if (rc) return rc;
+    a.ray_counter = s->ray_partials;
+  }
+  if (p->renderer == PT_RENDERER_PATHTRACER) {
+    // the queue block (head, unit counts, F; pt_path.h: pt_unit_scatter) starts every frame zeroed: by the path
+    // kernel of the frame before (it clears the OTHER block), by a memset after anything went wrong in between
+    a.qpar = s->queue_parity;
+    s->queue_last = s->queue + (size_t)a.qpar * PT_QUEUE_WORDS;
+    if (!s->queue_clean) HIP_TRY(hipMemsetAsync(s->queue_last, 0, PT_QUEUE_WORDS * sizeof(unsigned long long), st));
+    s->queue_clean = false;  // (true again once this frame's path kernel is enqueued)
+    size_t have = s->ws_bytes / sizeof(double);
+    int rc = ensure(&s->ws, &have, (pl.ws_bytes + sizeof(double) - 1) / sizeof(double), st);
+    s->ws_bytes = have * sizeof(double);
+    if (rc) return rc;
+    a.ws = s->ws;
+  }
+  // path tracer: per-region masks/keys from the first pass, work units for the second from pt_unit_scatter
+  if (pl.path_tiled) {
+    int rc = ensure(&s->region_keys, &s->region_keys_cap, (size_t)pl.nregions, st);
+    if (!rc) rc = ensure(&s->region_mask, &s->region_mask_cap, (size_t)pl.nregions, st);
+    if (!rc) rc = ensure(&s->units, &s->units_cap, (size_t)pl.units_need, st);
+    if (!rc && pl.q_alt) rc = ensure(&s->handover, &s->handover_doubles, pl.handover_doubles, st);
+    if (!rc && pl.q_alt) rc = ensure(&s->units_handed, &s->units_handed_n, (size_t)pl.handover_cap, st);
+    if (rc) return rc;
+    a.units = s->units;
+    a.region_keys = s->region_keys;
+    a.region_mask = s->region_mask;
+    a.handover = s->handover;
+    a.units_handed = s->units_handed;
+    s->last_handover_cap = a.handover_cap;
+  }
+  // large scenes: two-level culling (cells of PT_CELL x PT_CELL global pixels, then 8x8 tiles)
+  if (pl.hier) {
+    int rc = ensure(&s->cell_list, &s->cell_list_cap, (size_t)pl.ncells * pl.cell_stride, st);
+    if (!rc) rc = ensure(&s->cell_count, &s->cell_count_cap, (size_t)pl.ncells, st);
+    if (rc) return rc;
+    a.cell_list = s->cell_list;
+    a.cell_count = s->cell_count;
+  }
+  return PT_OK;
+}
+
+// large scenes: every cell's survivors, in front of the kernel whose tiles cull from them
+static int enqueue_cells(pt_scene *s, const PtPlan &pl, PtKArgs &a, FrameLaunches &go) {
+  if (pl.cell_chunk_len > PT_CELL_CHUNK) return fail(PT_ERR_INVALID, "internal: cell chunk exceeds its LDS staging");
+  HIP_TRY(hipMemsetAsync(s->cell_count, 0, (size_t)pl.ncells * sizeof(int), go.st));
+  int chunks = pl.cell_chunks, chunk_len = pl.cell_chunk_len;
+  void *args[] = {&a, &chunks, &chunk_len};
+  go((const void *)pt_cell_kernel, dim3(pl.cell_groups * pl.cell_chunks), 0, false, args);
+  return PT_OK;
+}
+
+// a hit-record frame: the tile kernel's culling modes, or every shape through world_query
+static int enqueue_hits(pt_scene *s, const PtPlan &pl, bool cull, PtKArgs &a, int channels, FrameLaunches &go) {
+  const size_t lds = cull ? pl.lds_tile : 0;
+  s->stats.lds_bytes = (int)lds;
+  if (cull && pl.hier)
+    if (int rc = enqueue_cells(s, pl, a, go)) return rc;
+  // pt_hits_kernel<HIER, ORTHO, CULL> (pt_hits.h) by (cull, then: pl.tile_mode with it, pl.ortho without)
+  static const KernelRow hits[] = {
+      {0, 1, pt_hits_kernel<false, true, false>}, {0, 0, pt_hits_kernel<false, false, false>},
+      {1, PT_TILE_HIER, pt_hits_kernel<true, false, true>}, {1, PT_TILE_ORTHO, pt_hits_kernel<false, true, true>},
+      {1, PT_TILE_PLAIN, pt_hits_kernel<false, false, true>}};
+  void *args[] = {&a, &channels};
+  go(pick(hits, cull, cull ? pl.tile_mode : (int)pl.ortho), dim3(pl.grid), lds, true, args);
+  return PT_OK;
+}
+
+// small worlds, 16x16 tiles: the shapes' records ride in LDS for shading (Flat; OnOff reads none of them)
+static int enqueue_tile4(pt_scene *s, const PtPlan &pl, int R, PtKArgs &a, FrameLaunches &go) {
+  s->stats.lds_bytes = (int)pl.lds_main;
+  // pt_tile4_kernel<renderer, LDS> by (renderer, pl.t4lds)
+  static const KernelRow tile4[] = {{PT_RENDERER_ONOFF, 0, pt_tile4_kernel<PT_RENDERER_ONOFF, false>},
+                                    {PT_RENDERER_FLAT, 1, pt_tile4_kernel<PT_RENDERER_FLAT, true>},
+                                    {PT_RENDERER_FLAT, 0, pt_tile4_kernel<PT_RENDERER_FLAT, false>}};
+  const bool staged = R != PT_RENDERER_ONOFF && pl.t4lds;
+  if (staged) {
+    // the staged variant copies recs[] and aux[] with 16-byte global -> LDS loads, in PT_TILE4_STAGE_ROUNDS unrolled rounds:
+    // both tables and the dynamic LDS block (it follows the kernel's static LDS) must be 16-byte aligned, the image must fit
+    static int static_lds = -1;  // (a property of the code: looked up once)
+    if (static_lds < 0) {
+      hipFuncAttributes fa;
+      HIP_TRY(hipFuncGetAttributes(&fa, tile4[1].fn));
+      static_lds = (int)fa.sharedSizeBytes;
+    }
+    if ((((uintptr_t)a.recs | (uintptr_t)a.aux) & 15) != 0 || (static_lds & 15) != 0)
+      return fail(PT_ERR_INVALID, "internal: pt_tile4_kernel<FLAT, LDS> needs 16-byte aligned shape tables and LDS");
+    if (pl.lds_main > (size_t)PT_TILE4_STAGE_ROUNDS * (PT_BLOCK / 64) * 1024)
+      return fail(PT_ERR_INVALID, "internal: scene image exceeds pt_tile4_kernel's staging copy");
+  }
+  void *args[] = {&a};
+  go(pick(tile4, R, staged), dim3(pl.grid4_x, pl.grid4_y, 1), pl.lds_main, true, args);
+  return PT_OK;
+}
+
+// 8x8 tiles: the frame of OnOff / Flat / PointLight, the path tracer's first pass
+static int enqueue_tiles(pt_scene *s, const PtPlan &pl, int R, PtKArgs &a, FrameLaunches &go) {
+  s->stats.lds_bytes = (int)pl.lds_tile;
+  if (pl.hier)
+    if (int rc = enqueue_cells(s, pl, a, go)) return rc;
+  // pt_tile_kernel<renderer, waves, HIER, ORTHO, BLOCKS> by (renderer, pl.tile_mode)
+  static const KernelRow tiles[] = {
+      {PT_RENDERER_ONOFF, PT_TILE_HIER, pt_tile_kernel<PT_RENDERER_ONOFF, 4, true>},
+      {PT_RENDERER_ONOFF, PT_TILE_ORTHO, pt_tile_kernel<PT_RENDERER_ONOFF, 4, false, true>},
+      {PT_RENDERER_ONOFF, PT_TILE_PLAIN, pt_tile_kernel<PT_RENDERER_ONOFF, 4, false>},
+      {PT_RENDERER_FLAT, PT_TILE_HIER, pt_tile_kernel<PT_RENDERER_FLAT, 4, true>},
+      {PT_RENDERER_FLAT, PT_TILE_ORTHO, pt_tile_kernel<PT_RENDERER_FLAT, 4, false, true>},
+      {PT_RENDERER_FLAT, PT_TILE_PLAIN, pt_tile_kernel<PT_RENDERER_FLAT, 4, false>},
+      {PT_RENDERER_POINTLIGHT, PT_TILE_HIER, pt_tile_kernel<PT_RENDERER_POINTLIGHT, PT_WAVES_POINTLIGHT, true>},
+      {PT_RENDERER_POINTLIGHT, PT_TILE_ORTHO, pt_tile_kernel<PT_RENDERER_POINTLIGHT, PT_WAVES_POINTLIGHT, false, true>},
+      {PT_RENDERER_POINTLIGHT, PT_TILE_PLAIN, pt_tile_kernel<PT_RENDERER_POINTLIGHT, PT_WAVES_POINTLIGHT, false>},
+      {PT_RENDERER_PATHTRACER, PT_TILE_BLOCKS, pt_tile_kernel<PT_RENDERER_PATHTRACER, 4, false, false, true>},
+      {PT_RENDERER_PATHTRACER, PT_TILE_HIER, pt_tile_kernel<PT_RENDERER_PATHTRACER, 4, true>},
+      {PT_RENDERER_PATHTRACER, PT_TILE_ORTHO, pt_tile_kernel<PT_RENDERER_PATHTRACER, 4, false, true>},
+      {PT_RENDERER_PATHTRACER, PT_TILE_PLAIN, pt_tile_kernel<PT_RENDERER_PATHTRACER, 4, false>}};
+  int pgrid = pl.path_tiled ? pl.grid : 0;  // (the first pass is told the second pass's grid)
+  void *args[] = {&a, &pgrid};
+  go(pick(tiles, R, pl.tile_mode), dim3(pl.path_tiled ? pl.grid_first : pl.grid), pl.lds_tile, !pl.path_tiled, args);
+  return PT_OK;
+}
+
+// the path tracer's second pass: the pixels the first one flagged, fullest regions first
+static int enqueue_second_pass(pt_scene *s, const PtPlan &pl, PtKArgs &a, bool measured, FrameLaunches &go) {
+  const hipStream_t st = go.st;
+  if (pl.tree)  // one pixel per unit: "64 lanes per pixel, whatever the number of flagged pixels"
+    hipLaunchKernelGGL(pt_unit_scatter, dim3(pl.grid_scatter), dim3(PT_SCATTER_BLOCK), 0, st, s->region_keys, s->region_mask, pl.nregions,
+                       s->units, (int)s->units_cap, s->queue_last, (long long)1 << 60, 64, 1, pl.q_min, pl.q_budget_per_flagged, pl.q_budget_min);
+  else
+    hipLaunchKernelGGL(pt_unit_scatter, dim3(pl.grid_scatter), dim3(PT_SCATTER_BLOCK), 0, st, s->region_keys, s->region_mask, pl.nregions,
+                       s->units, (int)s->units_cap, s->queue_last, pl.lanes_cap, pl.nsamp, (long long)pl.min_rounds);
+  if (pl.q_alt) {
+    // num_of_rays > 1: the one-queue kernel IN FRONT of the tree kernel, with an argument block of its own; it returns at once
+    // unless PT_Q_CHOICE says 1, and then leaves the pixels over its budget to the tree kernel behind it (PT_Q_HEAVY)
+    PtKArgs aq = pt_one_queue_args(a, pl);
+    aq.cold = s->args2.dev;
+    if (int rc = refresh_cold(s->args2, aq, st)) return rc;
+    static const KernelRow alts[] = {
+        {PT_ALT_FLAGGED_LEAN_LDS, 0, pt_path_flagged_kernel<1, 1>}, {PT_ALT_FLAGGED_LEAN_SPLIT, 0, pt_path_flagged_kernel<1, 2>},
+        {PT_ALT_FLAGGED_SPLIT, 0, pt_path_flagged_kernel<0, 2>}, {PT_ALT_FLAGGED_LDS, 0, pt_path_flagged_kernel<0, 1>}};
+    const void *alt = pick(alts, pl.alt);
+    HIP_TRY(path_lds_limit(alt, pl.lds_q));
+    void *args[] = {&aq};
+    go(alt, dim3(pl.grid_q), pl.lds_q, false, args);
+  }
+  static const KernelRow seconds[] = {
+      {PT_SECOND_TREE_LEAN, 0, pt_path_tree_kernel<true>}, {PT_SECOND_TREE_LEAN_SCENE, 0, pt_path_tree_kernel<true, true>},
+      {PT_SECOND_TREE, 0, pt_path_tree_kernel<false>}, {PT_SECOND_REGIONS_LDS_SCENE_LEAN, 0, pt_path_regions_kernel<true, true, 1>},
+      {PT_SECOND_REGIONS_LDS_SCENE, 0, pt_path_regions_kernel<true, true>}, {PT_SECOND_REGIONS_LDS_NOGRID, 0, pt_path_regions_kernel<true, false, 2>},
+      {PT_SECOND_REGIONS_LDS, 0, pt_path_regions_kernel<true>}, {PT_SECOND_REGIONS_HBM, 0, pt_path_regions_kernel<false>}};
+  const void *second = pick(seconds, pl.second);
+  HIP_TRY(path_lds_limit(second, pl.lds_main));
+  void *args[] = {&a};
+  go(second, dim3(pl.grid), pl.lds_main, true, args);
+  // (pt_stats.vgprs: the tree kernel's; pt_stats.kernel follows the device's choice, see fold_stats -- only when the frame
+  // is measured at all: a frame loop with timing and counting off enqueues neither the copy nor its event)
+  if (pl.q_alt && measured) {
+    HIP_TRY(hipMemcpyAsync(s->ray_counter_host + 2, s->queue_last + PT_Q_CHOICE, sizeof(unsigned long long), hipMemcpyDeviceToHost, st));
+    s->choice_pending = true;
+  }
+  return PT_OK;
+}
+
+// no tile culling at all (worlds of fewer than four shapes, PTRACE_CULL=0): a lane per pixel
+static void enqueue_untiled(const PtPlan &pl, int R, PtKArgs &a, FrameLaunches &go) {
+  void *args[] = {&a};
+  if (R == PT_RENDERER_PATHTRACER) {
+    go((const void *)pt_path_kernel, dim3(pl.grid), 0, true, args);
+    return;
+  }
+  // pt_simple_kernel<renderer, HOIST> by (renderer, pl.simple_hoist)
+  static const KernelRow simple[] = {
+      {PT_RENDERER_ONOFF, 1, pt_simple_kernel<PT_RENDERER_ONOFF, true>}, {PT_RENDERER_ONOFF, 0, pt_simple_kernel<PT_RENDERER_ONOFF, false>},
+      {PT_RENDERER_FLAT, 1, pt_simple_kernel<PT_RENDERER_FLAT, true>}, {PT_RENDERER_FLAT, 0, pt_simple_kernel<PT_RENDERER_FLAT, false>},
+      {PT_RENDERER_POINTLIGHT, 1, pt_simple_kernel<PT_RENDERER_POINTLIGHT, true>}, {PT_RENDERER_POINTLIGHT, 0, pt_simple_kernel<PT_RENDERER_POINTLIGHT, false>}};
+  go(pick(simple, R, pl.simple_hoist), dim3(pl.grid), 0, true, args);
+}
+
+// registers per lane of a kernel (hipFuncGetAttributes; looked up once per kernel)
+static int kernel_vgprs(const void *fn) {
+  static std::vector<std::pair<const void *, int>> known;
+  for (const auto &kv : known)
+    if (kv.first == fn) return kv.second;
+  hipFuncAttributes fa;
+  const int regs = hipFuncGetAttributes(&fa, fn) == hipSuccess ? fa.numRegs : 0;
+  (void)hipGetLastError();
+  known.push_back({fn, regs});
+  return regs;
+}
+
 // launch() = plan (pt_plan.h: a pure function of the scene's facts, the camera, the parameters and the tuning table) +
-// enqueue (this function: buffers, the argument block, the launches the plan names -- no decision is taken here).
+// argument block (pt_frame_args.h: a pure function of the same and the plan) + enqueue (here and in the helpers above: the
+// handle's buffers, the launches the plan names, the bookkeeping of pt_stats -- no decision is taken here).
 // hits_channels >= 0: a hit-record frame (pt_render_hits; pt_hits_plan.h) of those channels instead of the renderer's colours.
 static int launch(pt_scene *s, const pt_camera *cam, const pt_params *p, void *out_dev, hipStream_t st, int hits_channels = -1) {
   const PtTuning &tn = pt_tuning();
@@ -512,43 +727,11 @@ static int launch(pt_scene *s, const pt_camera *cam, const pt_params *p, void *o
   PtKArgs a;
   memset(&a, 0, sizeof a);
   fill_scene_args(s, a);
-  a.bs_levels = pl.bs_levels;
-  a.dome_shortcut = s->dome_shortcut ? 1 : 0;
+  pt_fill_frame_args(a, cam, p, pl, tn, s->dome_shortcut, s->sh->dome_cands);
   a.out = out_dev;
-  a.cam_kind = cam->kind;
-  memcpy(a.cam_m, cam->m, sizeof a.cam_m);
-  a.cam_dist = cam->screen_distance;
-  a.cam_aspect = cam->aspect_ratio;
-  fill_cone_model(a, cam, p->width, p->height);
-  a.W = p->width;
-  a.H = p->height;
-  a.S = p->samples_per_side;
-  a.N = p->num_of_rays;
-  a.D = p->max_depth;
-  a.rr = p->rr_limit;
-  a.pcg_mode = p->pcg_mode;
-  a.s0 = p->path_state;
-  a.q0 = p->path_seq;
-  if (p->pcg_mode == PT_PCG_SEQ) {  // (OnOff / Flat / PointLight only: check_params)
-    if (p->samples_per_side > 0) {  // the jitter stream of the reference's ImageTracer, entered by jump-ahead per pixel
-      a.s0 = p->jitter_state;
-      a.q0 = p->jitter_seq;
-    } else {
-      a.pcg_mode = PT_PCG_PIXEL;  // pixel-centre rays: no random number is drawn, the alignments coincide
-    }
-  }
-  a.row_block = p->row_block > 0 ? p->row_block : 1;
-  a.n_ranks = p->n_ranks > 0 ? p->n_ranks : 1;
-  a.rank = p->rank;
-  a.out_f32 = p->out_format == PT_OUT_F32;
-  for (int k = 0; k < 3; ++k) {
-    a.bg[k] = p->background[k];
-    a.onoff[k] = p->onoff_color[k];
-    a.ambient[k] = p->ambient[k];
-  }
-  // The scene's workspace (argument block copy, hoisted constants, region/cell tables, frame stack, ray
-  // partials) is shared by all its launches, which are ordered by being on ONE stream.  A launch on another
-  // stream than the previous one first lets that stream drain (host-side wait; a rare event).
+
+  // All launches of a handle are ordered by being on ONE stream.  A launch on another stream than the previous one first
+  // lets that stream drain (host-side wait; a rare event).
   if (s->launched && s->last_stream != st) {
     if (hipStreamSynchronize(s->last_stream) != hipSuccess) (void)hipGetLastError();  // (a destroyed stream has nothing in flight)
   }
@@ -556,138 +739,22 @@ static int launch(pt_scene *s, const pt_camera *cam, const pt_params *p, void *o
   s->launched = true;
   s->count_pending = false;
   s->choice_pending = false;
-  a.rows_local = pl.rows;
-  a.npass = pl.npass;
-  a.npix = pl.npix;
-  s->stats.n_pixels = (uint64_t)a.npix;
-  if (a.npix == 0) return PT_OK;
-
-  a.frame_doubles = pl.frame_doubles;
-  a.diag_lds = pl.diag_lds;
-  a.grid_occ_lds = pl.grid_occ_lds;
-  a.scene_lds = pl.scene_lds;
-  a.nthreads = pl.nthreads;
-  a.block_h = pl.block_h;
+  s->stats.n_pixels = (uint64_t)pl.npix;
+  if (pl.npix == 0) return PT_OK;
   s->stats.grid = pl.grid;
   s->stats.block = PT_BLOCK;
   s->stats.lds_bytes = 0;
   s->stats.kernel = pl.kernel;
-  const int n_count_slots = pl.grid + pl.grid_first + pl.grid_q;
 
-  if (s->count_rays) {
-    size_t have = (size_t)s->ray_partials_n * 2;
-    int rc = ensure(&s->ray_partials, &have, (size_t)n_count_slots * 2, st);
-    s->ray_partials_n = (int)(have / 2);
-    if (rc) return rc;
-    a.ray_counter = s->ray_partials;
-  }
-
-  if (pl.hoist && !(s->hoist_valid && s->hoist_stream == st && memcmp(&s->hoist_cam, cam, sizeof(pt_camera)) == 0)) {
-    V3 o = {-cam->screen_distance, 0.0, 0.0};
-    // camera.py:116-124: origin (-d, 0, 0) through the camera transformation, reference order
-    V3 w;
-    w.x = o.x * cam->m[0] + o.y * cam->m[1] + o.z * cam->m[2] + cam->m[3];
-    w.y = o.x * cam->m[4] + o.y * cam->m[5] + o.z * cam->m[6] + cam->m[7];
-    w.z = o.x * cam->m[8] + o.y * cam->m[9] + o.z * cam->m[10] + cam->m[11];
-    hipLaunchKernelGGL(pt_prep_hoist, dim3((a.n_shapes + 255) / 256), dim3(256), 0, st, a.recs, s->hoist,
-                       s->hoist_diag, a.n_shapes, a.n_diag, w);
-    s->hoist_cam = *cam;
-    s->hoist_valid = true;
-    s->hoist_stream = st;
-  }
-
-  if (pl.zero_frame) {
-    // render.py:100-101: every primary call returns Color(0, 0, 0) without a world query
-    HIP_TRY(hipEventRecord(s->ev0, st));
-    HIP_TRY(hipMemsetAsync(out_dev, 0, pt_output_bytes(p), st));
-    HIP_TRY(hipEventRecord(s->ev1, st));
-    if (s->count_rays) {
-      HIP_TRY(hipMemsetAsync(s->ray_counter, 0, 2 * sizeof(unsigned long long), st));
-      HIP_TRY(hipMemcpyAsync(s->ray_counter_host, s->ray_counter, 2 * sizeof(unsigned long long),
-                             hipMemcpyDeviceToHost, st));
-      HIP_TRY(hipEventRecord(s->ev_count, st));
-      s->count_pending = true;
-    }
-    return PT_OK;
-  }
-  if (p->renderer == PT_RENDERER_PATHTRACER) {
-    // the queue block (head, unit counts, F; pt_path.h: pt_unit_scatter) starts every frame zeroed: by the path
-    // kernel of the frame before (it clears the OTHER block), by a memset after anything went wrong in between
-    a.qpar = s->queue_parity;
-    s->queue_last = s->queue + (size_t)a.qpar * PT_QUEUE_WORDS;
-    if (!s->queue_clean) HIP_TRY(hipMemsetAsync(s->queue_last, 0, PT_QUEUE_WORDS * sizeof(unsigned long long), st));
-    s->queue_clean = false;  // (true again once this frame's path kernel is enqueued)
-    a.p_max_path = pl.p_max_path;
-    a.s_min_path = pl.s_min_path;
-    size_t have = s->ws_bytes / sizeof(double);
-    int rc = ensure(&s->ws, &have, (pl.ws_bytes + sizeof(double) - 1) / sizeof(double), st);
-    s->ws_bytes = have * sizeof(double);
-    if (rc) return rc;
-    a.ws = s->ws;
-  }
-
-  // path tracer: per-region masks/keys from the first pass, work units for the second from pt_unit_scatter
-  if (pl.path_tiled) {
-    int rc = ensure(&s->region_keys, &s->region_keys_cap, (size_t)pl.nregions, st);
-    if (!rc) rc = ensure(&s->region_mask, &s->region_mask_cap, (size_t)pl.nregions, st);
-    if (!rc) rc = ensure(&s->units, &s->units_cap, (size_t)pl.units_need, st);
-    if (rc) return rc;
-    a.units = s->units;
-    a.region_keys = s->region_keys;
-    a.region_mask = s->region_mask;
-    a.spec_draws = pl.spec_draws;
-    a.tree_jump_lds = pl.tree_jump_lds;
-    if (pl.q_alt) {
-      rc = ensure(&s->handover, &s->handover_doubles, pl.handover_doubles, st);
-      if (rc) return rc;
-      rc = ensure(&s->units_handed, &s->units_handed_n, (size_t)pl.handover_cap, st);
-      if (rc) return rc;
-    }
-    a.handover = s->handover;
-    a.units_handed = s->units_handed;
-    a.handover_cap = pl.q_alt ? pl.handover_cap : 0;
-    s->last_handover_cap = a.handover_cap;
-    a.q_budget = 0;  // (the one-queue kernel's block carries these)
-    a.q_tail_budget = 0;
-    a.q_few_lanes = 0;
-    a.dbg_trace_unit = (int)tn.trace_unit;
-    // The sphere the camera is deepest inside (object-space |o'|^2 - 1 most negative, and below -0.5): the
-    // first pass settles, per pixel, what can only hit that sphere (pt_tile_kernel re-checks every condition
-    // from the exact hoisted constants; this only names the candidate).
-    a.dome_slot = -1;
-    if (!pl.ortho && tn.pixel_dome) {
-      const double ox = -cam->screen_distance * cam->m[0] + cam->m[3], oy = -cam->screen_distance * cam->m[4] + cam->m[7],
-                   oz = -cam->screen_distance * cam->m[8] + cam->m[11];
-      double best = -0.5;
-      for (const auto &dc : s->sh->dome_cands) {
-        const double *m = dc.invm;
-        const double px = ox * m[0] + oy * m[1] + oz * m[2] + m[3], py = ox * m[4] + oy * m[5] + oz * m[6] + m[7],
-                     pz = ox * m[8] + oy * m[9] + oz * m[10] + m[11];
-        const double c = px * px + py * py + pz * pz - 1.0;
-        if (c < best) {
-          best = c;
-          a.dome_slot = dc.slot;
-        }
-      }
-    }
-  }
-  // large scenes: two-level culling (cells of PT_CELL x PT_CELL global pixels, then 8x8 tiles)
-  if (pl.hier) {
-    int rc = ensure(&s->cell_list, &s->cell_list_cap, (size_t)pl.ncells * pl.cell_stride, st);
-    if (!rc) rc = ensure(&s->cell_count, &s->cell_count_cap, (size_t)pl.ncells, st);
-    if (rc) return rc;
-    a.cell_list = s->cell_list;
-    a.cell_count = s->cell_count;
-    a.cells_x = pl.cells_x;
-    a.cell_stride = pl.cell_stride;
-  }
+  if (pl.hoist) enqueue_hoist(s, cam, a, st);
+  if (pl.zero_frame) return enqueue_zero_frame(s, p, out_dev, st);
+  if (int rc = frame_buffers(s, p, pl, a, st)) return rc;
   a.cold = s->args.dev;
   if (int rc = refresh_cold(s->args, a, st)) return rc;
-  const void *main_fn = nullptr;  // the render kernel proper (the last one launched), for pt_stats.vgprs
+
   const bool prof = s->timing && s->profiling && (size_t)(2 * s->prof_used + 1) < s->prof.size();
-  const hipEvent_t ev_a = s->timing ? (prof ? s->prof[2 * s->prof_used] : s->ev0) : nullptr;
-  const hipEvent_t ev_b = s->timing ? (prof ? s->prof[2 * s->prof_used + 1] : s->ev1) : nullptr;
-  bool ev_started = false;
+  FrameLaunches go{st, s->timing ? (prof ? s->prof[2 * s->prof_used] : s->ev0) : nullptr,
+                   s->timing ? (prof ? s->prof[2 * s->prof_used + 1] : s->ev1) : nullptr};
   const int R = p->renderer;
 #ifdef PT_DEBUG_TIME
   if (pl.tile4 || ((pl.tile || pl.path_tiled) && R != PT_RENDERER_PATHTRACER)) {
@@ -696,198 +763,29 @@ static int launch(pt_scene *s, const pt_camera *cam, const pt_params *p, void *o
     if (s->queue_parity == 0) s->queue_clean = false;
   }
 #endif
+  int rc = PT_OK;
   if (hits_channels >= 0) {
-    // pt_hits_kernel<HIER, ORTHO, CULL> (pt_hits.h): the tile kernel's culling modes, or every shape through world_query
-    const size_t lds = hits_cull ? pl.lds_tile : 0;
-    s->stats.lds_bytes = (int)lds;
-    if (hits_cull && pl.hier) {
-      if (pl.cell_chunk_len > PT_CELL_CHUNK) return fail(PT_ERR_INVALID, "internal: cell chunk exceeds its LDS staging");
-      HIP_TRY(hipMemsetAsync(s->cell_count, 0, (size_t)pl.ncells * sizeof(int), st));
-      PT_LAUNCH(pt_cell_kernel, pl.cell_groups * pl.cell_chunks, 0, false, a, pl.cell_chunks, pl.cell_chunk_len);
-    }
-    if (!hits_cull && pl.ortho)
-      PT_LAUNCH((pt_hits_kernel<false, true, false>), pl.grid, lds, true, a, hits_channels);
-    else if (!hits_cull)
-      PT_LAUNCH((pt_hits_kernel<false, false, false>), pl.grid, lds, true, a, hits_channels);
-    else if (pl.tile_mode == PT_TILE_HIER)
-      PT_LAUNCH((pt_hits_kernel<true, false, true>), pl.grid, lds, true, a, hits_channels);
-    else if (pl.tile_mode == PT_TILE_ORTHO)
-      PT_LAUNCH((pt_hits_kernel<false, true, true>), pl.grid, lds, true, a, hits_channels);
-    else
-      PT_LAUNCH((pt_hits_kernel<false, false, true>), pl.grid, lds, true, a, hits_channels);
+    rc = enqueue_hits(s, pl, hits_cull, a, hits_channels, go);
   } else if (pl.tile4) {
-    // small worlds: the shapes' records ride in LDS for shading (Flat; OnOff reads none of them)
-    s->stats.lds_bytes = (int)pl.lds_main;
-    const dim3 grid4(pl.grid4_x, pl.grid4_y, 1);
-#define PT_LAUNCH4(R_, L_)                                                                                                  \
-  do {                                                                                                                      \
-    main_fn = (const void *)pt_tile4_kernel<R_, L_>;                                                                        \
-    hipExtLaunchKernelGGL((pt_tile4_kernel<R_, L_>), grid4, dim3(PT_BLOCK), pl.lds_main, st, ev_a, ev_b, 0, a);             \
-  } while (0)
-    if (R == PT_RENDERER_ONOFF)
-      PT_LAUNCH4(PT_RENDERER_ONOFF, false);
-    else if (pl.t4lds) {
-      // the staged variant copies recs[] and aux[] with 16-byte global -> LDS loads, in PT_TILE4_STAGE_ROUNDS unrolled rounds:
-      // both tables and the dynamic LDS block (it follows the kernel's static LDS) must be 16-byte aligned, the image must fit
-      static int static_lds = -1;  // (a property of the code: looked up once)
-      if (static_lds < 0) {
-        hipFuncAttributes fa;
-        HIP_TRY(hipFuncGetAttributes(&fa, (const void *)pt_tile4_kernel<PT_RENDERER_FLAT, true>));
-        static_lds = (int)fa.sharedSizeBytes;
-      }
-      if ((((uintptr_t)a.recs | (uintptr_t)a.aux) & 15) != 0 || (static_lds & 15) != 0)
-        return fail(PT_ERR_INVALID, "internal: pt_tile4_kernel<FLAT, LDS> needs 16-byte aligned shape tables and LDS");
-      if (pl.lds_main > (size_t)PT_TILE4_STAGE_ROUNDS * (PT_BLOCK / 64) * 1024)
-        return fail(PT_ERR_INVALID, "internal: scene image exceeds pt_tile4_kernel's staging copy");
-      PT_LAUNCH4(PT_RENDERER_FLAT, true);
-    } else
-      PT_LAUNCH4(PT_RENDERER_FLAT, false);
-#undef PT_LAUNCH4
+    rc = enqueue_tile4(s, pl, R, a, go);
   } else if (pl.tile || pl.path_tiled) {
-    const size_t lds = pl.lds_tile;
-    s->stats.lds_bytes = (int)lds;
-    const int tgrid = pl.path_tiled ? pl.grid_first : pl.grid;
-    const bool last = !pl.path_tiled;
-    const int pgrid = pl.path_tiled ? pl.grid : 0;  // (the first pass is told the second pass's grid)
-    if (pl.hier) {
-      if (pl.cell_chunk_len > PT_CELL_CHUNK) return fail(PT_ERR_INVALID, "internal: cell chunk exceeds its LDS staging");
-      HIP_TRY(hipMemsetAsync(s->cell_count, 0, (size_t)pl.ncells * sizeof(int), st));
-      PT_LAUNCH(pt_cell_kernel, pl.cell_groups * pl.cell_chunks, 0, false, a, pl.cell_chunks, pl.cell_chunk_len);
-    }
-    // pt_tile_kernel<renderer, waves, HIER, ORTHO, BLOCKS>
-#define PT_TILE_MODES(R_, W_)                                                                              \
-  do {                                                                                                     \
-    if (pl.tile_mode == PT_TILE_HIER)                                                                      \
-      PT_LAUNCH((pt_tile_kernel<R_, W_, true>), tgrid, lds, last, a, pgrid);                               \
-    else if (pl.tile_mode == PT_TILE_ORTHO)                                                                \
-      PT_LAUNCH((pt_tile_kernel<R_, W_, false, true>), tgrid, lds, last, a, pgrid);                        \
-    else                                                                                                   \
-      PT_LAUNCH((pt_tile_kernel<R_, W_, false>), tgrid, lds, last, a, pgrid);                              \
-  } while (0)
-    if (R == PT_RENDERER_ONOFF)
-      PT_TILE_MODES(PT_RENDERER_ONOFF, 4);
-    else if (R == PT_RENDERER_FLAT)
-      PT_TILE_MODES(PT_RENDERER_FLAT, 4);
-    else if (R == PT_RENDERER_POINTLIGHT)
-      PT_TILE_MODES(PT_RENDERER_POINTLIGHT, PT_WAVES_POINTLIGHT);
-    else if (pl.tile_mode == PT_TILE_BLOCKS)
-      PT_LAUNCH((pt_tile_kernel<PT_RENDERER_PATHTRACER, 4, false, false, true>), tgrid, lds, last, a, pgrid);
-    else
-      PT_TILE_MODES(PT_RENDERER_PATHTRACER, 4);
-#undef PT_TILE_MODES
-    if (pl.path_tiled) {
-      // second pass: the pixels the first one flagged, fullest regions first
-      if (pl.tree)  // one pixel per unit: "64 lanes per pixel, whatever the number of flagged pixels"
-        hipLaunchKernelGGL(pt_unit_scatter, dim3(pl.grid_scatter), dim3(PT_SCATTER_BLOCK), 0, st, s->region_keys, s->region_mask, pl.nregions,
-                           s->units, (int)s->units_cap, s->queue_last, (long long)1 << 60, 64, 1, pl.q_min, pl.q_budget_per_flagged, pl.q_budget_min);
-      else
-        hipLaunchKernelGGL(pt_unit_scatter, dim3(pl.grid_scatter), dim3(PT_SCATTER_BLOCK), 0, st, s->region_keys, s->region_mask, pl.nregions,
-                           s->units, (int)s->units_cap, s->queue_last, pl.lanes_cap, pl.nsamp, (long long)pl.min_rounds);
-      if (pl.q_alt) {
-        // num_of_rays > 1: the one-queue kernel IN FRONT of the tree kernel, with an argument block of its own (a lane per
-        // pixel: 20 doubles per depth and lane, its own grid, its own slots for the ray counts); it returns at once unless
-        // PT_Q_CHOICE says 1, and then leaves the pixels over its budget to the tree kernel behind it (PT_Q_HEAVY)
-        PtKArgs aq = a;
-        aq.cold = s->args2.dev;
-        aq.nthreads = pl.grid_q * PT_BLOCK;
-        aq.frame_doubles = 20;
-        aq.p_max_path = pl.q_p_max_path;
-        aq.s_min_path = pl.q_s_min_path;
-        aq.count_base = pl.grid + pl.grid_first;
-        aq.q_budget = pl.q_budget;
-        aq.q_tail_budget = pl.q_tail_budget;
-        aq.q_few_lanes = pl.q_few_lanes;
-        aq.scene_lds = -1;
-        aq.grid_occ_lds = -1;
-        aq.diag_lds = pl.q_diag_lds;
-        aq.ws = s->ws;
-        if (int rc = refresh_cold(s->args2, aq, st)) return rc;
-#define PT_ALT(K_)                                              \
-  do {                                                          \
-    HIP_TRY(path_lds_limit((const void *)(K_), pl.lds_q));      \
-    PT_LAUNCH((K_), pl.grid_q, pl.lds_q, false, aq);            \
-  } while (0)
-        switch (pl.alt) {
-          case PT_ALT_FLAGGED_LEAN_LDS: PT_ALT((pt_path_flagged_kernel<1, 1>)); break;
-          case PT_ALT_FLAGGED_LEAN_SPLIT: PT_ALT((pt_path_flagged_kernel<1, 2>)); break;
-          case PT_ALT_FLAGGED_SPLIT: PT_ALT((pt_path_flagged_kernel<0, 2>)); break;
-          default: PT_ALT((pt_path_flagged_kernel<0, 1>)); break;
-        }
-#undef PT_ALT
-      }
-      const bool last2 = true;
-#define PT_SECOND(K_)                                               \
-  do {                                                              \
-    HIP_TRY(path_lds_limit((const void *)(K_), pl.lds_main));       \
-    PT_LAUNCH((K_), pl.grid, pl.lds_main, last2, a);                \
-  } while (0)
-      switch (pl.second) {
-        case PT_SECOND_TREE_LEAN: PT_SECOND((pt_path_tree_kernel<true>)); break;
-        case PT_SECOND_TREE_LEAN_SCENE: PT_SECOND((pt_path_tree_kernel<true, true>)); break;
-        case PT_SECOND_TREE: PT_SECOND((pt_path_tree_kernel<false>)); break;
-        case PT_SECOND_REGIONS_LDS_SCENE_LEAN: PT_SECOND((pt_path_regions_kernel<true, true, 1>)); break;
-        case PT_SECOND_REGIONS_LDS_SCENE: PT_SECOND((pt_path_regions_kernel<true, true>)); break;
-        case PT_SECOND_REGIONS_LDS_NOGRID: PT_SECOND((pt_path_regions_kernel<true, false, 2>)); break;
-        case PT_SECOND_REGIONS_LDS: PT_SECOND((pt_path_regions_kernel<true>)); break;
-        default: PT_SECOND((pt_path_regions_kernel<false>)); break;
-      }
-#undef PT_SECOND
-      // (pt_stats.vgprs: the tree kernel's; pt_stats.kernel follows the device's choice, see fold_stats -- only when the frame
-      // is measured at all: a frame loop with timing and counting off enqueues neither the copy nor its event)
-      if (pl.q_alt && (s->timing || s->count_rays || prof)) {
-        HIP_TRY(hipMemcpyAsync(s->ray_counter_host + 2, s->queue_last + PT_Q_CHOICE, sizeof(unsigned long long), hipMemcpyDeviceToHost, st));
-        s->choice_pending = true;
-      }
-    }
-  } else if (R == PT_RENDERER_PATHTRACER) {
-    PT_LAUNCH(pt_path_kernel, pl.grid, 0, true, a);
+    rc = enqueue_tiles(s, pl, R, a, go);
+    if (!rc && pl.path_tiled) rc = enqueue_second_pass(s, pl, a, s->timing || s->count_rays || prof, go);
   } else {
-#define PT_SIMPLE(R_)                                                              \
-  do {                                                                             \
-    if (pl.simple_hoist)                                                           \
-      PT_LAUNCH((pt_simple_kernel<R_, true>), pl.grid, 0, true, a);                \
-    else                                                                           \
-      PT_LAUNCH((pt_simple_kernel<R_, false>), pl.grid, 0, true, a);               \
-  } while (0)
-    if (R == PT_RENDERER_ONOFF)
-      PT_SIMPLE(PT_RENDERER_ONOFF);
-    else if (R == PT_RENDERER_FLAT)
-      PT_SIMPLE(PT_RENDERER_FLAT);
-    else
-      PT_SIMPLE(PT_RENDERER_POINTLIGHT);
-#undef PT_SIMPLE
+    enqueue_untiled(pl, R, a, go);
   }
+  if (rc) return rc;
   HIP_TRY(hipGetLastError());
-  if (p->renderer == PT_RENDERER_PATHTRACER) {  // its path kernel is enqueued: the other queue block will be zero
+  if (R == PT_RENDERER_PATHTRACER) {  // its path kernel is enqueued: the other queue block will be zero
     s->queue_parity ^= 1;
     s->queue_clean = true;
   }
-  if (main_fn) {
-    // registers per lane of that kernel (hipFuncGetAttributes; looked up once per kernel)
-    static std::vector<std::pair<const void *, int>> known;
-    int regs = -1;
-    for (const auto &kv : known)
-      if (kv.first == main_fn) regs = kv.second;
-    if (regs < 0) {
-      hipFuncAttributes fa;
-      regs = hipFuncGetAttributes(&fa, main_fn) == hipSuccess ? fa.numRegs : 0;
-      (void)hipGetLastError();
-      known.push_back({main_fn, regs});
-    }
-    s->stats.vgprs = regs;
-  }
-  if (prof) {
-    s->prof_used++;
-    s->stats_valid = false;
-  } else if (s->timing) {
-    s->stats_valid = true;
-  } else {
-    s->stats_valid = false;
-  }
+  if (go.main_fn) s->stats.vgprs = kernel_vgprs(go.main_fn);
+  s->stats_valid = s->timing && !prof;
+  if (prof) s->prof_used++;
   if (s->count_rays) {
-    hipLaunchKernelGGL(pt_sum_counts, dim3(1), dim3(256), 0, st, s->ray_partials, n_count_slots, s->ray_counter);
-    HIP_TRY(hipMemcpyAsync(s->ray_counter_host, s->ray_counter, 2 * sizeof(unsigned long long),
-                           hipMemcpyDeviceToHost, st));
+    hipLaunchKernelGGL(pt_sum_counts, dim3(1), dim3(256), 0, st, s->ray_partials, pl.grid + pl.grid_first + pl.grid_q, s->ray_counter);
+    HIP_TRY(hipMemcpyAsync(s->ray_counter_host, s->ray_counter, 2 * sizeof(unsigned long long), hipMemcpyDeviceToHost, st));
     // ev1 was recorded BEFORE the count left the device: whoever reads ray_counter_host waits for this one
     HIP_TRY(hipEventRecord(s->ev_count, st));
     s->count_pending = true;
@@ -1611,9 +1509,31 @@ extern "C" int pt_debug_read_trace(unsigned long long *out, int n) {
 }
 #endif
 
-// ---- diagnostics (not part of the reference seam): the culling predicate on its own ------------------------
-// keep[i] (by World.shapes index) = would the cull of the primary rays through the image rectangle
-// [x0, x1] x [row0, row1 + 1] keep shape i?  pixel_x >= 0: the same for the cone of the single pixel
+// ---- diagnostics (not part of the reference seam): probes of single device functions, used by the tests ------------------
+// A probe's round trip through ONE device allocation, freed on every way out (Staged): [the block, where the kernel reads its
+// cold half (`a` non-null: it gets `cold` and its device copy) | the input | the output].  launch(in_dev, out_dev) enqueues the
+// kernel on the null stream; then out_bytes come back to `out` and the out2_bytes behind them to `out2`.
+template <typename Launch>
+static int run_probe(PtKArgs *a, const void *in, size_t in_bytes, void *out, size_t out_bytes, Launch launch, void *out2 = nullptr,
+                     size_t out2_bytes = 0) {
+  const size_t head = a ? sizeof(PtKArgs) : 0;
+  Staged m;
+  HIP_TRY(hipMalloc((void **)&m.dev, head + up8(in_bytes) + std::max<size_t>(out_bytes + out2_bytes, 8)));
+  char *in_dev = m.dev + head, *out_dev = in_dev + up8(in_bytes);
+  if (a) {
+    a->cold = (const PtKArgs *)m.dev;
+    HIP_TRY(hipMemcpy(m.dev, a, sizeof *a, hipMemcpyHostToDevice));
+  }
+  if (in_bytes) HIP_TRY(hipMemcpy(in_dev, in, in_bytes, hipMemcpyHostToDevice));
+  launch(in_dev, out_dev);
+  HIP_TRY(hipGetLastError());
+  HIP_TRY(hipMemcpy(out, out_dev, out_bytes, hipMemcpyDeviceToHost));
+  if (out2_bytes) HIP_TRY(hipMemcpy(out2, out_dev + out_bytes, out2_bytes, hipMemcpyDeviceToHost));
+  return PT_OK;
+}
+
+// The culling predicate on its own: keep[i] (by World.shapes index) = would the cull of the primary rays through the image
+// rectangle [x0, x1] x [row0, row1 + 1] keep shape i?  pixel_x >= 0: the same for the cone of the single pixel
 // (pixel_x, pixel_row) inside that tile (pixel_cone, perspective only).  Planes answer 1.
 extern "C" int pt_debug_cull_probe(pt_scene *s, const pt_camera *cam, int width, int height, int x0, int x1, int row0,
                                    int row1, int pixel_x, int pixel_row, int *keep) {
@@ -1622,65 +1542,37 @@ extern "C" int pt_debug_cull_probe(pt_scene *s, const pt_camera *cam, int width,
   PtKArgs a;
   memset(&a, 0, sizeof a);
   fill_cone_model(a, cam, width, height);
-  PtKArgs *a_dev = nullptr;
-  int *keep_dev = nullptr;
-  HIP_TRY(hipMalloc((void **)&a_dev, sizeof a));
-  HIP_TRY(hipMalloc((void **)&keep_dev, sizeof(int) * std::max(1, s->sh->sc.n_shapes)));
-  a.cold = a_dev;
-  a.recs = s->sh->recs;
-  a.bounds = s->sh->bounds;
-  a.n_shapes = s->sh->sc.n_shapes;
-  a.n_spheres = s->sh->sc.n_spheres;
-  HIP_TRY(hipMemcpy(a_dev, &a, sizeof a, hipMemcpyHostToDevice));
-  hipLaunchKernelGGL(pt_cull_probe_kernel, dim3(1), dim3(64), 0, 0, a, x0, x1, row0, row1, pixel_x, pixel_row, keep_dev);
-  HIP_TRY(hipGetLastError());
-  HIP_TRY(hipMemcpy(keep, keep_dev, sizeof(int) * a.n_shapes, hipMemcpyDeviceToHost));
-  (void)hipFree(a_dev);
-  (void)hipFree(keep_dev);
-  return PT_OK;
+  fill_shape_tables(s, a);
+  return run_probe(&a, nullptr, 0, keep, sizeof(int) * a.n_shapes, [&](char *, char *keep_dev) {
+    hipLaunchKernelGGL(pt_cull_probe_kernel, dim3(1), dim3(64), 0, 0, a, x0, x1, row0, row1, pixel_x, pixel_row, (int *)keep_dev);
+  });
 }
 
-// ---- diagnostics (not part of the reference seam): device primitive probe used by the tests -------------
+// device primitives (sqrt, division, libm, the generator): out[i] = op(x[i], y[i])
 extern "C" int pt_debug_probe(int op, const double *x, const double *y, double *out, int n) {
   if (n <= 0 || !x || !out) return fail(PT_ERR_INVALID, "bad probe arguments");
-  double *dx = nullptr, *dy = nullptr, *dout = nullptr;
   const size_t bytes = (size_t)n * sizeof(double);
-  HIP_TRY(hipMalloc((void **)&dx, bytes));
-  HIP_TRY(hipMalloc((void **)&dy, bytes));
-  HIP_TRY(hipMalloc((void **)&dout, bytes));
+  Staged m;
+  HIP_TRY(hipMalloc((void **)&m.dev, 3 * bytes));
+  double *dx = (double *)m.dev, *dy = dx + n, *dout = dy + n;
   HIP_TRY(hipMemcpy(dx, x, bytes, hipMemcpyHostToDevice));
   HIP_TRY(hipMemcpy(dy, y ? y : x, bytes, hipMemcpyHostToDevice));
   hipLaunchKernelGGL(pt_probe_kernel, dim3((n + 255) / 256), dim3(256), 0, 0, op, dx, dy, dout, n);
   HIP_TRY(hipGetLastError());
   HIP_TRY(hipMemcpy(out, dout, bytes, hipMemcpyDeviceToHost));
-  (void)hipFree(dx);
-  (void)hipFree(dy);
-  (void)hipFree(dout);
   return PT_OK;
 }
 
-// ---- diagnostics: the hit record, camera rays and BRDF scattering of the device path on their own ----------------
+// the hit record, camera rays and BRDF scattering of the device path on their own
 extern "C" int pt_debug_hit_probe(pt_scene *s, int shape_index, const double *rays, int n, double *out) {
   if (!s || !rays || !out || n <= 0 || shape_index >= s->sh->sc.n_shapes) return fail(PT_ERR_INVALID, "bad probe arguments");
   HIP_TRY(hipSetDevice(s->device));
   PtKArgs a;
   memset(&a, 0, sizeof a);
-  a.recs = s->sh->recs;
-  a.aux = s->sh->aux;
-  a.diag = s->sh->diag;
-  a.n_shapes = s->sh->sc.n_shapes;
-  a.n_spheres = s->sh->sc.n_spheres;
-  a.n_diag = s->sh->sc.n_diag;
-  double *rd = nullptr, *od = nullptr;
-  HIP_TRY(hipMalloc((void **)&rd, (size_t)n * 8 * sizeof(double)));
-  HIP_TRY(hipMalloc((void **)&od, (size_t)n * 12 * sizeof(double)));
-  HIP_TRY(hipMemcpy(rd, rays, (size_t)n * 8 * sizeof(double), hipMemcpyHostToDevice));
-  hipLaunchKernelGGL(pt_hit_probe_kernel, dim3((n + 63) / 64), dim3(64), 0, 0, a, shape_index, rd, n, od);
-  HIP_TRY(hipGetLastError());
-  HIP_TRY(hipMemcpy(out, od, (size_t)n * 12 * sizeof(double), hipMemcpyDeviceToHost));
-  (void)hipFree(rd);
-  (void)hipFree(od);
-  return PT_OK;
+  fill_shape_tables(s, a);  // (and nothing else of the scene: one shape is queried as a one-record view of these)
+  return run_probe(nullptr, rays, (size_t)n * 8 * sizeof(double), out, (size_t)n * 12 * sizeof(double), [&](char *rd, char *od) {
+    hipLaunchKernelGGL(pt_hit_probe_kernel, dim3((n + 63) / 64), dim3(64), 0, 0, a, shape_index, (const double *)rd, n, (double *)od);
+  });
 }
 
 extern "C" int pt_debug_lanes_probe(pt_scene *s, int anyhit, const double *rays, int n, double *out) {
@@ -1689,67 +1581,32 @@ extern "C" int pt_debug_lanes_probe(pt_scene *s, int anyhit, const double *rays,
   PtKArgs a;
   memset(&a, 0, sizeof a);
   fill_scene_args(s, a);
-  PtKArgs *a_dev = nullptr;
-  double *rd = nullptr, *od = nullptr;
-  HIP_TRY(hipMalloc((void **)&a_dev, sizeof a));
-  HIP_TRY(hipMalloc((void **)&rd, (size_t)n * 8 * sizeof(double)));
-  HIP_TRY(hipMalloc((void **)&od, (size_t)n * 4 * sizeof(double)));
-  a.cold = a_dev;
-  HIP_TRY(hipMemcpy(a_dev, &a, sizeof a, hipMemcpyHostToDevice));
-  HIP_TRY(hipMemcpy(rd, rays, (size_t)n * 8 * sizeof(double), hipMemcpyHostToDevice));
-  if (anyhit)
-    hipLaunchKernelGGL(pt_lanes_probe_kernel<true>, dim3((n + 63) / 64), dim3(64), 0, 0, a, rd, n, od);
-  else
-    hipLaunchKernelGGL(pt_lanes_probe_kernel<false>, dim3((n + 63) / 64), dim3(64), 0, 0, a, rd, n, od);
-  HIP_TRY(hipGetLastError());
-  HIP_TRY(hipMemcpy(out, od, (size_t)n * 4 * sizeof(double), hipMemcpyDeviceToHost));
-  (void)hipFree(a_dev);
-  (void)hipFree(rd);
-  (void)hipFree(od);
-  return PT_OK;
+  return run_probe(&a, rays, (size_t)n * 8 * sizeof(double), out, (size_t)n * 4 * sizeof(double), [&](char *rd, char *od) {
+    if (anyhit)
+      hipLaunchKernelGGL(pt_lanes_probe_kernel<true>, dim3((n + 63) / 64), dim3(64), 0, 0, a, (const double *)rd, n, (double *)od);
+    else
+      hipLaunchKernelGGL(pt_lanes_probe_kernel<false>, dim3((n + 63) / 64), dim3(64), 0, 0, a, (const double *)rd, n, (double *)od);
+  });
 }
 
 extern "C" int pt_debug_camera_probe(const pt_camera *cam, int width, int height, const double *pix, int n, double *out) {
   if (!cam || !pix || !out || n <= 0 || width <= 0 || height <= 0) return fail(PT_ERR_INVALID, "bad probe arguments");
   PtKArgs a;
   memset(&a, 0, sizeof a);
-  a.cam_kind = cam->kind;
-  memcpy(a.cam_m, cam->m, sizeof a.cam_m);
-  a.cam_dist = cam->screen_distance;
-  a.cam_aspect = cam->aspect_ratio;
-  a.W = width;
-  a.H = height;
-  PtKArgs *a_dev = nullptr;
-  double *pd = nullptr, *od = nullptr;
-  HIP_TRY(hipMalloc((void **)&a_dev, sizeof a));
-  HIP_TRY(hipMalloc((void **)&pd, (size_t)n * 4 * sizeof(double)));
-  HIP_TRY(hipMalloc((void **)&od, (size_t)n * 7 * sizeof(double)));
-  a.cold = a_dev;
-  HIP_TRY(hipMemcpy(a_dev, &a, sizeof a, hipMemcpyHostToDevice));
-  HIP_TRY(hipMemcpy(pd, pix, (size_t)n * 4 * sizeof(double), hipMemcpyHostToDevice));
-  hipLaunchKernelGGL(pt_camera_probe_kernel, dim3((n + 63) / 64), dim3(64), 0, 0, a, pd, n, od);
-  HIP_TRY(hipGetLastError());
-  HIP_TRY(hipMemcpy(out, od, (size_t)n * 7 * sizeof(double), hipMemcpyDeviceToHost));
-  (void)hipFree(a_dev);
-  (void)hipFree(pd);
-  (void)hipFree(od);
-  return PT_OK;
+  pt_fill_camera(a, cam, width, height);
+  return run_probe(&a, pix, (size_t)n * 4 * sizeof(double), out, (size_t)n * 7 * sizeof(double), [&](char *pd, char *od) {
+    hipLaunchKernelGGL(pt_camera_probe_kernel, dim3((n + 63) / 64), dim3(64), 0, 0, a, (const double *)pd, n, (double *)od);
+  });
 }
 
 extern "C" int pt_debug_scatter_probe(const double *in, int n, double *out, unsigned long long *state_after) {
   if (!in || !out || !state_after || n <= 0) return fail(PT_ERR_INVALID, "bad probe arguments");
-  double *id = nullptr, *od = nullptr;
-  unsigned long long *sd = nullptr;
-  HIP_TRY(hipMalloc((void **)&id, (size_t)n * 12 * sizeof(double)));
-  HIP_TRY(hipMalloc((void **)&od, (size_t)n * 7 * sizeof(double)));
-  HIP_TRY(hipMalloc((void **)&sd, (size_t)n * sizeof(unsigned long long)));
-  HIP_TRY(hipMemcpy(id, in, (size_t)n * 12 * sizeof(double), hipMemcpyHostToDevice));
-  hipLaunchKernelGGL(pt_scatter_probe_kernel, dim3((n + 63) / 64), dim3(64), 0, 0, id, n, od, sd);
-  HIP_TRY(hipGetLastError());
-  HIP_TRY(hipMemcpy(out, od, (size_t)n * 7 * sizeof(double), hipMemcpyDeviceToHost));
-  HIP_TRY(hipMemcpy(state_after, sd, (size_t)n * sizeof(unsigned long long), hipMemcpyDeviceToHost));
-  (void)hipFree(id);
-  (void)hipFree(od);
-  (void)hipFree(sd);
-  return PT_OK;
+  const size_t out_bytes = (size_t)n * 7 * sizeof(double);
+  return run_probe(
+      nullptr, in, (size_t)n * 12 * sizeof(double), out, out_bytes,
+      [&](char *id, char *od) {
+        hipLaunchKernelGGL(pt_scatter_probe_kernel, dim3((n + 63) / 64), dim3(64), 0, 0, (const double *)id, n, (double *)od,
+                           (unsigned long long *)(od + out_bytes));
+      },
+      state_after, (size_t)n * sizeof(unsigned long long));
 }
