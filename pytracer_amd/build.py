@@ -14,6 +14,7 @@ after libptrace.so, in the order of ``ADDONS`` (csrc/ptrace_NAME.hip, include/pt
 * scatter: BRDF.scatter_ray and the Russian roulette for hit records
 * radiance: the whole ``PathTracer`` recursion for ray batches
 * gather: the mean radiance over the hemisphere of batches of surface points
+* bake: surface points from (shape, u, v), and light maps over a shape's (u, v) grid
 """
 from __future__ import annotations
 
@@ -34,13 +35,20 @@ FLAGS = ["--offload-arch=gfx950", "-O3", "-ffp-contract=off", "-fno-fast-math", 
 # the add-ons, in build order: name -> (sources, library, cuid)
 ADDONS = {name: ([f"ptrace_{name}.hip"], os.path.join(HERE, f"libptrace_{name}.so"), f"libptrace_{name}")
           for name in ("rays", "surface", "scatter", "radiance", "gather")}
-# every library the recipe makes, in build order: what build() and needs_build() walk
+# libptrace.so and the add-ons of interfaces 1.0 - 1.4, in build order
 TARGETS = ((FLAGS, LIB, SOURCES),) + tuple((FLAGS[:-1] + [f"-cuid={cuid}"], lib, sources) for sources, lib, cuid in ADDONS.values())
 (_, (RAYS_FLAGS, RAYS_LIB, RAYS_SOURCES), (SURFACE_FLAGS, SURFACE_LIB, SURFACE_SOURCES), (SCATTER_FLAGS, SCATTER_LIB, SCATTER_SOURCES),
  (RADIANCE_FLAGS, RADIANCE_LIB, RADIANCE_SOURCES), (GATHER_FLAGS, GATHER_LIB, GATHER_SOURCES)) = TARGETS  # (the rows by name)
+# The add-ons since interface 1.5, rows of the same kind.  ADDONS and TARGETS above keep the values they had at interface 1.4
+# (tests/test_gather_host.py pins them: six rows, the gather's last), so what came later is listed here and ALL_TARGETS is what
+# build() and needs_build() walk.
+LATER_ADDONS = {name: ([f"ptrace_{name}.hip"], os.path.join(HERE, f"libptrace_{name}.so"), f"libptrace_{name}") for name in ("bake",)}
+LATER_TARGETS = tuple((FLAGS[:-1] + [f"-cuid={cuid}"], lib, sources) for sources, lib, cuid in LATER_ADDONS.values())
+((BAKE_FLAGS, BAKE_LIB, BAKE_SOURCES),) = LATER_TARGETS
+ALL_TARGETS = TARGETS + LATER_TARGETS
 # every file the translation units include: all of csrc/ (tests/test_host.py checks this list against the #include lines)
 DEPS = sorted(f for f in os.listdir(CSRC) if f.endswith((".hip", ".h"))) + [
-    os.path.join("..", "..", "include", h) for h in ["ptrace.h", "ptrace_debug.h"] + [f"ptrace_{name}.h" for name in ADDONS]]
+    os.path.join("..", "..", "include", h) for h in ["ptrace.h", "ptrace_debug.h"] + [f"ptrace_{name}.h" for name in list(ADDONS) + list(LATER_ADDONS)]]
 
 
 def code_hash(lib: str = LIB) -> str:
@@ -79,17 +87,17 @@ def _hipcc() -> str:
 
 
 def needs_build() -> bool:
-    libs = [lib for _, lib, _ in TARGETS]
+    libs = [lib for _, lib, _ in ALL_TARGETS]
     if not all(os.path.exists(lib) for lib in libs):
         return True
-    t = min(os.path.getmtime(lib) for lib in libs)  # (one list of files for all six: they share the headers)
+    t = min(os.path.getmtime(lib) for lib in libs)  # (one list of files for all seven: they share the headers)
     return any(os.path.getmtime(os.path.join(CSRC, d)) > t for d in DEPS)
 
 
 def build(force: bool = False, verbose: bool = False) -> str:
     if not force and not needs_build():
         return LIB
-    for flags, lib, sources in TARGETS:
+    for flags, lib, sources in ALL_TARGETS:
         cmd = [_hipcc()] + flags + ["-o", lib] + [os.path.join(CSRC, s) for s in sources]
         if verbose:
             print(" ".join(cmd), file=sys.stderr)

@@ -419,8 +419,98 @@ def gather(input_name, output, samples, num_of_rays, max_depth, russian_roulette
                f"wrote {output} ({', '.join(planes)})")
 
 
+def parse_size(text: str):
+    """``WxH`` -> (W, H), both at least 1."""
+    w, x, h = text.lower().partition("x")
+    try:
+        size = (int(w), int(h)) if x else None
+    except ValueError:
+        size = None
+    if size is None or size[0] < 1 or size[1] < 1:
+        raise UsageError(f"--size expects WxH with W and H at least 1, got {text!r}")
+    return size
+
+
+BAKE_WINDOW_SAMPLES = 1 << 24  # hemisphere rays per window of a bake: 512 MiB of sample planes in the workspace
+
+
+@click.command("bake")
+@click.option("--shape", type=int, required=True, help="Index in World.shapes of the shape whose map is baked (a DiffuseBRDF shape)")
+@click.option("--size", type=str, default="256x256", help="Texels of the map over the shape's (u, v) square: WxH")
+@click.option("--samples", type=int, default=64, help="Samples per texel")
+@click.option("--side", type=int, default=1, help="1: the side the shape's local normal points to (a sphere's outside); -1: the other")
+@click.option("--no-jitter", is_flag=True, default=False, help="Every sample at its texel's centre")
+@click.option("--output", "-o", type=str, default="map.pfm", help="Name of the PFM file to create")
+@click.option("--num-of-rays", type=int, default=1, help="Number of rays departing from each surface point below the hemisphere's rays")
+@click.option("--max-depth", type=int, default=3, help="Maximum allowed ray depth")
+@click.option("--russian-roulette-limit", type=int, default=3, help="Depth from which on the Russian roulette runs")
+@click.option("--init-state", type=int, default=45, help="Initial seed of the generators (positive number)")
+@click.option("--init-seq", type=int, default=54,
+              help="Identifier of texel 0's first sequence: sample k of texel t draws from PCG(init_state, init_seq + t * samples + k)")
+@click.option("--depth", type=int, default=1, help="Ray.depth of the hemisphere's rays (1: the children of a camera ray's hit)")
+@click.option("--declare-float", "-d", type=str, multiple=True, help="Declare a variable: --declare-float=VAR:VALUE")
+@click.option("--device", type=int, default=0, help="GPU to bake on")
+@click.argument("input_scene_name", type=str, default="builtin:demo")
+def bake(shape, size, samples, side, no_jitter, output, num_of_rays, max_depth, russian_roulette_limit, init_state, init_seq, depth,
+         declare_float, device, input_scene_name):
+    """The outgoing-radiance map of one diffuse shape: per texel of its (u, v) grid, emitted + brdf colour x the mean radiance
+    arriving over the hemisphere of `samples` points of the texel.  Writes a PFM -- the ImagePigment of scenes.baked_world, with
+    which FlatRenderer renders the shape's converged indirect light."""
+    from . import rays as rb
+
+    try:
+        width, height = parse_size(size)
+        if side not in (1, -1):
+            raise UsageError(f"--side {side}: must be 1 or -1")
+        if samples < 1 or num_of_rays < 1 or max_depth < 0 or depth < 0:
+            raise UsageError("--samples and --num-of-rays must be at least 1, --max-depth and --depth not negative")
+        if max_depth - depth > 64:
+            raise UsageError(f"--max-depth {max_depth} with --depth {depth}: a bake walks at most 64 levels")
+        if width * samples > rb.MAX_RAYS:
+            raise UsageError(f"{width} texels x {samples} samples in one row: a bake window takes at most 2^31 - 1 hemisphere rays")
+        world, _, _ = _load_scene(input_scene_name, parse_float_overrides(declare_float), 640, 480)
+        if not 0 <= shape < len(world.shapes):
+            raise UsageError(f"--shape {shape}: the scene has {len(world.shapes)} shape(s)")
+        if type(world.shapes[shape].material.brdf).__name__ != "DiffuseBRDF":
+            raise UsageError(f"--shape {shape}: a {type(world.shapes[shape].material.brdf).__name__} shape -- what a mirror sends out "
+                             "depends on where it is seen from, a map cannot hold it")
+    except UsageError as e:
+        click.echo(f"pytracer_amd bake: {e}", err=True)
+        sys.exit(2)
+    from types import SimpleNamespace
+
+    import numpy as np
+
+    from . import _lib, flatten
+    from .device import DeviceScene
+
+    _lib.standalone()  # (torch-free, like `render`)
+    rows_per = max(1, BAKE_WINDOW_SAMPLES // (width * samples))
+    out = np.empty((height, width, 3), dtype=np.float64)
+    traced = 0
+    started = perf_counter()
+    with DeviceScene(flatten.flatten_world(world), device) as scene:
+        wq = rb.WorldQueries(scene)
+        centres = rb.texel_centres(width, height)
+        mat = wq.materials(SimpleNamespace(shape_index=np.full((height, width), shape, np.int32), uv=centres))
+        for row0 in range(0, height, rows_per):  # (the texel index is global: the windows are the whole map, bit for bit)
+            h = min(rows_per, height - row0)
+            part = wq.light_map(shape, width, height, samples, side, not no_jitter, (0, row0, width, h), depth, init_state, init_seq,
+                                num_of_rays, max_depth, russian_roulette_limit)
+            out[row0: row0 + h] = np.asarray(mat.emitted)[row0: row0 + h] + np.asarray(mat.brdf_color)[row0: row0 + h] * part.radiance
+            traced += int(part.n_rays.sum())
+    wall = perf_counter() - started
+    image = hm.HdrImage(width, height)
+    image.set_array(out)
+    with open(output, "wb") as f:
+        image.write_pfm(f)
+    click.echo(f"shape {shape}: {width}x{height} texels x {samples} sample(s), {len(world.shapes)} shape(s), {traced} rays traced, "
+               f"{wall:.3f} s: wrote {output}")
+
+
 cli.add_command(render)
 cli.add_command(hits)
 cli.add_command(rays)
 cli.add_command(radiance)
 cli.add_command(gather)
+cli.add_command(bake)

@@ -538,6 +538,106 @@ class DeviceScene:
                                            p(buf), buf.nbytes))
         return rb.GatheredRadiance(buf, n, bits)
 
+    # -- the bake (include/ptrace_bake.h, libptrace_bake.so): surface points from (shape, u, v), light maps over a (u, v) grid ---
+    def surface_points(self, shape, uv, side=None, device: bool = False, stream=None, out=None, n=None):
+        """The world point and the unit normal at ``(u, v)`` of a shape -- the inverse of the shapes' own ``(u, v)`` maps
+        (shapes.py:36-42, 183-185), then ``Transformation.__mul__``, the normal normalised (include/ptrace_bake.h).  ``shape``:
+        ``World.shapes`` indices (outside the scene: the record is zeros), ``uv``: ``[..., 2]``, ``side``: int32 per record
+        (negative: the side the local normal points away from) or ``None`` (+1) -> ``[6, n]`` float64, point xyz then normal xyz:
+        its halves are the ``points`` and ``normals`` of :meth:`gather`.  ``device=True``: ``shape`` (``n`` int32), ``uv`` (two
+        planes of ``n`` doubles) and ``side`` are in HBM as for :meth:`surface`; the batch is enqueued on ``stream`` -> the output
+        ``DeviceBuffer`` (``out``, or a new one)."""
+        from . import _bake_lib, rays as rb
+
+        L, block = _bake_lib.lib(), self.kernel_args()
+        if device:
+            handle = getattr(stream, "handle", stream)
+            n = self._device_count(shape, n)
+            if out is None:
+                from .devmem import DeviceBuffer
+
+                out = DeviceBuffer((6, max(n, 1)), np.float64, self.device)
+            ptr = self._plane_ptr
+            _bake_lib.check(L.pt_rays_surface_points_device(self.device, block, len(block), ptr(shape, "shape"), ptr(uv, "uv"),
+                                                            ptr(side, "side"), n, ptr(out, "out"), int(out.nbytes),
+                                                            C.c_void_p(handle) if handle else None))
+            if hasattr(out, "rendered_on"):
+                out.rendered_on(stream)
+            return out
+        if stream is not None or out is not None or n is not None:
+            raise ValueError("stream=, out= and n= go with device=True (host batches are staged and synchronous)")
+        shape = np.ascontiguousarray(shape, dtype=np.int32).reshape(-1)
+        n = shape.shape[0]
+        uvp = rb.planar(uv, 2)
+        if uvp.shape[1] != n:
+            raise ValueError(f"{n} shape indices but {uvp.shape[1]} (u, v) pairs")
+        if side is not None:
+            side = np.ascontiguousarray(np.asarray(side).reshape(-1), dtype=np.int32)
+            if side.shape != (n,):
+                raise ValueError(f"side must hold one int32 per record ({n}), not {side.shape}")
+        buf = np.empty((6, n), dtype=np.float64)
+        p = lambda a: a.ctypes.data_as(C.c_void_p) if a is not None else None  # noqa: E731
+        _bake_lib.check(L.pt_rays_surface_points(self.device, block, len(block), p(shape), p(uvp), p(side), n, p(buf), buf.nbytes))
+        return buf
+
+    def bake_workspace_bytes(self, width: int, height: int, samples: int, num_of_rays: int = 1, max_depth: int = 10, depth: int = 1,
+                             window=None) -> int:
+        """Bytes of the workspace ``bake(device=True)`` needs for ``window`` (``(col0, row0, w, h)``; ``None``: the whole map) of a
+        ``width x height`` map at ``samples`` samples (``pt_rays_bake_workspace_bytes``: the node stacks, sized by the lanes a launch
+        keeps resident, and four 8-byte planes of ``w * h * samples`` values)."""
+        from . import _bake_lib
+
+        par = _bake_lib.params(0, 1, width, height, window, True, samples, num_of_rays, max_depth, 0, depth, 0, 0, (0.0, 0.0, 0.0))
+        need = int(_bake_lib.lib().pt_rays_bake_workspace_bytes(self.device, C.byref(par)))
+        if need == 0:
+            raise ValueError(f"no workspace size for these arguments: {_bake_lib.last_error()}")
+        return need
+
+    def bake(self, shape: int, width: int, height: int, samples: int, side: int = 1, jitter: bool = True, window=None,
+             init_state: int = 42, init_seq: int = 54, num_of_rays: int = 1, max_depth: int = 10, russian_roulette_limit: int = 3,
+             background=(0.0, 0.0, 0.0), depth: int = 1, channels="all", device: bool = False, stream=None, out=None, workspace=None):
+        """The light map of ``World.shapes[shape]``: per texel of ``window`` (``(col0, row0, w, h)``; ``None``: all) of its
+        ``width x height`` grid over ``(u, v)`` the mean over ``k < samples`` of ``PathTracer(world, background, g, num_of_rays,
+        max_depth, russian_roulette_limit)(DiffuseBRDF.scatter_ray(g, ., p, n, depth))`` with ``g = PCG(init_state, init_seq + t *
+        samples + k)``, ``t`` the texel's index in the WHOLE map, and ``(p, n)`` the surface point at the texel's centre or
+        (``jitter``) at a point of the texel drawn from ``g`` first; summed on the device strictly in ``k`` order
+        (include/ptrace_bake.h).  ``channels``: ``"count"``, ``"all"``, ``"none"`` or ``PT_BAKE_*`` bits
+        -> :class:`pytracer_amd.rays.BakedMap`.  ``device=True``: the bake is enqueued on ``stream`` with ``workspace``
+        (:meth:`bake_workspace_bytes` bytes of device memory; ``None``: a new buffer) and stays in HBM -> the output
+        ``DeviceBuffer`` (``out``, or a new one)."""
+        from . import _bake_lib, rays as rb
+
+        L, block, bits = _bake_lib.lib(), self.kernel_args(), rb.bake_channels(channels)
+        par = _bake_lib.params(shape, side, width, height, window, jitter, samples, num_of_rays, max_depth, russian_roulette_limit, depth,
+                               init_state, init_seq, background)
+        texels = max(par.w, 0) * max(par.h, 0)
+        if device:
+            from .devmem import DeviceBuffer
+
+            handle = getattr(stream, "handle", stream)
+            if out is None:
+                out = DeviceBuffer((max(rb.bake_bytes(texels, bits), 8),), np.uint8, self.device)
+            if workspace is None:
+                # (0: arguments the library refuses -- the call below then says which, with its own error code)
+                need = int(L.pt_rays_bake_workspace_bytes(self.device, C.byref(par)))
+                if need:
+                    workspace = DeviceBuffer((need,), np.uint8, self.device)
+                    out._bake_workspace = workspace  # in flight on `stream` as long as the output is: freed with it
+            ptr = self._plane_ptr
+            _bake_lib.check(L.pt_rays_bake_device(self.device, block, len(block), C.byref(par), bits, ptr(workspace, "workspace"),
+                                                  int(workspace.nbytes) if workspace is not None else 0, ptr(out, "out"), int(out.nbytes),
+                                                  C.c_void_p(handle) if handle else None))
+            if hasattr(out, "rendered_on"):
+                out.rendered_on(stream)
+            if hasattr(workspace, "rendered_on"):
+                workspace.rendered_on(stream)
+            return out
+        if stream is not None or out is not None or workspace is not None:
+            raise ValueError("stream=, out= and workspace= go with device=True (host bakes are staged and synchronous)")
+        buf = np.empty(max(rb.bake_bytes(texels, bits), 8), dtype=np.uint8)
+        _bake_lib.check(L.pt_rays_bake(self.device, block, len(block), C.byref(par), bits, buf.ctypes.data_as(C.c_void_p), buf.nbytes))
+        return rb.BakedMap(buf, par.w, par.h, bits)
+
     def cull_probe(self, cam: abi.Camera, width: int, height: int, x0: int, x1: int, row0: int, row1: int,
                    pixel=None) -> np.ndarray:
         """Diagnostics: which shapes (by ``World.shapes`` index) the conservative cull of the primary rays through

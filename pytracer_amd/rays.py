@@ -23,6 +23,12 @@ texel), ``samples`` cosine-weighted rays per record made, walked and averaged on
 ``DeviceScene.gather`` (include/ptrace_gather.h, libptrace_gather.so) or ``WorldQueries.hemisphere_radiance``:
 :class:`GatheredRadiance` views the answer.
 
+Its seventh -- the bake: a light map over a shape's ``(u, v)`` grid, every texel the gather of ``samples`` points INSIDE the texel
+(the surface points are made on the device from ``(shape, u, v)``; a map baked in windows is the map baked whole) -- goes
+through ``DeviceScene.surface_points`` / ``DeviceScene.bake`` (include/ptrace_bake.h, libptrace_bake.so) or
+``WorldQueries.surface_points`` / ``light_map`` / ``outgoing_map``: :class:`BakedMap` views the answer, and
+``scenes.baked_world`` turns maps into a world ``FlatRenderer`` renders with its indirect light in place.
+
 Layout: planar.  A batch is ``[8, n]`` float64 -- origin xyz, direction xyz, tmin, tmax, the fields of ``Ray`` (ray.py:29-50);
 a result is one buffer, the int32 shape plane first (padded to 8 bytes), then the selected fp64 planes of ``n`` values each.
 """
@@ -54,6 +60,10 @@ _RAD_OF = {"pcg": RAD_PCG, "count": RAD_COUNT}
 
 GATHER_COUNT, GATHER_ALL = 1, 1  # PT_GATHER_* of include/ptrace_gather.h
 _GATHER_OF = {"count": GATHER_COUNT}
+
+
+BAKE_COUNT, BAKE_ALL = 1, 1  # PT_BAKE_* of include/ptrace_bake.h
+_BAKE_OF = {"count": BAKE_COUNT}
 
 
 def _parse_channels(channels, names_to_bits, all_bits, what) -> int:
@@ -488,6 +498,70 @@ class GatheredRadiance(_BatchViews):
         return out
 
 
+def bake_channels(channels) -> int:
+    """``PT_BAKE_*`` bits from an int, a name (``"count"``), ``"all"`` or ``"none"``."""
+    return _parse_channels(channels, _BAKE_OF, BAKE_ALL, "bake")
+
+
+def bake_bytes(texels: int, channels: int) -> int:
+    """Mirror of ``pt_rays_bake_bytes`` (``texels`` = w * h of the baked rectangle): 0 for arguments the library refuses."""
+    if not (0 <= texels <= MAX_RAYS and 0 <= channels <= BAKE_ALL):
+        return 0
+    return texels * 8 * (3 + (1 if channels & BAKE_COUNT else 0))
+
+
+def bake_plane_offset(texels: int, channels: int, channel: int, component: int = 0) -> int:
+    """Mirror of ``pt_rays_bake_plane_offset`` (bytes; ``channel`` 0: the three radiance planes, ``BAKE_COUNT``; < 0: not
+    selected)."""
+    if not (0 <= texels <= MAX_RAYS and 0 <= channels <= BAKE_ALL) or component < 0:
+        return -1
+    if channel == 0:
+        return texels * 8 * component if component < 3 else -1
+    if channel == BAKE_COUNT and channels & BAKE_COUNT:
+        return texels * 24 if component < 1 else -1
+    return -1
+
+
+class BakedMap(_BatchViews):
+    """Views over the buffer of a bake (``buf``: ``pt_rays_bake_bytes(w * h)`` bytes, contiguous ``uint8``) of a ``w x h``
+    rectangle of texels, row-major: row ``r`` is ``v``, column ``c`` is ``u`` -- an ``ImagePigment``'s ``(col, row)``.  Nothing here
+    copies.  ``radiance``: ``[h, w, 3]``, per texel the mean of ``PathTracer(...)(ray)`` over its samples, summed in sample order;
+    ``n_rays``: ``[h, w]`` uint64, the rays handed to a world query for the texel."""
+
+    _names, _all, _what, _unit = _BAKE_OF, BAKE_ALL, "bake", "texels"
+    _bytes, _offset = staticmethod(bake_bytes), staticmethod(bake_plane_offset)
+
+    def __init__(self, buf, width: int, height: int, channels=BAKE_ALL):
+        self.width, self.height = int(width), int(height)
+        super().__init__(buf, self.width * self.height, channels, (self.height, self.width))
+        self.radiance = np.moveaxis(self.buffer[: self.n * 24].view(np.float64).reshape((3,) + self.shape), 0, -1)
+
+    def has(self, name: str) -> bool:  # (any other name is a channel this bake does not have, not an error)
+        return name in _BAKE_OF and super().has(name)
+
+    @property
+    def n_rays(self) -> np.ndarray:
+        return self._plane_views(BAKE_COUNT, 1, np.uint64)[0].reshape(self.shape)
+
+    def planes(self) -> dict:
+        """name -> view, for every selected channel."""
+        out = {"radiance": self.radiance}
+        if self.has("count"):
+            out["n_rays"] = self.n_rays
+        return out
+
+
+def texel_centres(width: int, height: int, window=None) -> np.ndarray:
+    """``[h, w, 2]``: ``(u, v)`` at the centres of the texels of ``window`` (``(col0, row0, w, h)``; ``None``: all) of a
+    ``width x height`` map, as the bake forms them: ``(col + 0.5) * (1.0 / width)``, ``(row + 0.5) * (1.0 / height)``."""
+    col0, row0, w, h = (0, 0, int(width), int(height)) if window is None else (int(x) for x in window)
+    u = (np.arange(col0, col0 + w, dtype=np.float64) + 0.5) * (1.0 / int(width))
+    v = (np.arange(row0, row0 + h, dtype=np.float64) + 0.5) * (1.0 / int(height))
+    out = np.empty((h, w, 2), dtype=np.float64)
+    out[..., 0], out[..., 1] = u[None, :], v[:, None]
+    return out
+
+
 def stream_numbers(seqs) -> np.ndarray:
     """``uint64[n]`` from stream numbers of any size and sign, wrapped into the 64-bit range as :func:`pcg_streams` wraps them
     (a signed array like the C cast; Python ints modulo 2^64): the ``seqs`` plane of a gather batch."""
@@ -613,3 +687,44 @@ class WorldQueries:
         out = self.scene.gather(planar(points, 3), planar(normals, 3), samples, init_state, seqs, active, num_of_rays, max_depth,
                                 russian_roulette_limit, background, depth, bits, init_seq=init_seq)
         return GatheredRadiance(out.buffer, out.n, bits, shape=shape)
+
+    def surface_points(self, shape, uv, side=1):
+        """The world point and unit normal at ``uv`` (``[..., 2]``) of ``World.shapes[shape]`` (``shape``: one index, or one per
+        record), on the side the shape's local normal points to (``side=1``) or the other (``-1``; one value, or one per record)
+        -> ``(points, normals)``, each ``[..., 3]``: what :meth:`hemisphere_radiance` takes as ``hits`` and ``normals=``."""
+        uv = np.asarray(uv, dtype=np.float64)
+        if uv.ndim < 1 or uv.shape[-1] != 2:
+            raise ValueError(f"uv must be [..., 2], not {uv.shape}")
+        lead = uv.shape[:-1]
+        n = int(np.prod(lead, dtype=np.int64))
+        shapes = np.broadcast_to(np.asarray(shape, dtype=np.int32), lead).reshape(-1)
+        sides = np.broadcast_to(np.asarray(side, dtype=np.int32), lead).reshape(-1)
+        out = self.scene.surface_points(shapes, uv.reshape(n, 2), sides)
+        return out[0:3].T.reshape(lead + (3,)), out[3:6].T.reshape(lead + (3,))
+
+    def light_map(self, shape: int, width: int, height: int, samples: int, side: int = 1, jitter: bool = True, window=None,
+                  depth: int = 1, init_state: int = 42, init_seq: int = 54, num_of_rays: int = 1, max_depth: int = 10,
+                  russian_roulette_limit: int = 3, background=(0.0, 0.0, 0.0), channels="all") -> BakedMap:
+        """The light map of ``World.shapes[shape]`` over its ``(u, v)`` square, ``width x height`` texels (or the ``window``
+        ``(col0, row0, w, h)`` of them): per texel the mean radiance arriving over the hemisphere of ``samples`` points of the
+        texel (``jitter=False``: its centre), texel ``t`` of the whole map drawing from the streams ``init_seq + t * samples +
+        k`` -- a map baked in windows is the map baked whole.  ``depth``: the hemisphere rays' ``Ray.depth``; the default 1 means
+        they are the children of a depth-0 hit, a camera ray's.  The other parameters are ``PathTracer``'s -> :class:`BakedMap`."""
+        return self.scene.bake(shape, width, height, samples, side, jitter, window, init_state, init_seq, num_of_rays, max_depth,
+                               russian_roulette_limit, background, depth, channels)
+
+    def outgoing_map(self, shape: int, width: int, height: int, samples: int, side: int = 1, jitter: bool = True, **kw) -> np.ndarray:
+        """``[height, width, 3]``: what a ``DiffuseBRDF`` shape sends out at every texel, ``emitted(uv_c) + brdf_color(uv_c) *
+        light_map`` with the material's colours at the texel centres ``uv_c`` (:meth:`materials`) -- render.py:139 for a hit there,
+        with the converged mean in place of ``num_of_rays`` children.  Composed on the host.  ``kw``: :meth:`light_map`'s."""
+        from types import SimpleNamespace
+
+        kw.pop("window", None)
+        kw["channels"] = "none"
+        centres = texel_centres(width, height)
+        index = np.full(centres.shape[:-1], int(shape), dtype=np.int32)
+        mat = self.materials(SimpleNamespace(shape_index=index, uv=centres))
+        if not np.all(np.asarray(mat.brdf_kind) == abi.BRDF_DIFFUSE):
+            raise ValueError(f"shape {shape} has no DiffuseBRDF: what a mirror sends out depends on where it is seen from, a map cannot hold it")
+        baked = self.light_map(shape, width, height, samples, side, jitter, **kw)
+        return np.asarray(mat.emitted) + np.asarray(mat.brdf_color) * np.asarray(baked.radiance)

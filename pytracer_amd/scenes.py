@@ -7,7 +7,7 @@ from __future__ import annotations
 
 from typing import Tuple
 
-from .hostmodel import (PCG, CheckeredPigment, Color, DiffuseBRDF, Material, PerspectiveCamera, Plane,
+from .hostmodel import (PCG, CheckeredPigment, Color, DiffuseBRDF, HdrImage, ImagePigment, Material, PerspectiveCamera, Plane,
                         PointLight, SpecularBRDF, Sphere, Transformation, UniformPigment, Vec, World,
                         rotation_y, rotation_z, scaling, translation)
 
@@ -77,3 +77,36 @@ def demo_world(clock: float = 150.0) -> Tuple[World, PerspectiveCamera]:
     camera = PerspectiveCamera(screen_distance=1.0, aspect_ratio=1.0,
                                transformation=_as_parsed(rotation_z(30.0), translation(Vec(-4.0, 0.0, 1.0))))
     return world, camera
+
+
+def baked_world(world, maps) -> World:
+    """``world`` with the outgoing radiance of some of its shapes baked in: ``maps`` is ``{shape_index: [H, W, 3] array}``
+    (``WorldQueries.outgoing_map``), and every listed shape comes back with the material ``DiffuseBRDF(UniformPigment(BLACK))``,
+    ``emitted_radiance = ImagePigment(map)`` -- row ``r`` of the map is ``v``, column ``c`` is ``u``, the pigment's ``(col, row)``.
+    ``FlatRenderer`` returns ``pigment + emitted_radiance`` (render.py:72-74), so it renders such a shape as its map, texel for
+    texel.  Everything else -- the other shapes, the transformations, the lights -- stays as it was; ``world`` is not modified."""
+    import numpy as np
+
+    shapes = list(world.shapes)
+    out = World()
+    for light in getattr(world, "point_lights", []):
+        out.add_light(light)
+    unknown = [i for i in maps if not 0 <= int(i) < len(shapes)]
+    if unknown:
+        raise ValueError(f"the world has {len(shapes)} shapes; no shape {unknown[0]}")
+    by_index = {int(i): m for i, m in maps.items()}
+    for i, shape in enumerate(shapes):
+        if i not in by_index:
+            out.add_shape(shape)
+            continue
+        arr = np.asarray(by_index[i], dtype=np.float64)
+        if arr.ndim != 3 or arr.shape[2] != 3 or arr.shape[0] < 1 or arr.shape[1] < 1:
+            raise ValueError(f"the map of shape {i} must be [H, W, 3], not {arr.shape}")
+        image = HdrImage(arr.shape[1], arr.shape[0])
+        image.set_array(arr)
+        material = Material(DiffuseBRDF(UniformPigment(BLACK)), ImagePigment(image))
+        kind = {"Sphere": Sphere, "Plane": Plane}.get(type(shape).__name__)
+        if kind is None:
+            raise ValueError(f"shape {i} is a {type(shape).__name__}: a map is baked for a Sphere or a Plane")
+        out.add_shape(kind(shape.transformation, material))
+    return out

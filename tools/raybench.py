@@ -42,7 +42,18 @@ with ``num_of_rays`` 2.  Beside each, in the same process, the route a caller ha
 rays and their generators made beforehand in HBM (the scatter query on records that name a diffuse shape; not timed), then
 ``pt_rays_radiance_device`` on them, timed the same way; the host's sum of that output in sample order is compared with the gather's
 output bit for bit.  Last, the time of the radiance query with ``num_of_rays = K`` on ONE ray per record (the frame's primary ray):
-another estimator -- one generator per record, K children at every depth -- reported for comparison."""
+another estimator -- one generator per record, K children at every depth -- reported for comparison.
+
+    python tools/raybench.py --bake [--map 512 --samples 16 --repeats 5 ...]
+
+The bake query (libptrace_bake.so: pt_rays_bake_device): a ``--map x --map`` light map at ``--samples`` samples of the first diffuse
+sphere of C2 behind its sky sphere, ``num_of_rays=1``, ``max_depth=3``, limit 3, depth 1, with and without jitter.  Beside it, in
+the same process, the gather query on the same texel-centre records, prepared in HBM by ``pt_rays_surface_points_device`` (timed
+on its own, not part of the gather's time), at the same K and the same streams: the centre-mode bake must equal it bit for bit.
+The three are timed ALTERNATING, ``--repeats`` rounds of ``--warmup`` + ``--steps`` launches each between two events; printed are
+every round's time, the median per query and the spread of the rounds (max - min over the median).  Then the purpose as two
+times: the flat frame of the baked ``demo`` world (its ground plane and sky carrying their outgoing maps) beside the path-traced
+frame of ``demo`` at the CLI's defaults (640x480, ``num_of_rays=10``, ``max_depth=3``), kernel times from ``stats()``."""
 import argparse
 import ctypes as C
 import os
@@ -63,7 +74,13 @@ def main():
     ap.add_argument("--scatter", action="store_true", help="time the bounce (roulette + scatter_ray) and the PathTracerShader route")
     ap.add_argument("--radiance", action="store_true", help="time the radiance query beside the chain in HBM and the fused path tracer")
     ap.add_argument("--gather", action="store_true", help="time the gather query beside path_radiance on the same sample rays prepared in HBM")
+    ap.add_argument("--bake", action="store_true", help="time the bake query beside the gather on the same texel-centre records prepared in HBM")
+    ap.add_argument("--map", type=int, default=512, help="--bake: texels per side of the map")
+    ap.add_argument("--samples", type=int, default=16, help="--bake: samples per texel")
+    ap.add_argument("--repeats", type=int, default=5, help="--bake: alternating rounds per query")
     args = ap.parse_args()
+    if args.bake:
+        return bake(args)
     if args.gather:
         return gather(args)
     if args.radiance:
@@ -438,6 +455,99 @@ def gather(args):
             tree_rays = int(rb.RayRadiance(tout.numpy(), m, "count").n_rays.sum())
             print(f"    radiance query, num_of_rays={K} on one primary ray per record (another estimator): {tree_ms:9.3f} ms, {tree_rays} rays "
                   f"traced, {tree_rays / tree_ms / 1e3:.1f} Mray/s")
+    return 0 if ok else 1
+
+
+def bake(args):
+    import torch
+
+    from pytracer_amd import abi, flatten, hostmodel as hm, rays as rb, scenes
+    from pytracer_amd.device import DeviceScene
+    from pytracer_amd.devmem import DeviceBuffer, DeviceSpan
+
+    M, K, N, D, LIMIT, DEPTH, BG, S0, Q0 = args.map, args.samples, 1, 3, 3, 1, (0.1, 0.2, 0.3), 45, 54
+    flat = flatten.flatten_world(scenes.synthetic_world(32, with_plane=True))
+    shape = next(i for i in range(1, flat.n_shapes) if flat.kind[i] == abi.SHAPE_SPHERE and flat.brdf_kind[i] == abi.BRDF_DIFFUSE)
+    texels = M * M
+    ok = True
+    with DeviceScene(flat) as ds:
+        stream = torch.cuda.Stream()
+        st = stream.cuda_stream
+
+        def timed(go):
+            for _ in range(args.warmup):
+                go()
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record(stream)
+            for _ in range(args.steps):
+                go()
+            e1.record(stream)
+            e1.synchronize()
+            return e0.elapsed_time(e1) / args.steps
+
+        # the gather's records: the texel centres' surface points, made in HBM
+        uv = np.ascontiguousarray(np.moveaxis(rb.texel_centres(M, M), -1, 0)).reshape(2, texels)
+        uv_dev = torch.from_numpy(uv).cuda()
+        shape_dev = torch.full((texels,), shape, dtype=torch.int32, device="cuda")
+        points = DeviceBuffer((6, texels), np.float64)
+        torch.cuda.synchronize()
+        points_ms = timed(lambda: ds.surface_points(shape_dev, uv_dev, None, device=True, stream=st, out=points))
+        pts, nrm = DeviceSpan(points, 24 * texels, 0), DeviceSpan(points, 24 * texels, 24 * texels)
+        gws = DeviceBuffer((ds.gather_workspace_bytes(texels, K, N, D, DEPTH),), np.uint8)
+        gout = DeviceBuffer((rb.gather_bytes(texels, rb.GATHER_ALL),), np.uint8)
+        bws = DeviceBuffer((ds.bake_workspace_bytes(M, M, K, N, D, DEPTH),), np.uint8)
+        bout = DeviceBuffer((rb.bake_bytes(texels, rb.BAKE_ALL),), np.uint8)
+        queries = {
+            "gather on the centres' records": lambda: ds.gather(pts, nrm, K, S0, None, None, N, D, LIMIT, BG, DEPTH, "all", init_seq=Q0,
+                                                                 device=True, stream=st, out=gout, workspace=gws, n=texels),
+            "bake, centres (no jitter)": lambda: ds.bake(shape, M, M, K, 1, False, None, S0, Q0, N, D, LIMIT, BG, DEPTH, "all", device=True,
+                                                         stream=st, out=bout, workspace=bws),
+            "bake, jitter": lambda: ds.bake(shape, M, M, K, 1, True, None, S0, Q0, N, D, LIMIT, BG, DEPTH, "all", device=True, stream=st,
+                                            out=bout, workspace=bws),
+        }
+        rounds = {name: [] for name in queries}
+        kept = {}
+        for _ in range(args.repeats):  # alternating: a drift of the machine meets all three alike
+            for name, go in queries.items():
+                rounds[name].append(timed(go))
+                kept[name] = (gout if name.startswith("gather") else bout).numpy().copy()
+        print(f"C2, shape {shape} (a diffuse sphere): {M}x{M} texels x {K} samples = {texels * K} hemisphere rays, num_of_rays={N}, max_depth={D}, "
+              f"limit={LIMIT}, depth={DEPTH}; {args.repeats} alternating rounds of {args.warmup} warm-up + {args.steps} timed launches")
+        print(f"surface_points for the {texels} texel centres: {points_ms:.3f} ms (not part of the gather's time)")
+        med = {}
+        for name, ms in rounds.items():
+            med[name] = float(np.median(ms))
+            traced = int(kept[name][24 * texels:].view(np.uint64).sum())
+            print(f"{name:32s} median {med[name]:9.3f} ms  spread {(max(ms) - min(ms)) / med[name]:6.2%}  rounds {' '.join(f'{x:.3f}' for x in ms)}  "
+                  f"{traced} rays traced, {traced / med[name] / 1e3:.1f} Mray/s")
+        same = kept["bake, centres (no jitter)"].tobytes() == kept["gather on the centres' records"].tobytes()
+        ok = ok and same
+        base = med["gather on the centres' records"]
+        print(f"bake / gather: centres {med['bake, centres (no jitter)'] / base:.3f} x, jitter {med['bake, jitter'] / base:.3f} x (bar: 1.25 x); the centre-mode "
+              f"map {'equals' if same else 'DIFFERS FROM'} the gather's output bit for bit")
+    # the purpose, as two times: the baked demo world under FlatRenderer beside the path tracer at the CLI's defaults
+    W, H = 640, 480
+    world, camera = scenes.demo_world()
+    cam = flatten.flatten_camera(hm.PerspectiveCamera(screen_distance=1.0, aspect_ratio=W / H, transformation=camera.transformation))
+    with DeviceScene(flatten.flatten_world(world)) as ds:
+        wq = rb.WorldQueries(ds)
+        maps = {i: wq.outgoing_map(i, 256, 256, 64, init_state=S0, num_of_rays=1, max_depth=3) for i in (0, 1)}
+        par = abi.make_params(W, H, abi.RENDERER_PATHTRACER, samples_per_side=1, num_of_rays=10, max_depth=3, pcg_mode=abi.PCG_SAMPLE,
+                              path_state=45, path_seq=54)
+        path_ms = []
+        for _ in range(args.warmup + args.steps):
+            ds.render(cam, par)
+            path_ms.append(ds.stats().kernel_ms)
+    with DeviceScene(flatten.flatten_world(scenes.baked_world(world, maps))) as ds:
+        par = abi.make_params(W, H, abi.RENDERER_FLAT, samples_per_side=0)
+        flat_ms = []
+        for _ in range(args.warmup + 10 * args.steps):
+            ds.render(cam, par)
+            flat_ms.append(ds.stats().kernel_ms)
+        kernel = ds.stats().kernel
+    path, flat_t = float(np.median(path_ms[args.warmup:])), float(np.median(flat_ms[args.warmup:]))
+    print(f"demo {W}x{H}: path-traced frame (num_of_rays=10, max_depth=3) kernels {path:.3f} ms; flat frame of the baked world (planes 0 and 1 "
+          f"as 256x256 maps at 64 samples) kernel {flat_t * 1e3:.1f} us (kernel {kernel}): {path / flat_t:.0f} x")
     return 0 if ok else 1
 
 
