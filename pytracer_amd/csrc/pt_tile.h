@@ -986,17 +986,21 @@ __global__ __launch_bounds__(PT_BLOCK) __attribute__((amdgpu_waves_per_eu(PT_TIL
   constexpr int TH = 16;  // tile height
   constexpr bool ANYHIT = RENDERER == PT_RENDERER_ONOFF;
 #ifdef PT_DEBUG_TIME
-  // cycles of this wave in: 0 prologue, 1 cone, 2 cull, 3 dome tile, 4 rays, 5 query, 6 shade, 7 store
+  // cycles of this wave in: 0 prologue, 1 cone, 2 cull, 3 dome tile, 4 rays, 5 query, 6 shade, 7 store, 8 the wait at the barrier
+  // (its own figure: it is the other waves' time, not this wave's query)
   // (Flat: 6 is the uniform pixels and the loop over the wave's patterned winners with their stores, 7 the per-pixel
   //  remainder behind the loop)
-  unsigned long long tsum[8] = {0, 0, 0, 0, 0, 0, 0, 0}, tprev = __builtin_amdgcn_s_memtime();
+  unsigned long long tsum[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0}, tprev = __builtin_amdgcn_s_memtime();
 #define PT_T4(k) do { const unsigned long long tn = __builtin_amdgcn_s_memtime(); tsum[k] += tn - tprev; tprev = tn; } while (0)
 #else
 #define PT_T4(k) do { } while (0)
 #endif
   const int lane = threadIdx.x & 63, wib = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
-  // ---- everything the front end reads from memory is asked for in ONE batch behind the kernel arguments: every field of
-  //      the cold block that cone, cull and shortcut need, the lane's bounding sphere, the staging copy ----
+  // ---- what cone, cull and shortcut read from memory is asked for behind the kernel arguments: the cold block's fields for
+  //      them, the lane's bounding sphere, the staging copy.  As compiled, the scalar loads stand in two groups in between the
+  //      staging copy's exec-masked blocks, one wait each; the camera of the fp64 rays is read at the rays, three more round
+  //      trips.  Reading it here as well, or making the rays in front of the cone, was measured level or slower
+  //      (profiles/DROPPED_VARIANTS.md): a wave waits for its SIMD's VALU far more than for these trips. ----
   int W, rows_local, npass, n_ranks, row_block, rank, dome_sw, f32_sw, cam_kind;
   ConeCam cam;
   pt_kargs c0 = cold_args(a);
@@ -1019,8 +1023,10 @@ __global__ __launch_bounds__(PT_BLOCK) __attribute__((amdgpu_waves_per_eu(PT_TIL
   if constexpr (SLDS) {
     // recs[] then aux[] into LDS, straight from global memory (no register in between), 16 bytes per lane: chunk c is the
     // bytes [1024 c, 1024 c + 1024) of the image, wave w takes the chunks w, w + 4, ...  128 n is a multiple of 16, so no lane
-    // straddles the two tables; lanes past the image are switched off.  Nothing waits for these loads here: the one
-    // barrier in front of the shading retires them.
+    // straddles the two tables; lanes past the image are switched off.  The barrier in front of the shading is what
+    // needs them; as compiled, the cull's wait for the lane's bounding sphere (s_waitcnt vmcnt(0): loads in exec-masked blocks
+    // cannot be counted) retires them first, ~5 kcycles after they were issued.  The copy stays HERE: its ~120 instructions run
+    // while the wave waits for its scalar loads anyway; issued behind the cull it cost 0.65 us per frame (DROPPED_VARIANTS.md).
     const int nrec = a.n_shapes * (int)sizeof(PtShapeRec), nimg = nrec + a.n_shapes * (int)sizeof(PtShapeAux);
     const char *src_rec = (const char *)a.recs, *src_aux = (const char *)a.aux - nrec;
 #pragma unroll
@@ -1147,9 +1153,19 @@ __global__ __launch_bounds__(PT_BLOCK) __attribute__((amdgpu_waves_per_eu(PT_TIL
         pt_kargs c = cold_args(a);
         const double dist = c->cam_dist, aspect = c->cam_aspect;
         const double Wd = (double)c->W, Hd = (double)c->H;
-        const int growA = gr0 + (crA - lr0), growB = gr0 + (crB - lr0);
-        const double uA = ((double)ccA + 0.5) / Wd, uB = ((double)ccB + 0.5) / Wd;
-        const double vA = 1.0 - ((double)growA + 0.5) / Hd, vB = 1.0 - ((double)growB + 0.5) / Hd;
+        // u = (column + 0.5) / W depends on the column only, v on the row only, and a tile has sixteen of each: ONE fp64 division
+        // per lane makes all 32 quotients (lanes 0 - 15 and 32 - 47: column j = lane & 15; lanes 16 - 31 and 48 - 63: row j; clamped
+        // as ccA .. crB are) and every lane fetches its four with ds_bpermute.  The operands of each division are those the lane
+        // itself would use, so the quotients are bit for bit the same.  The wave is limited by what its SIMD's VALU issues, not
+        // by this chain: four divisions per lane (a v_rcp_f64 and fourteen more instructions each) were 4 % of a wave's VALU
+        // instructions (profiles/r10_tile4_front_ab.txt).  The whole wave is active here (`valid`, `done`: wave-uniform).
+        const int qj = lane & 15;
+        const bool qrow = (lane & 16) != 0;
+        const int qcol = tx * 16 + qj, qlrow = lr0 + qj;
+        const int qcc = qcol < W ? qcol : W - 1, qcr = qlrow < rows_local ? qlrow : rows_local - 1;
+        const double quot = ((double)(qrow ? gr0 + (qcr - lr0) : qcc) + 0.5) / (qrow ? Hd : Wd);
+        const double uA = __shfl(quot, lane & 7, 64), uB = __shfl(quot, 8 + (lane & 7), 64);
+        const double vA = 1.0 - __shfl(quot, 16 + (lane >> 3), 64), vB = 1.0 - __shfl(quot, 24 + (lane >> 3), 64);
         const double dyA = (1.0 - 2.0 * uA) * aspect, dyB = (1.0 - 2.0 * uB) * aspect;
         const double dzA = 2.0 * vA - 1.0, dzB = 2.0 * vB - 1.0;
         const double m0 = c->cam_m[0], m1 = c->cam_m[1], m2 = c->cam_m[2], m3 = c->cam_m[3];
@@ -1243,8 +1259,9 @@ __global__ __launch_bounds__(PT_BLOCK) __attribute__((amdgpu_waves_per_eu(PT_TIL
   }
   // The one barrier of the kernel: every wave arrives here exactly once, whatever it did above.  __syncthreads() first lets
   // each wave wait for the staging loads it issued itself, so behind it the whole image is in LDS for every wave.
+  if (valid) PT_T4(5);  // (a wave without a tile reports no cycles)
   if constexpr (SLDS) __syncthreads();
-  if (valid) PT_T4(5);  // (the wait at the barrier counts as query time; a wave without a tile reports no cycles, as before)
+  if (valid) PT_T4(8);
   if (shade) {
     // ---- shade + store ----
     if constexpr (RENDERER == PT_RENDERER_ONOFF) {  // render.py:52-53
@@ -1425,19 +1442,19 @@ __global__ __launch_bounds__(PT_BLOCK) __attribute__((amdgpu_waves_per_eu(PT_TIL
 #ifdef PT_DEBUG_HEAVY  // section sums of the HEAVY sampled waves only (more than PT_DEBUG_HEAVY cycles)
   {
     unsigned long long tot_ = 0;
-    for (int q = 0; q < 8; ++q) tot_ += tsum[q];
+    for (int q = 0; q < 9; ++q) tot_ += tsum[q];
     if ((threadIdx.x & 63) == 0 && ((blockIdx.y * gridDim.x + blockIdx.x) & 3) == 0 && tot_ > PT_DEBUG_HEAVY)
-      for (int q = 0; q < 8; ++q) atomicAdd(pt_queue(a) + 1 + q, tsum[q]);
+      for (int q = 0; q < 9; ++q) atomicAdd(pt_queue(a) + 1 + q, tsum[q]);
   }
 #else
   if ((threadIdx.x & 63) == 0 && ((blockIdx.y * gridDim.x + blockIdx.x) & 15) == 0)
-    for (int q = 0; q < 8; ++q) atomicAdd(pt_queue(a) + 1 + q, tsum[q]);
+    for (int q = 0; q < 9; ++q) atomicAdd(pt_queue(a) + 1 + q, tsum[q]);
 #endif
   if ((threadIdx.x & 63) == 0) {  // every wave's cycles, by workgroup and wave (tools/dbgtile4_waves.py: how uneven are a workgroup's four tiles?)
     const int wv = (blockIdx.y * gridDim.x + blockIdx.x) * 4 + (int)(threadIdx.x >> 6);
     if (wv < PT_UNITLOG_LEN) {
       unsigned long long tot_ = 0;
-      for (int q = 0; q < 8; ++q) tot_ += tsum[q];
+      for (int q = 0; q < 9; ++q) tot_ += tsum[q];
       pt_unitlog[wv * 8] = tot_;
       pt_unitlog[wv * 8 + 1] = tsum[0] + tsum[1] + tsum[2] + tsum[3];  // prologue, cone, cull, dome check: per tile
       pt_unitlog[wv * 8 + 2] = __builtin_amdgcn_s_memtime();
@@ -1445,7 +1462,7 @@ __global__ __launch_bounds__(PT_BLOCK) __attribute__((amdgpu_waves_per_eu(PT_TIL
   }
   if ((threadIdx.x & 63) == 0 && ((blockIdx.y * gridDim.x + blockIdx.x) & 15) == 0) {  // (sampled waves) the longest one, and how many took more than 16 / 24 / 32 kcycles
     unsigned long long tot = 0;
-    for (int q = 0; q < 8; ++q) tot += tsum[q];
+    for (int q = 0; q < 9; ++q) tot += tsum[q];
     atomicMax(pt_queue(a) + 12, tot);
     if (tot > 16384ULL) atomicAdd(pt_queue(a) + 13, 1ULL);
     if (tot > 24576ULL) atomicAdd(pt_queue(a) + 14, 1ULL);
