@@ -33,6 +33,30 @@ struct alignas(256) PtShapeAux {
 };
 static_assert(sizeof(PtShapeAux) == 256, "PtShapeAux must be 256 B");
 
+// The Flat palette: what FlatRenderer returns for a shape whose two pigments are uniform, and whether they are.  32 B per
+// shape instead of the 28 B the same answer takes out of 256-byte-strided aux[]: step (a) of pt_tile4_kernel<FLAT, *>'s
+// shading reads one record per pixel.  The table stands directly behind aux[] in the same allocation, padded with zeros to
+// whole 1 KiB chunks (pt_flat_pal_chunks), so that a wave can copy it with unmasked 16-byte-per-lane loads: the kernels find
+// it as (const PtFlatPal *)(a.aux + a.n_shapes) and the argument block has no field for it.
+struct alignas(16) PtFlatPal {
+  double c[3];       // needs_uv == 0: aux.pig_c2 (= pig_c1 + emi_c1, pt_scene_build.h); else 0
+  int32_t needs_uv;  // aux.needs_uv
+  int32_t _pad;
+};
+static_assert(sizeof(PtFlatPal) == 32, "PtFlatPal must be 32 B");
+#define PT_FLAT_PAL_CHUNK 1024  // bytes a wave copies with one 16-byte-per-lane load
+// chunks the palette of n shapes is padded to
+__host__ __device__ static inline int pt_flat_pal_chunks(int n) {
+  return (n * (int)sizeof(PtFlatPal) + PT_FLAT_PAL_CHUNK - 1) / PT_FLAT_PAL_CHUNK;
+}
+// pt_tile4_kernel<FLAT, LDS>: bytes from one wave's copy of the palette to the next wave's inside the workgroup's dynamic LDS
+// block of n * 384 bytes (pt_plan.h: lds_main).  Four slices of whole chunks fit from 11 shapes on; below, the four waves share
+// ONE slice (stride 0): each writes the same bytes to the same place and waits for its own loads only.
+__host__ __device__ static inline int pt_flat_pal_slice(int n) {
+  const int bytes = pt_flat_pal_chunks(n) * PT_FLAT_PAL_CHUNK;
+  return 4 * bytes <= n * (int)(sizeof(PtShapeRec) + sizeof(PtShapeAux)) ? bytes : 0;
+}
+
 struct alignas(64) PtLight {
   double pos[3];
   double color[3];

@@ -306,8 +306,9 @@ static inline void pt_make_plan(const PtSceneFacts &s, const pt_camera *cam, con
     pl.grid4_y = (unsigned)(((rows + 15) / 16 + 1) / 2);
     grid = (int)(pl.grid4_x * pl.grid4_y);
     const size_t scene_bytes = (size_t)s.n_shapes * (PT_PLAN_REC_BYTES + PT_PLAN_AUX_BYTES);
-    // (24 KB: this limit is also what bounds the kernel's unrolled staging copy, PT_TILE4_STAGE_ROUNDS in pt_tile.h --
-    //  6 rounds of 4 waves x 1 KiB; raise the two together)
+    // (24 KB = 64 shapes: the staged variant's waves copy the Flat palette of at most that many, PT_TILE4_PAL_CHUNKS in
+    //  pt_tile.h -- raise the two together.  The kernel uses at most 4 slices x 2 KiB of the block; it is still reserved at the
+    //  size of the scene image it used to hold, which tests pin and which costs no occupancy: DESIGN.md item 15)
     pl.t4lds = t.tile4_lds != 0 && p->renderer == PT_RENDERER_FLAT && scene_bytes <= 24 * 1024;
     pl.lds_main = pl.t4lds ? scene_bytes : 0;
   }

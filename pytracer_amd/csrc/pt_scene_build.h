@@ -39,6 +39,7 @@ struct PtSceneHost {
   PtSceneScalars sc;
   std::vector<PtShapeRec> recs;
   std::vector<PtShapeAux> aux;
+  std::vector<PtFlatPal> flat_pal;  // [n_shapes]; the upload pads it to whole chunks behind aux[] (pt_layout.h)
   std::vector<PtDiagRec> diag;
   std::vector<float4> bounds;
   std::vector<float> bsoa;
@@ -307,6 +308,32 @@ static inline void pt_pack_records(const pt_scene_desc *d, const std::vector<int
   h.lights = lights;
   h.tex = tex;
   h.tex_data = tex_data;
+}
+
+// the Flat palette (pt_layout.h: PtFlatPal), from the packed aux[]: pt_pack_records has already put pigment + emitted into
+// pig_c2 of every shape with two uniform pigments
+static inline void pt_flat_palette(PtSceneHost &h) {
+  std::vector<PtFlatPal> pal(h.aux.size());
+  for (size_t slot = 0; slot < pal.size(); ++slot) {
+    PtFlatPal &e = pal[slot];
+    memset(&e, 0, sizeof e);
+    e.needs_uv = h.aux[slot].needs_uv;
+    if (!e.needs_uv)
+      for (int k = 0; k < 3; ++k) e.c[k] = h.aux[slot].pig_c2[k];
+  }
+  h.flat_pal = pal;
+}
+
+// what the upload puts into ONE allocation: aux[], and directly behind it the palette in whole zero-filled chunks
+// (pt_flat_pal_chunks: a wave of pt_tile4_kernel<FLAT, LDS> reads every chunk to its end)
+static inline std::vector<unsigned char> pt_aux_image(const PtSceneHost &h) {
+  const size_t n = h.aux.size(), aux_bytes = n * sizeof(PtShapeAux);
+  std::vector<unsigned char> img(aux_bytes + (size_t)pt_flat_pal_chunks((int)n) * PT_FLAT_PAL_CHUNK, 0);
+  if (n) {
+    memcpy(img.data(), h.aux.data(), aux_bytes);
+    memcpy(img.data() + aux_bytes, h.flat_pal.data(), n * sizeof(PtFlatPal));
+  }
+  return img;
 }
 
 static inline void pt_cull_bounds(PtSceneHost &h) {
@@ -610,6 +637,7 @@ static inline void pt_build_scene(const pt_scene_desc *d, const PtTuning &tn, Pt
   h.sc.n_lights = d->n_lights;
   h.sc.n_textures = d->n_textures;
   pt_pack_records(d, pt_slot_order(d, h.sc), h);
+  pt_flat_palette(h);
   pt_cull_bounds(h);
   pt_ball_tables(h);
   pt_build_grid(tn, h);

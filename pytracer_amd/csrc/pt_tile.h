@@ -968,17 +968,21 @@ PT_DEV void sphere_roots1(const PtKArgs &a, int slot, bool active, bool inside, 
   PT_SPHERE_ROOTS_IN(slot, inside);
 }
 
-// SLDS (small worlds, Flat): the shapes' records (128 B + 256 B each) are staged in LDS by the workgroup and shading
-//   gathers from there instead of through the vector memory path (C2: 14.4 -> 13.9 us per frame).  The copy is asynchronous
-//   (global -> LDS loads issued at the top, no register staging) and is waited for by the one barrier in front of the shading.
+// SLDS (small worlds, Flat): every wave copies the scene's Flat palette (pt_layout.h: PtFlatPal, 32 B per shape, behind aux[])
+//   into its own slice of the dynamic LDS block, and step (a) of the shading gathers the pixels' colours from there instead of
+//   through the vector memory path.  The copy is asynchronous (one or two global -> LDS loads issued at the top, no register
+//   staging); a wave waits for its own loads only, so the kernel has no workgroup barrier but add_ray_count's.  Everything else
+//   of the records (the loop's scalar loads, the per-pixel remainder) reads global memory in both variants.
+//   (Until the palette existed the workgroup staged recs[] and aux[] whole, 384 B per shape, behind a barrier.)
 // (A variant with 16x8 tiles and two pixels per lane -- twice the waves, half the pixels each, for frames whose 16x16 tiles do
 //  not fill the chip -- was measured slower on every frame and deleted in round 6: profiles/DROPPED_VARIANTS.md.)
 #ifndef PT_TILE4_WAVES
-#define PT_TILE4_WAVES 4  // waves per SIMD the register allocation aims at (5 / 6 measured: profiles/DROPPED_VARIANTS.md)
+#define PT_TILE4_WAVES 5  // waves per SIMD the register allocation aims at: 96 VGPRs, no scratch.  (At 4 the Flat variants take 99 since the
+                          //  staged one's remainder reads global memory, a wave per SIMD for nothing; 6 / 8: profiles/DROPPED_VARIANTS.md)
 #endif
-// SLDS: rounds of the staging copy, one 1 KiB chunk per wave and round.  6 rounds x 4 waves x 1 KiB = the 24 KB up to which the
-// plan stages (pt_plan.h: t4lds); the host refuses to launch the staged variant on a larger image.
-#define PT_TILE4_STAGE_ROUNDS 6
+// SLDS: chunks of the palette a wave copies at most: 2 x 1 KiB = 64 shapes, the most the plan admits to the staged variant
+// (pt_plan.h: t4lds); the host refuses to launch it for a larger palette.
+#define PT_TILE4_PAL_CHUNKS 2
 #define PT_PIN_SGPR(x) asm volatile("" : "+s"(x))  // the value exists HERE, in a scalar register
 template <int RENDERER, bool SLDS = false>
 __global__ __launch_bounds__(PT_BLOCK) __attribute__((amdgpu_waves_per_eu(PT_TILE4_WAVES, 8))) void pt_tile4_kernel(const PtKArgs a) {
@@ -997,9 +1001,8 @@ __global__ __launch_bounds__(PT_BLOCK) __attribute__((amdgpu_waves_per_eu(PT_TIL
 #endif
   const int lane = threadIdx.x & 63, wib = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
   // ---- what cone, cull and shortcut read from memory is asked for behind the kernel arguments: the cold block's fields for
-  //      them, the lane's bounding sphere, the staging copy.  As compiled, the scalar loads stand in two groups in between the
-  //      staging copy's exec-masked blocks, one wait each; the camera of the fp64 rays is read at the rays, three more round
-  //      trips.  Reading it here as well, or making the rays in front of the cone, was measured level or slower
+  //      them, the wave's copy of the palette, the lane's bounding sphere.  The camera of the fp64 rays is read at the rays,
+  //      three more round trips.  Reading it here as well, or making the rays in front of the cone, was measured level or slower
   //      (profiles/DROPPED_VARIANTS.md): a wave waits for its SIMD's VALU far more than for these trips. ----
   int W, rows_local, npass, n_ranks, row_block, rank, dome_sw, f32_sw, cam_kind;
   ConeCam cam;
@@ -1019,24 +1022,25 @@ __global__ __launch_bounds__(PT_BLOCK) __attribute__((amdgpu_waves_per_eu(PT_TIL
     cam.dy[i] = c0->cone_dy[i];
     cam.apex[i] = c0->cone_apex[i];
   }
-  const float4 b_first = a.bounds[lane < a.n_shapes ? lane : 0];
+  int pal_at = 0;  // SLDS: where this wave's copy of the palette starts in the dynamic LDS block (bytes)
   if constexpr (SLDS) {
-    // recs[] then aux[] into LDS, straight from global memory (no register in between), 16 bytes per lane: chunk c is the
-    // bytes [1024 c, 1024 c + 1024) of the image, wave w takes the chunks w, w + 4, ...  128 n is a multiple of 16, so no lane
-    // straddles the two tables; lanes past the image are switched off.  The barrier in front of the shading is what
-    // needs them; as compiled, the cull's wait for the lane's bounding sphere (s_waitcnt vmcnt(0): loads in exec-masked blocks
-    // cannot be counted) retires them first, ~5 kcycles after they were issued.  The copy stays HERE: its ~120 instructions run
-    // while the wave waits for its scalar loads anyway; issued behind the cull it cost 0.65 us per frame (DROPPED_VARIANTS.md).
-    const int nrec = a.n_shapes * (int)sizeof(PtShapeRec), nimg = nrec + a.n_shapes * (int)sizeof(PtShapeAux);
-    const char *src_rec = (const char *)a.recs, *src_aux = (const char *)a.aux - nrec;
+    // The palette into this wave's slice, straight from global memory (no register in between), 16 bytes per lane and 1 KiB
+    // per load.  Every lane loads: the table is mapped and zero-filled to the end of its last chunk (pt_scene_upload), the
+    // chunk count is a scalar, and a wave-uniform branch skips the second chunk of a world of at most 32 shapes.  EVERY wave
+    // issues them, also one without a tile, and every wave passes the s_waitcnt vmcnt(0) in front of the shading phase before
+    // it can end: a load still in flight behind s_endpgm would write into LDS that may be the next workgroup's by then.
+    // As compiled the cull's wait for the lane's bounding sphere, asked for right behind, retires them first.
+    const int nchunk = pt_flat_pal_chunks(a.n_shapes);
+    pal_at = wib * pt_flat_pal_slice(a.n_shapes);
+    const char *src = (const char *)(a.aux + a.n_shapes) + lane * 16;
 #pragma unroll
-    for (int r = 0; r < PT_TILE4_STAGE_ROUNDS; ++r) {
-      const int cbase = (r * (PT_BLOCK / 64) + wib) * 1024, b = cbase + lane * 16;
-      if (b < nimg)
-        __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void *)((b < nrec ? src_rec : src_aux) + b),
-                                         (__attribute__((address_space(3))) void *)((char *)pt_lds_masks + cbase), 16, 0, 0);
-    }
+    for (int ch = 0; ch < PT_TILE4_PAL_CHUNKS; ++ch)
+      if (ch < nchunk)
+        __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void *)(src + ch * PT_FLAT_PAL_CHUNK),
+                                         (__attribute__((address_space(3))) void *)((char *)pt_lds_masks + pal_at + ch * PT_FLAT_PAL_CHUNK),
+                                         16, 0, 0);
   }
+  const float4 b_first = a.bounds[lane < a.n_shapes ? lane : 0];
   // (pinned: the scalar loads above must not sink into the branches that use their results, where each would be a
   //  dependent round trip of its own)
   PT_PIN_SGPR(f32_sw);
@@ -1059,8 +1063,8 @@ __global__ __launch_bounds__(PT_BLOCK) __attribute__((amdgpu_waves_per_eu(PT_TIL
   const int tx = blockIdx.x * 2 + (wib & 1), ty = blockIdx.y * 2 + (wib >> 1);
   unsigned long long nrays = 0, nres = 0;
   const bool valid = tx * 16 < W && ty * TH < rows_local;  // (wave-uniform; the ray count below needs every wave)
-  // Every wave of the workgroup runs the same three phases: the front phase (cone, cull, then the shortcut or the query),
-  // ONE barrier, the shading phase.  `valid` and `shade` are wave-uniform and only ever skip a phase's WORK.
+  // Every wave runs the same three phases: the front phase (cone, cull, then the shortcut or the query), the wait for its own
+  // palette loads, the shading phase.  `valid` and `shade` are wave-uniform and only ever skip a phase's WORK, never the wait.
   bool shade = false;
   bool act[4];
   long long pix[4];
@@ -1257,11 +1261,15 @@ __global__ __launch_bounds__(PT_BLOCK) __attribute__((amdgpu_waves_per_eu(PT_TIL
       shade = true;
     }
   }
-  // The one barrier of the kernel: every wave arrives here exactly once, whatever it did above.  __syncthreads() first lets
-  // each wave wait for the staging loads it issued itself, so behind it the whole image is in LDS for every wave.
+  // Every wave arrives here exactly once, whatever it did above, and waits for the palette loads it issued itself (and for
+  // nobody else's: no barrier).  Written out, not left to the compiler's tracking of LDS written by vector memory loads: the
+  // wait also has to stand on the paths that read nothing from LDS and go straight to the end of the program.
   if (valid) PT_T4(5);  // (a wave without a tile reports no cycles)
+  if constexpr (SLDS) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+#ifdef PT_TILE4_BARRIER  // (a measurement switch: the palette with the old workgroup barrier kept, profiles/r11_tile4_palette_ab.txt)
   if constexpr (SLDS) __syncthreads();
-  if (valid) PT_T4(8);
+#endif
+  if (valid) PT_T4(8);  // (section 8 was the wait at the workgroup barrier; it is the wait for the wave's own loads now)
   if (shade) {
     // ---- shade + store ----
     if constexpr (RENDERER == PT_RENDERER_ONOFF) {  // render.py:52-53
@@ -1298,36 +1306,36 @@ __global__ __launch_bounds__(PT_BLOCK) __attribute__((amdgpu_waves_per_eu(PT_TIL
           nrays += 1ULL;
         }
       }
-      // (a) per lane, the four pixels side by side: two gathers (needs_uv, then pig_c2) and their two waits serve all four
-      //     pixels and every uniform winner at once.  (Taken through the loop, one round trip per winner, a tile among C2's
-      //     spheres with ten winners lost 4 kcycles against the per-pixel code: profiles/r09_tile4_winners_ab.txt.)
-      //     A pixel without a winner reads record 0 and stores nothing.
+      // (a) per lane, the four pixels side by side: one gather of the winner's palette record (32 B: the colour and needs_uv,
+      //     two 16-byte reads) per pixel, all eight reads in front of ONE wait, serves all four pixels and every uniform winner
+      //     at once -- from the wave's slice of LDS, or from the table behind aux[] in global memory.  (Taken through the loop,
+      //     one round trip per winner, a tile among C2's spheres with ten winners lost 4 kcycles against the per-pixel code:
+      //     profiles/r09_tile4_winners_ab.txt.)  A pixel without a winner reads record 0 and stores nothing.
       {
-        double cu[NPX][3];
-        int uv[NPX];
+        typedef double __attribute__((ext_vector_type(2))) pt_d2;
+        pt_d2 lo[NPX], hi[NPX];  // (c[0], c[1]) and (c[2], needs_uv | pad) of PtFlatPal
 #pragma unroll
         for (int k = 0; k < NPX; ++k) {
           const int hit = pend[k] >= 0 ? pend[k] : 0;
-          if constexpr (SLDS)
-            uv[k] = ((pt_lds_aux)(const void *)(pt_lds_f64 + a.n_shapes * 16) + hit)->needs_uv;
-          else
-            uv[k] = a.aux[hit].needs_uv;
-        }
-#pragma unroll
-        for (int k = 0; k < NPX; ++k) {
-          const int hit = pend[k] >= 0 ? pend[k] : 0;
-#pragma unroll
-          for (int q = 0; q < 3; ++q) {
-            if constexpr (SLDS)
-              cu[k][q] = ((pt_lds_aux)(const void *)(pt_lds_f64 + a.n_shapes * 16) + hit)->pig_c2[q];
-            else
-              cu[k][q] = a.aux[hit].pig_c2[q];
+          if constexpr (SLDS) {
+            typedef const __attribute__((address_space(3))) pt_d2 *pt_lds_d2;
+            const pt_lds_d2 e = (pt_lds_d2)(const void *)((const __attribute__((address_space(3))) char *)(const void *)pt_lds_masks +
+                                                           pal_at + hit * (int)sizeof(PtFlatPal));
+            lo[k] = e[0];
+            hi[k] = e[1];
+          } else {
+            const pt_d2 *e = (const pt_d2 *)((const PtFlatPal *)(a.aux + a.n_shapes) + hit);
+            lo[k] = e[0];
+            hi[k] = e[1];
           }
         }
+        // (pinned: or the reads of a pixel sink into the branch that stores it, two dependent waits of their own)
+#pragma unroll
+        for (int k = 0; k < NPX; ++k) asm volatile("" : "+v"(lo[k]), "+v"(hi[k]));
 #pragma unroll
         for (int k = 0; k < NPX; ++k)
-          if (pend[k] >= 0 && uv[k] == 0) {
-            const V3 c = {cu[k][0], cu[k][1], cu[k][2]};
+          if (pend[k] >= 0 && (int)(unsigned)__double_as_longlong(hi[k].y) == 0) {  // (needs_uv: the low word)
+            const V3 c = {lo[k].x, lo[k].y, hi[k].x};
             store_pixel(a, pix[k], c, out_f32);
             pend[k] = -1;
           }
@@ -1417,19 +1425,10 @@ __global__ __launch_bounds__(PT_BLOCK) __attribute__((amdgpu_waves_per_eu(PT_TIL
             rk.o = org;
             rk.d = dir[k];
             rk.tmin = tmin;
-            V3 p1, p2;
-            if constexpr (SLDS) {
-              const pt_lds_rec rec = (pt_lds_rec)(const void *)pt_lds_f64 + hit;
-              const pt_lds_aux ax = (pt_lds_aux)(const void *)(pt_lds_f64 + a.n_shapes * 16) + hit;
-              hit_details(rec, ax, rk, h4.best_t[k], h, true);
-              p1 = brdf_pigment(a, ax, h.u, h.v);
-              p2 = emitted_pigment(a, ax, h.u, h.v);
-            } else {
-              const PtShapeAux *ax = cold_args(a)->aux + hit;
-              hit_details(a.recs + hit, ax, rk, h4.best_t[k], h, true);
-              p1 = brdf_pigment(a, ax, h.u, h.v);
-              p2 = emitted_pigment(a, ax, h.u, h.v);
-            }
+            // (global memory in both variants: cold on every measured frame, and LDS holds the palette alone)
+            const PtShapeAux *ax = cold_args(a)->aux + hit;
+            hit_details(a.recs + hit, ax, rk, h4.best_t[k], h, true);
+            const V3 p1 = brdf_pigment(a, ax, h.u, h.v), p2 = emitted_pigment(a, ax, h.u, h.v);
             const V3 c = {p1.x + p2.x, p1.y + p2.y, p1.z + p2.z};
             store_pixel(a, pix[k], c, out_f32);
           }

@@ -199,6 +199,15 @@ static int upload(T **dst, const std::vector<T> &src) {
   return PT_OK;
 }
 
+// aux[] and, directly behind it in the same allocation, the Flat palette in whole zero-filled chunks (pt_layout.h: PtFlatPal):
+// pt_tile4_kernel<FLAT, *> finds it as a.aux + a.n_shapes and may read every mapped chunk to its end
+static int upload_aux_and_palette(PtShapeAux **dst, const PtSceneHost &h) {
+  const std::vector<unsigned char> img = pt_aux_image(h);
+  HIP_TRY(hipMalloc((void **)dst, std::max(img.size(), sizeof(PtShapeAux))));  // (an empty world: a pointer nobody reads through)
+  if (!img.empty()) HIP_TRY(hipMemcpy(*dst, img.data(), img.size(), hipMemcpyHostToDevice));
+  return PT_OK;
+}
+
 // what every handle has of its own besides the per-camera constants: counters, queue blocks, the argument block, a stream
 // and events.  On failure the handle is freed.
 static int handle_state(pt_scene *s) {
@@ -271,7 +280,7 @@ extern "C" int pt_scene_upload(const pt_scene_desc *d, int device, pt_scene **ou
     std::vector<PtHoistDiag> hd(std::max(sh->sc.n_diag, 1));
     UP(upload(&s->hoist_diag, hd));
   }
-  UP(upload(&sh->aux, h.aux));
+  UP(upload_aux_and_palette(&sh->aux, h));
   UP(upload(&sh->lights, h.lights));
   UP(upload(&sh->tex, h.tex));
   UP(upload(&sh->tex_data, h.tex_data));
@@ -590,7 +599,7 @@ static int enqueue_hits(pt_scene *s, const PtPlan &pl, bool cull, PtKArgs &a, in
   return PT_OK;
 }
 
-// small worlds, 16x16 tiles: the shapes' records ride in LDS for shading (Flat; OnOff reads none of them)
+// small worlds, 16x16 tiles: the shapes' Flat colours ride in LDS for shading (Flat; OnOff reads none of them)
 static int enqueue_tile4(pt_scene *s, const PtPlan &pl, int R, PtKArgs &a, FrameLaunches &go) {
   s->stats.lds_bytes = (int)pl.lds_main;
   // pt_tile4_kernel<renderer, LDS> by (renderer, pl.t4lds)
@@ -599,8 +608,9 @@ static int enqueue_tile4(pt_scene *s, const PtPlan &pl, int R, PtKArgs &a, Frame
                                     {PT_RENDERER_FLAT, 0, pt_tile4_kernel<PT_RENDERER_FLAT, false>}};
   const bool staged = R != PT_RENDERER_ONOFF && pl.t4lds;
   if (staged) {
-    // the staged variant copies recs[] and aux[] with 16-byte global -> LDS loads, in PT_TILE4_STAGE_ROUNDS unrolled rounds:
-    // both tables and the dynamic LDS block (it follows the kernel's static LDS) must be 16-byte aligned, the image must fit
+    // the staged variant: every wave copies the Flat palette behind aux[] into a slice of its own with 16-byte global -> LDS
+    // loads.  The tables and the dynamic LDS block (it follows the kernel's static LDS) must be 16-byte aligned, and the four
+    // slices must lie inside the block, which the plan still sizes for the whole scene image
     static int static_lds = -1;  // (a property of the code: looked up once)
     if (static_lds < 0) {
       hipFuncAttributes fa;
@@ -609,8 +619,10 @@ static int enqueue_tile4(pt_scene *s, const PtPlan &pl, int R, PtKArgs &a, Frame
     }
     if ((((uintptr_t)a.recs | (uintptr_t)a.aux) & 15) != 0 || (static_lds & 15) != 0)
       return fail(PT_ERR_INVALID, "internal: pt_tile4_kernel<FLAT, LDS> needs 16-byte aligned shape tables and LDS");
-    if (pl.lds_main > (size_t)PT_TILE4_STAGE_ROUNDS * (PT_BLOCK / 64) * 1024)
-      return fail(PT_ERR_INVALID, "internal: scene image exceeds pt_tile4_kernel's staging copy");
+    const size_t pal_bytes = (size_t)pt_flat_pal_chunks(a.n_shapes) * PT_FLAT_PAL_CHUNK;
+    if (pt_flat_pal_chunks(a.n_shapes) > PT_TILE4_PAL_CHUNKS ||
+        (size_t)(PT_BLOCK / 64 - 1) * pt_flat_pal_slice(a.n_shapes) + pal_bytes > pl.lds_main)
+      return fail(PT_ERR_INVALID, "internal: the four palette slices of pt_tile4_kernel<FLAT, LDS> do not fit its LDS block");
   }
   void *args[] = {&a};
   go(pick(tile4, R, staged), dim3(pl.grid4_x, pl.grid4_y, 1), pl.lds_main, true, args);

@@ -33,7 +33,8 @@ print("kernel ms", ds.stats().kernel_ms, "sampled waves", nw, "tiles/wave", 1440
 for n, v in zip(names, t):
     print(f"{n:26s} {v / nw:10.0f} cycles/wave  {100 * v / t.sum():5.1f} %")
 print("sum per wave", t.sum() / nw)
-if ds.stats().kernel == abi.KERNEL_TILE4:  # (its own figure since section 5 ends in front of the barrier; not part of the sum above)
-    print(f"{'wait at the barrier':26s} {q[9] / nw:10.0f} cycles/wave")
+if ds.stats().kernel == abi.KERNEL_TILE4:  # (its own figure since section 5 ends in front of it; not part of the sum above)
+    # the wave's wait for its own palette loads; in builds from before the palette, the wait at the workgroup barrier
+    print(f"{'wait in front of shading':26s} {q[9] / nw:10.0f} cycles/wave")
 if ds.stats().kernel == abi.KERNEL_TILE4:
     print(f"longest wave {q[12]} cycles; waves above 16 / 24 / 32 kcycles: {q[13]} / {q[14]} / {q[15]} of the {nw} sampled")

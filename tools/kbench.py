@@ -60,6 +60,10 @@ CONFIGS = {
     "c5": (10000, False, True, 1280, 720, dict(renderer=abi.RENDERER_FLAT)),
     "c5pt": (10000, False, True, 1280, 720, dict(renderer=abi.RENDERER_PATHTRACER, samples_per_side=2, num_of_rays=1,
                                                  max_depth=3, rr_limit=3, path_state=45, path_seq=54)),
+    # Flat frames beside C2 for pt_tile4_kernel<FLAT, *>: 100 spheres (the noLDS variant), the demo world (patterned spheres:
+    # the per-pixel remainder of the shading)
+    "c100": (100, True, False, 1280, 720, dict(renderer=abi.RENDERER_FLAT)),
+    "demoflat": ("demo", False, False, 1280, 960, dict(renderer=abi.RENDERER_FLAT)),
     "c2ortho": (32, True, False, 1280, 720, dict(renderer=abi.RENDERER_FLAT, ortho=True)),
     "c3ortho": (32, False, False, 1280, 720, dict(renderer=abi.RENDERER_PATHTRACER, samples_per_side=4, num_of_rays=1,
                                                   max_depth=3, rr_limit=3, path_state=45, path_seq=54, ortho=True)),
