@@ -15,6 +15,7 @@ after libptrace.so, in the order of ``ADDONS`` (csrc/ptrace_NAME.hip, include/pt
 * radiance: the whole ``PathTracer`` recursion for ray batches
 * gather: the mean radiance over the hemisphere of batches of surface points
 * bake: surface points from (shape, u, v), and light maps over a shape's (u, v) grid
+* sh: order-2 spherical-harmonic radiance probes at free points, and their evaluation
 """
 from __future__ import annotations
 
@@ -46,9 +47,15 @@ LATER_ADDONS = {name: ([f"ptrace_{name}.hip"], os.path.join(HERE, f"libptrace_{n
 LATER_TARGETS = tuple((FLAGS[:-1] + [f"-cuid={cuid}"], lib, sources) for sources, lib, cuid in LATER_ADDONS.values())
 ((BAKE_FLAGS, BAKE_LIB, BAKE_SOURCES),) = LATER_TARGETS
 ALL_TARGETS = TARGETS + LATER_TARGETS
+# The add-ons since interface 1.6.  ALL_TARGETS keeps the value it had at interface 1.5 (tests/test_bake_host.py pins it: seven
+# rows, the bake's last), so what came later is listed here and EVERY_TARGET is what build() and needs_build() walk.
+NEWER_ADDONS = {name: ([f"ptrace_{name}.hip"], os.path.join(HERE, f"libptrace_{name}.so"), f"libptrace_{name}") for name in ("sh",)}
+NEWER_TARGETS = tuple((FLAGS[:-1] + [f"-cuid={cuid}"], lib, sources) for sources, lib, cuid in NEWER_ADDONS.values())
+((SH_FLAGS, SH_LIB, SH_SOURCES),) = NEWER_TARGETS
+EVERY_TARGET = ALL_TARGETS + NEWER_TARGETS
 # every file the translation units include: all of csrc/ (tests/test_host.py checks this list against the #include lines)
 DEPS = sorted(f for f in os.listdir(CSRC) if f.endswith((".hip", ".h"))) + [
-    os.path.join("..", "..", "include", h) for h in ["ptrace.h", "ptrace_debug.h"] + [f"ptrace_{name}.h" for name in list(ADDONS) + list(LATER_ADDONS)]]
+    os.path.join("..", "..", "include", h) for h in ["ptrace.h", "ptrace_debug.h"] + [f"ptrace_{name}.h" for name in list(ADDONS) + list(LATER_ADDONS) + list(NEWER_ADDONS)]]
 
 
 def code_hash(lib: str = LIB) -> str:
@@ -87,17 +94,17 @@ def _hipcc() -> str:
 
 
 def needs_build() -> bool:
-    libs = [lib for _, lib, _ in ALL_TARGETS]
+    libs = [lib for _, lib, _ in EVERY_TARGET]
     if not all(os.path.exists(lib) for lib in libs):
         return True
-    t = min(os.path.getmtime(lib) for lib in libs)  # (one list of files for all seven: they share the headers)
+    t = min(os.path.getmtime(lib) for lib in libs)  # (one list of files for all eight: they share the headers)
     return any(os.path.getmtime(os.path.join(CSRC, d)) > t for d in DEPS)
 
 
 def build(force: bool = False, verbose: bool = False) -> str:
     if not force and not needs_build():
         return LIB
-    for flags, lib, sources in ALL_TARGETS:
+    for flags, lib, sources in EVERY_TARGET:
         cmd = [_hipcc()] + flags + ["-o", lib] + [os.path.join(CSRC, s) for s in sources]
         if verbose:
             print(" ".join(cmd), file=sys.stderr)

@@ -508,9 +508,95 @@ def bake(shape, size, samples, side, no_jitter, output, num_of_rays, max_depth, 
                f"{wall:.3f} s: wrote {output}")
 
 
+def parse_grid(text: str):
+    """``ox,oy,oz,step,nx,ny,nz`` -> (origin, step, dims) of a :class:`pytracer_amd.rays.ProbeGrid`."""
+    parts = text.split(",")
+    try:
+        if len(parts) != 7:
+            raise ValueError
+        origin, step = tuple(float(x) for x in parts[:3]), float(parts[3])
+        dims = tuple(int(x) for x in parts[4:])
+    except ValueError:
+        raise UsageError(f"--grid expects ox,oy,oz,step,nx,ny,nz (four numbers, three counts), got {text!r}") from None
+    if not step > 0.0 or min(dims) < 1:
+        raise UsageError(f"--grid {text}: the step must be positive and nx, ny, nz at least 1")
+    return origin, step, dims
+
+
+@click.command("probes")
+@click.option("--grid", type=str, default=None, help="Probes on a lattice: ox,oy,oz,step,nx,ny,nz (probe (ix, iy, iz) has index (iz * ny + iy) * nx + ix)")
+@click.option("--input", "input_name", type=str, default=None,
+              help="Probes at the [n, 3] points of a .npy file, or of an .npz holding them as `points` (or as its only array)")
+@click.option("--output", type=str, default="probes.npz", help="Name of the .npz file to create")
+@click.option("--samples", type=int, default=256, help="Samples (rays uniform on the sphere) per probe")
+@click.option("--num-of-rays", type=int, default=1, help="Number of rays departing from each surface point below the probes' rays")
+@click.option("--max-depth", type=int, default=3, help="Maximum allowed ray depth")
+@click.option("--russian-roulette-limit", type=int, default=3, help="Depth from which on the Russian roulette runs")
+@click.option("--init-state", type=int, default=45, help="Initial seed of the generators (positive number)")
+@click.option("--init-seq", type=int, default=54,
+              help="Identifier of probe 0's first sequence: sample k of probe i draws from PCG(init_state, init_seq + i * samples + k)")
+@click.option("--depth", type=int, default=1, help="Ray.depth of the probes' rays (1: the children of a camera ray's hit)")
+@click.option("--declare-float", "-d", type=str, multiple=True, help="Declare a variable: --declare-float=VAR:VALUE")
+@click.option("--device", type=int, default=0, help="GPU to trace on")
+@click.argument("input_scene_name", type=str, default="builtin:demo")
+def probes(grid, input_name, output, samples, num_of_rays, max_depth, russian_roulette_limit, init_state, init_seq, depth, declare_float,
+           device, input_scene_name):
+    """Radiance probes at free points of the scene: per point the 27 order-2 spherical-harmonic coefficients of the radiance
+    arriving there (`samples` rays uniform on the sphere, each followed by PathTracer(world, BLACK, its own generator, ...),
+    projected on the device in sample order).  Writes an .npz of coefficients [n, 9, 3], n_rays [n] and points [n, 3]."""
+    import numpy as np
+
+    from . import rays as rb
+
+    try:
+        if (grid is None) == (input_name is None):
+            raise UsageError("the probes' points come from --grid or from --input: give one of them")
+        if samples < 1 or num_of_rays < 1 or max_depth < 0 or depth < 0:
+            raise UsageError("--samples and --num-of-rays must be at least 1, --max-depth and --depth not negative")
+        if max_depth - depth > 64:
+            raise UsageError(f"--max-depth {max_depth} with --depth {depth}: a probe walks at most 64 levels")
+        if grid is not None:
+            lattice = rb.ProbeGrid(*parse_grid(grid))
+            n = lattice.n  # (counted before the points are made: a lattice can be asked for that no memory holds)
+        else:
+            try:
+                batch = np.load(input_name)
+            except (OSError, ValueError) as e:
+                raise UsageError(f"--input {input_name}: {e}") from None
+            if not isinstance(batch, np.ndarray):  # an .npz
+                names = list(batch.files)
+                if "points" not in names and len(names) != 1:
+                    raise UsageError(f"--input {input_name}: an .npz must hold the points as `points` or as its only array, not {names}")
+                batch = batch["points" if "points" in names else names[0]]
+            if batch.ndim != 2 or batch.shape[1] != 3 or batch.dtype.kind not in "fiu":
+                raise UsageError(f"--input {input_name}: expected [n, 3] points, got {batch.dtype} {batch.shape}")
+            points = np.asarray(batch, dtype=np.float64)
+            n = points.shape[0]
+        if n * samples > rb.MAX_RAYS:
+            raise UsageError(f"{n} probes x {samples} samples: a call takes at most 2^31 - 1 rays (split the points)")
+        if grid is not None:
+            points = lattice.points()
+        world, _, _ = _load_scene(input_scene_name, parse_float_overrides(declare_float), 640, 480)
+    except UsageError as e:
+        click.echo(f"pytracer_amd probes: {e}", err=True)
+        sys.exit(2)
+    from . import _lib, flatten
+    from .device import DeviceScene
+
+    _lib.standalone()  # (torch-free, like `render`)
+    with DeviceScene(flatten.flatten_world(world), device) as scene:
+        res = rb.WorldQueries(scene).radiance_probes(points, samples, init_state, init_seq, None, None, num_of_rays, max_depth,
+                                                     russian_roulette_limit, (0.0, 0.0, 0.0), depth, "all")
+    planes = dict(res.planes(), points=points)
+    np.savez(output, **planes)
+    click.echo(f"{n} probe(s) x {samples} sample(s), {len(world.shapes)} shape(s), {int(res.n_rays.sum())} rays traced: "
+               f"wrote {output} ({', '.join(planes)})")
+
+
 cli.add_command(render)
 cli.add_command(hits)
 cli.add_command(rays)
 cli.add_command(radiance)
 cli.add_command(gather)
 cli.add_command(bake)
+cli.add_command(probes)

@@ -29,6 +29,13 @@ through ``DeviceScene.surface_points`` / ``DeviceScene.bake`` (include/ptrace_ba
 ``WorldQueries.surface_points`` / ``light_map`` / ``outgoing_map``: :class:`BakedMap` views the answer, and
 ``scenes.baked_world`` turns maps into a world ``FlatRenderer`` renders with its indirect light in place.
 
+Its eighth -- the probe: the radiance arriving at a free point of the world from every direction, as the 27 coefficients of the
+nine real spherical-harmonic functions of bands 0 - 2 per colour channel; the cosine-weighted hemisphere mean for ANY normal
+follows from them without a new ray, so a shape that a baked world does not know can be lit from the probes around it -- goes
+through ``DeviceScene.sh_project`` / ``sh_directions`` / ``sh_eval`` (include/ptrace_sh.h, libptrace_sh.so) or
+``WorldQueries.radiance_probes`` / ``probe_directions`` / ``probe_map`` / ``outgoing_probe_map``: :class:`ProbeSet` views the
+answer, :class:`ProbeGrid` places probes on a lattice and blends them.
+
 Layout: planar.  A batch is ``[8, n]`` float64 -- origin xyz, direction xyz, tmin, tmax, the fields of ``Ray`` (ray.py:29-50);
 a result is one buffer, the int32 shape plane first (padded to 8 bytes), then the selected fp64 planes of ``n`` values each.
 """
@@ -64,6 +71,15 @@ _GATHER_OF = {"count": GATHER_COUNT}
 
 BAKE_COUNT, BAKE_ALL = 1, 1  # PT_BAKE_* of include/ptrace_bake.h
 _BAKE_OF = {"count": BAKE_COUNT}
+
+
+SH_COUNT, SH_ALL = 1, 1  # PT_SH_* of include/ptrace_sh.h
+SH_RADIANCE, SH_HEMISPHERE = 0, 1  # the evaluation's kinds
+SH_COEFFS = 27  # planes of coefficients: plane 3 j + ch
+_SH_OF = {"count": SH_COUNT}
+# the basis' constants: ONE fp64 literal each, as the header states them
+SH_K0, SH_K1, SH_K2, SH_K3, SH_K4 = 0.28209479177387814, 0.4886025119029199, 1.0925484305920792, 0.31539156525252005, 0.5462742152960396
+SH_BAND_FACTORS = (1.0,) + (2.0 / 3.0,) * 3 + (0.25,) * 5  # A_j of PT_SH_HEMISPHERE
 
 
 def _parse_channels(channels, names_to_bits, all_bits, what) -> int:
@@ -551,6 +567,181 @@ class BakedMap(_BatchViews):
         return out
 
 
+def sh_channels(channels) -> int:
+    """``PT_SH_*`` bits from an int, a name (``"count"``), ``"all"`` or ``"none"``."""
+    return _parse_channels(channels, _SH_OF, SH_ALL, "probe")
+
+
+def sh_bytes(n: int, channels: int) -> int:
+    """Mirror of ``pt_rays_sh_bytes``: 0 for arguments the library refuses."""
+    if not (0 <= n <= MAX_RAYS and 0 <= channels <= SH_ALL):
+        return 0
+    return n * 8 * (SH_COEFFS + (1 if channels & SH_COUNT else 0))
+
+
+def sh_plane_offset(n: int, channels: int, channel: int, component: int = 0) -> int:
+    """Mirror of ``pt_rays_sh_plane_offset`` (bytes; ``channel`` 0: the 27 coefficient planes, component ``3 j + ch``;
+    ``SH_COUNT``; < 0: not selected)."""
+    if not (0 <= n <= MAX_RAYS and 0 <= channels <= SH_ALL) or component < 0:
+        return -1
+    if channel == 0:
+        return n * 8 * component if component < SH_COEFFS else -1
+    if channel == SH_COUNT and channels & SH_COUNT:
+        return n * 8 * SH_COEFFS if component < 1 else -1
+    return -1
+
+
+def sh_dirs_bytes(n: int, samples: int) -> int:
+    """Mirror of ``pt_rays_sh_dirs_bytes``."""
+    if not (0 <= n <= MAX_RAYS and samples >= 1 and n * samples <= MAX_RAYS):
+        return 0
+    return n * samples * 24
+
+
+def sh_basis(dirs) -> np.ndarray:
+    """``[..., 3]`` directions -> ``[..., 9]``: the nine real SH functions of bands 0 - 2 as include/ptrace_sh.h states them
+    (the literals, the order of the products; the directions are not normalised) -- the library's bits, in numpy."""
+    d = np.asarray(dirs, dtype=np.float64)
+    x, y, z = d[..., 0], d[..., 1], d[..., 2]
+    out = np.empty(d.shape[:-1] + (9,), dtype=np.float64)
+    out[..., 0] = SH_K0
+    out[..., 1] = SH_K1 * y
+    out[..., 2] = SH_K1 * z
+    out[..., 3] = SH_K1 * x
+    out[..., 4] = SH_K2 * (x * y)
+    out[..., 5] = SH_K2 * (y * z)
+    out[..., 6] = SH_K3 * (3.0 * (z * z) - 1.0)
+    out[..., 7] = SH_K2 * (x * z)
+    out[..., 8] = SH_K4 * (x * x - y * y)
+    return out
+
+
+def sh_evaluate(coefficients, dirs, kind: int = SH_RADIANCE) -> np.ndarray:
+    """The evaluation of include/ptrace_sh.h in numpy, operation for operation: ``coefficients`` ``[..., 9, 3]`` and ``dirs``
+    ``[..., 3]`` (record by record) -> ``[..., 3]``."""
+    if kind not in (SH_RADIANCE, SH_HEMISPHERE):
+        raise ValueError(f"kind {kind}: an evaluation is SH_RADIANCE (0) or SH_HEMISPHERE (1)")
+    c = np.asarray(coefficients, dtype=np.float64)
+    y = sh_basis(dirs)
+    out = np.zeros(np.broadcast_shapes(c.shape[:-2], y.shape[:-1]) + (3,), dtype=np.float64)
+    for j in range(9):
+        a = SH_BAND_FACTORS[j] if kind == SH_HEMISPHERE else 1.0
+        out = out + (a * y[..., j])[..., None] * c[..., j, :]
+    return out
+
+
+class ProbeSet(_BatchViews):
+    """Views over the buffer of a probe batch (``buf``: ``pt_rays_sh_bytes`` bytes, contiguous ``uint8``).  Nothing here copies.
+    ``coefficients``: ``[..., 9, 3]``, per probe the order-2 SH coefficients ``c[j][ch]`` of the radiance arriving there;
+    ``block``: the same memory as the ``[27, n]`` planes the library reads (plane ``3 j + ch``); ``n_rays``: the rays handed to a
+    world query for the probe (``uint64``).  ``shape``: what the probes' axis is viewed as; default ``[n]``.  ``evaluator``:
+    ``DeviceScene.sh_eval`` of the scene the probes came from (the evaluation reads no scene: any device scene's will do)."""
+
+    _names, _all, _what, _unit = _SH_OF, SH_ALL, "probe", "probes"
+    _bytes, _offset = staticmethod(sh_bytes), staticmethod(sh_plane_offset)
+
+    def __init__(self, buf, n: int, channels=SH_ALL, shape=None, evaluator=None):
+        super().__init__(buf, n, channels, shape)
+        self.evaluator = evaluator
+        self.block = self.buffer[: self.n * 8 * SH_COEFFS].view(np.float64).reshape(SH_COEFFS, self.n)
+        self.coefficients = np.moveaxis(self.block.reshape((9, 3) + self.shape), (0, 1), (-2, -1))
+
+    def has(self, name: str) -> bool:  # (any other name is a channel this batch does not have, not an error)
+        return name in _SH_OF and super().has(name)
+
+    @property
+    def n_rays(self) -> np.ndarray:
+        return self._plane_views(SH_COUNT, 1, np.uint64)[0].reshape(self.shape)
+
+    def planes(self) -> dict:
+        """name -> view, for every selected channel (what the ``probes`` command writes into its ``.npz``)."""
+        out = {"coefficients": self.coefficients}
+        if self.has("count"):
+            out["n_rays"] = self.n_rays
+        return out
+
+    def _eval(self, dirs, index, kind) -> np.ndarray:
+        if self.evaluator is None:
+            raise ValueError("this ProbeSet has no evaluator: pass evaluator=DeviceScene.sh_eval (or use rays.sh_evaluate on the host)")
+        d = np.asarray(dirs, dtype=np.float64)
+        if d.ndim < 1 or d.shape[-1] != 3:
+            raise ValueError(f"expected [..., 3] directions, not {d.shape}")
+        lead = d.shape[:-1]
+        if index is not None:
+            index = np.broadcast_to(np.asarray(index), lead).reshape(-1)
+        out = self.evaluator(self.block, planar(d, 3), index, kind)
+        return np.ascontiguousarray(out.T).reshape(lead + (3,))
+
+    def radiance(self, dirs, index=None) -> np.ndarray:
+        """The band-limited radiance arriving from ``dirs`` (``[..., 3]``; used as they are) at probe ``index`` (one value or
+        one per record; ``None``: record ``r`` reads probe ``r``) -> ``[..., 3]``, on the device (``sh_eval``)."""
+        return self._eval(dirs, index, SH_RADIANCE)
+
+    def hemisphere_mean(self, normals, index=None) -> np.ndarray:
+        """``(1 / pi) *`` the integral of the radiance times the cosine over the hemisphere around ``normals`` (``[..., 3]``, unit
+        length) at probe ``index`` -- what a gather record or a light-map texel holds -> ``[..., 3]``, on the device."""
+        return self._eval(normals, index, SH_HEMISPHERE)
+
+
+class ProbeGrid:
+    """A lattice of probe positions on the host: ``dims = (nx, ny, nz)`` points from ``origin`` in steps of ``step`` (one number
+    or three).  Probe ``(ix, iy, iz)`` has the index ``(iz * ny + iy) * nx + ix``."""
+
+    def __init__(self, origin, step, dims):
+        self.origin = np.asarray(origin, dtype=np.float64).reshape(3)
+        self.step = np.broadcast_to(np.asarray(step, dtype=np.float64), (3,)).copy()
+        self.dims = tuple(int(x) for x in dims)
+        if len(self.dims) != 3 or min(self.dims) < 1:
+            raise ValueError(f"dims must be three counts of at least 1, not {dims}")
+        if not np.all(self.step > 0.0):
+            raise ValueError(f"step must be positive, not {step}")
+        self.n = self.dims[0] * self.dims[1] * self.dims[2]
+
+    def points(self) -> np.ndarray:
+        """``[n, 3]``: the probes' positions in index order -- the ``points`` of ``radiance_probes``."""
+        nx, ny, nz = self.dims
+        iz, iy, ix = np.meshgrid(np.arange(nz), np.arange(ny), np.arange(nx), indexing="ij")
+        idx = np.stack([ix, iy, iz], axis=-1).reshape(-1, 3).astype(np.float64)
+        return self.origin + idx * self.step
+
+    def corners(self, points):
+        """``(index [m, 8], weight [m, 8])``: the eight probes around every point and their trilinear weights (a point outside
+        the lattice takes the nearest cell's border)."""
+        p = np.asarray(points, dtype=np.float64).reshape(-1, 3)
+        top = np.maximum(np.asarray(self.dims) - 2, 0)
+        g = (p - self.origin) / self.step
+        near = np.rint(g)
+        g = np.where(np.abs(g - near) <= 4.0 * np.finfo(np.float64).eps * np.maximum(np.abs(g), 1.0), near, g)  # a lattice point is ON it
+        i0 = np.clip(np.floor(g), 0, top).astype(np.int64)
+        f = np.clip(g - i0, 0.0, 1.0)
+        i1 = np.minimum(i0 + 1, np.asarray(self.dims) - 1)
+        nx, ny, _ = self.dims
+        index = np.empty((p.shape[0], 8), dtype=np.int64)
+        weight = np.empty((p.shape[0], 8), dtype=np.float64)
+        for c in range(8):
+            bx, by, bz = c & 1, (c >> 1) & 1, (c >> 2) & 1
+            ix, iy, iz = (i1 if bx else i0)[:, 0], (i1 if by else i0)[:, 1], (i1 if bz else i0)[:, 2]
+            index[:, c] = (iz * ny + iy) * nx + ix
+            weight[:, c] = (f[:, 0] if bx else 1.0 - f[:, 0]) * (f[:, 1] if by else 1.0 - f[:, 1]) * (f[:, 2] if bz else 1.0 - f[:, 2])
+        return index, weight
+
+    def blend(self, probes: "ProbeSet", points) -> "ProbeSet":
+        """Per point the coefficients blended from the eight probes around it by trilinear weights (numpy) -> a :class:`ProbeSet`
+        of one record per point, whose ``radiance`` / ``hemisphere_mean`` (``index=None``) evaluate the blend."""
+        if probes.n != self.n:
+            raise ValueError(f"{probes.n} probes for a lattice of {self.n}")
+        p = np.asarray(points, dtype=np.float64)
+        lead = p.shape[:-1]
+        index, weight = self.corners(p)
+        m = index.shape[0]
+        buf = np.zeros(max(sh_bytes(m, 0), 8), dtype=np.uint8)
+        out = ProbeSet(buf, m, 0, shape=lead, evaluator=probes.evaluator)
+        block = probes.block
+        for c in range(8):
+            out.block[:] = out.block + weight[:, c][None, :] * block[:, index[:, c]]
+        return out
+
+
 def texel_centres(width: int, height: int, window=None) -> np.ndarray:
     """``[h, w, 2]``: ``(u, v)`` at the centres of the texels of ``window`` (``(col0, row0, w, h)``; ``None``: all) of a
     ``width x height`` map, as the bake forms them: ``(col + 0.5) * (1.0 / width)``, ``(row + 0.5) * (1.0 / height)``."""
@@ -728,3 +919,47 @@ class WorldQueries:
             raise ValueError(f"shape {shape} has no DiffuseBRDF: what a mirror sends out depends on where it is seen from, a map cannot hold it")
         baked = self.light_map(shape, width, height, samples, side, jitter, **kw)
         return np.asarray(mat.emitted) + np.asarray(mat.brdf_color) * np.asarray(baked.radiance)
+
+    def radiance_probes(self, points, samples, init_state: int = 42, init_seq: int = 54, seqs=None, active=None, num_of_rays: int = 1,
+                        max_depth: int = 10, russian_roulette_limit: int = 3, background=(0.0, 0.0, 0.0), depth: int = 1,
+                        channels="all") -> ProbeSet:
+        """The order-2 spherical-harmonic coefficients of the radiance arriving at every point of ``points`` (``[..., 3]``, free
+        points of the world: no surface, no normal): ``samples`` rays per probe, sample ``k`` of probe ``i`` uniform on the sphere
+        from ``PCG(init_state, seqs[i] + k)`` and followed by ``PathTracer(world, background, that generator, num_of_rays,
+        max_depth, russian_roulette_limit)``; projected on the device, strictly in sample order.  ``seqs=None``: probe ``i``
+        starts at stream ``init_seq + i * samples``.  ``active``: an optional int32 array, negative = skipped.  ``depth``: the
+        rays' ``Ray.depth``; the default 1 (as :meth:`light_map`) means they are the rays a depth-0 hit at that point would
+        send -> :class:`ProbeSet`, shaped like the points."""
+        points = np.asarray(points, dtype=np.float64)
+        if points.ndim < 1 or points.shape[-1] != 3:
+            raise ValueError(f"points must be [..., 3], not {points.shape}")
+        bits = sh_channels(channels)
+        out = self.scene.sh_project(planar(points, 3), samples, init_state, init_seq, seqs, active, num_of_rays, max_depth,
+                                    russian_roulette_limit, background, depth, bits)
+        return ProbeSet(out.buffer, out.n, bits, shape=points.shape[:-1], evaluator=self.scene.sh_eval)
+
+    def probe_directions(self, n: int, samples: int, init_state: int = 42, init_seq: int = 54, seqs=None) -> np.ndarray:
+        """``[n, samples, 3]``: the directions the samples of ``n`` probes take, made on the device by the function the
+        projection uses (what :meth:`surface_points` is for the bake)."""
+        out = self.scene.sh_directions(n, samples, init_state, init_seq, seqs)
+        return np.ascontiguousarray(out.T).reshape(int(n), int(samples), 3)
+
+    def probe_map(self, shape: int, width: int, height: int, probes: ProbeSet, probe: int = 0, side: int = 1) -> np.ndarray:
+        """``[height, width, 3]``: the light map of ``World.shapes[shape]`` as ONE probe sees it -- ``probes.hemisphere_mean`` at
+        the normals of the texel centres (:meth:`surface_points`).  For a shape small against its distance to everything else:
+        the probe stands for every point of it."""
+        _, normals = self.surface_points(shape, texel_centres(width, height), side)
+        return probes.hemisphere_mean(normals, index=int(probe))
+
+    def outgoing_probe_map(self, shape: int, width: int, height: int, probes: ProbeSet, probe: int = 0, side: int = 1) -> np.ndarray:
+        """``[height, width, 3]``: what a ``DiffuseBRDF`` shape sends out at every texel when lit by one probe, ``emitted(uv_c) +
+        brdf_color(uv_c) * probe_map`` (:meth:`outgoing_map` with :meth:`probe_map` in place of a bake): a map for
+        ``scenes.baked_world``."""
+        from types import SimpleNamespace
+
+        centres = texel_centres(width, height)
+        index = np.full(centres.shape[:-1], int(shape), dtype=np.int32)
+        mat = self.materials(SimpleNamespace(shape_index=index, uv=centres))
+        if not np.all(np.asarray(mat.brdf_kind) == abi.BRDF_DIFFUSE):
+            raise ValueError(f"shape {shape} has no DiffuseBRDF: what a mirror sends out depends on where it is seen from, a map cannot hold it")
+        return np.asarray(mat.emitted) + np.asarray(mat.brdf_color) * self.probe_map(shape, width, height, probes, probe, side)
