@@ -593,7 +593,71 @@ def probes(grid, input_name, output, samples, num_of_rays, max_depth, russian_ro
                f"wrote {output} ({', '.join(planes)})")
 
 
+def load_probes(name: str, n: int):
+    """The ``coefficients`` of the .npz the ``probes`` command wrote, as the ``[27, n]`` block of a lattice of ``n`` probes."""
+    import numpy as np
+
+    try:
+        batch = np.load(name)
+        if isinstance(batch, np.ndarray):
+            raise UsageError(f"--probes {name}: an array, not the .npz the probes command writes")
+        with batch:
+            if "coefficients" not in batch.files:
+                raise UsageError(f"--probes {name}: no `coefficients` in it ({', '.join(batch.files)}): not written by the probes command?")
+            c = np.asarray(batch["coefficients"])
+    except (OSError, ValueError) as e:
+        raise UsageError(f"--probes {name}: {e}") from None
+    if c.ndim != 3 or c.shape[1:] != (9, 3) or c.dtype.kind != "f":
+        raise UsageError(f"--probes {name}: expected coefficients [n, 9, 3], got {c.dtype} {c.shape}")
+    if c.shape[0] != n:
+        raise UsageError(f"--probes {name} holds {c.shape[0]} probes, the lattice of --grid has {n}")
+    return np.ascontiguousarray(np.asarray(c, dtype=np.float64).transpose(1, 2, 0)).reshape(27, n)
+
+
+@click.command("lit")
+@click.option("--probes", "probes_name", type=str, required=True, help="The .npz the probes command wrote for the lattice of --grid")
+@click.option("--grid", type=str, required=True, help="The probes' lattice: ox,oy,oz,step,nx,ny,nz (as given to the probes command)")
+@click.option("--width", type=int, default=640, help="Width of the frame")
+@click.option("--height", type=int, default=480, help="Height of the frame")
+@click.option("--output", type=str, default="frame.pfm", help="Name of the .pfm file to create")
+@click.option("--declare-float", "-d", type=str, multiple=True, help="Declare a variable: --declare-float=VAR:VALUE")
+@click.option("--device", type=int, default=0, help="GPU to render on")
+@click.argument("input_scene_name", type=str, default="builtin:demo")
+def lit(probes_name, grid, width, height, output, declare_float, device, input_scene_name):
+    """A frame of the scene lit by a lattice of radiance probes: per pixel emitted + brdf_color * E, with E the eight probes
+    around the hit point blended and evaluated on the device (the hemisphere mean around the normal of a diffuse surface, the
+    radiance from the mirror direction of a specular one); black where nothing is hit.  Writes a PFM."""
+    from . import rays as rb
+
+    try:
+        if width < 1 or height < 1:
+            raise UsageError("--width and --height must be at least 1")
+        lattice = rb.ProbeGrid(*parse_grid(grid))
+        block = load_probes(probes_name, lattice.n)
+        world, camera, _ = _load_scene(input_scene_name, parse_float_overrides(declare_float), width, height)
+    except UsageError as e:
+        click.echo(f"pytracer_amd lit: {e}", err=True)
+        sys.exit(2)
+    from . import _lib, prefer_device_kernargs
+    from .shaders import ProbeLitShader
+
+    prefer_device_kernargs()
+    _lib.standalone()  # (torch-free, like `probes`)
+    image = hm.HdrImage(width, height)
+    tracer = GpuImageTracer(image=image, camera=camera, samples_per_side=0, device=device)
+    probe_set = rb.ProbeSet(block.reshape(-1).view("uint8"), lattice.n, 0, evaluator=tracer.world_queries(world).scene.sh_eval)
+    started = perf_counter()
+    tracer.fire_all_rays(ProbeLitShader(world, lattice, probe_set, tracer))
+    wall = perf_counter() - started
+    with open(output, "wb") as f:
+        image.write_pfm(f)
+    click.echo(f"{width}x{height} px, {len(world.shapes)} shape(s), a lattice of {'x'.join(str(d) for d in lattice.dims)} probes, "
+               f"{wall:.3f} s: wrote {output}")
+    tracer.close()
+
+
 cli.add_command(render)
+cli.add_command(lit)
 cli.add_command(hits)
 cli.add_command(rays)
 cli.add_command(radiance)

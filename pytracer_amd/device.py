@@ -802,6 +802,112 @@ class DeviceScene:
         _sh_lib.check(L.pt_rays_sh_eval(self.device, p(coeffs), n, p(index), p(dirs), m, int(kind), p(buf), buf.nbytes))
         return buf
 
+    # -- lit queries (include/ptrace_lit.h, libptrace_lit.so): records shaded from a lattice of probes ---------------------------
+    @staticmethod
+    def _lit_grid(grid):
+        """``(pt_lit_grid, n)`` from a :class:`pytracer_amd.rays.ProbeGrid` (anything with ``origin``, ``step`` and ``dims``)."""
+        from . import _lit_lib
+
+        g = _lit_lib.grid(grid.origin, grid.step, grid.dims)
+        return g, int(g.dims[0]) * int(g.dims[1]) * int(g.dims[2])
+
+    def lit_eval(self, grid, coeffs, points, dirs, active=None, kind: int = 0, device: bool = False, stream=None, out=None, m=None):
+        """Per record the coefficients of the eight probes of ``grid`` around ``points[:, r]``, blended by trilinear weights
+        (``ProbeGrid.corners`` / ``blend``) and evaluated towards ``dirs[:, r]`` (``kind``: ``PT_SH_RADIANCE`` 0 or
+        ``PT_SH_HEMISPHERE`` 1), in one kernel -> planar ``[3, m]`` float64.  ``coeffs``: the ``[27, n]`` block of the lattice's
+        probes; ``points``, ``dirs``: planar ``[3, m]``; ``active``: optional int32, negative = zeros.  A NaN point gives zeros.
+        No scene is read.  ``device=True``: the planes are in HBM (with ``m=`` where they are raw addresses), the batch is enqueued
+        on ``stream`` -> the output ``DeviceBuffer`` (``out``, or a new one)."""
+        from . import _lit_lib
+
+        L = _lit_lib.lib()
+        g, n = self._lit_grid(grid)
+        if device:
+            handle = getattr(stream, "handle", stream)
+            if m is None:
+                if not hasattr(points, "nbytes"):
+                    raise ValueError("m= is needed when the points are a raw device address")
+                m = int(points.nbytes) // 24
+            m = int(m)
+            if out is None:
+                from .devmem import DeviceBuffer
+
+                out = DeviceBuffer((3, max(m, 1)), np.float64, self.device)
+            ptr = self._plane_ptr
+            co_bytes = int(coeffs.nbytes) if hasattr(coeffs, "nbytes") else 216 * n
+            _lit_lib.check(L.pt_rays_lit_eval_device(self.device, C.byref(g), ptr(coeffs, "coeffs"), co_bytes, ptr(points, "points"),
+                                                     ptr(dirs, "dirs"), ptr(active, "active"), m, int(kind), ptr(out, "out"), int(out.nbytes),
+                                                     C.c_void_p(handle) if handle else None))
+            if hasattr(out, "rendered_on"):
+                out.rendered_on(stream)
+            return out
+        if stream is not None or out is not None or m is not None:
+            raise ValueError("stream=, out= and m= go with device=True (host batches are staged and synchronous)")
+        coeffs = np.ascontiguousarray(coeffs, dtype=np.float64)
+        points = np.ascontiguousarray(points, dtype=np.float64)
+        dirs = np.ascontiguousarray(dirs, dtype=np.float64)
+        if coeffs.ndim != 2 or coeffs.shape[0] != 27:
+            raise ValueError(f"coeffs must be the [27, n] block of a probe set, not {coeffs.shape}")
+        if points.ndim != 2 or points.shape[0] != 3 or dirs.shape != points.shape:
+            raise ValueError(f"points and dirs must be planar [3, m] (pytracer_amd.rays.planar), not {points.shape} and {dirs.shape}")
+        m = points.shape[1]
+        if active is not None:
+            active = np.ascontiguousarray(np.asarray(active).reshape(-1), dtype=np.int32)
+            if active.shape != (m,):
+                raise ValueError(f"active must hold one int32 per record ({m}), not {active.shape}")
+        buf = np.empty((3, m), dtype=np.float64)
+        p = lambda a: a.ctypes.data_as(C.c_void_p) if a is not None else None  # noqa: E731
+        _lit_lib.check(L.pt_rays_lit_eval(self.device, C.byref(g), p(coeffs), coeffs.nbytes, p(points), p(dirs), p(active), m, int(kind), p(buf),
+                                          buf.nbytes))
+        return buf
+
+    def lit_shade(self, grid, coeffs, shape_index, point, normal, uv, dirs, background=(0.0, 0.0, 0.0), device: bool = False, stream=None,
+                  out=None, n=None):
+        """Every hit record shaded from the lattice ``grid`` of probes ``coeffs`` (``[27, n_probes]``): ``background`` where nothing
+        was hit, else ``emitted(uv) + brdf_color(uv) * E`` with ``E`` the blend at ``point`` evaluated as the cosine-weighted
+        hemisphere mean around the unit normal (``DiffuseBRDF``) or as the radiance from the mirror direction (``SpecularBRDF``)
+        -- :func:`pytracer_amd.rays.lit_shade_host` on the device, in one kernel.  ``point``, ``normal``, ``dirs``: ``[..., 3]``,
+        ``uv``: ``[..., 2]``, ``dirs`` the directions of the rays that were traced -> ``[n, 3]`` float64 (a view of the three planes
+        the library wrote).  ``device=True``: planes in HBM as for :meth:`shade_lights` (a hit frame's own, with ``n=``); -> the
+        output ``DeviceBuffer`` of ``[3, n]`` float64."""
+        from . import _lit_lib, rays as rb
+
+        L, block = _lit_lib.lib(), self.kernel_args()
+        g, n_probes = self._lit_grid(grid)
+        bg = _lit_lib.rgb(background)
+        if device:
+            handle = getattr(stream, "handle", stream)
+            n = self._device_count(shape_index, n)
+            if out is None:
+                from .devmem import DeviceBuffer
+
+                out = DeviceBuffer((3, max(n, 1)), np.float64, self.device)
+            ptr = self._plane_ptr
+            slots = self.slot_table()
+            co_bytes = int(coeffs.nbytes) if hasattr(coeffs, "nbytes") else 216 * n_probes
+            _lit_lib.check(L.pt_rays_lit_shade_device(self.device, block, len(block), C.c_void_p(slots.data_ptr()), int(slots.nbytes), C.byref(g),
+                                                      ptr(coeffs, "coeffs"), co_bytes, ptr(shape_index, "shape_index"), ptr(point, "point"),
+                                                      ptr(normal, "normal"), ptr(uv, "uv"), ptr(dirs, "dirs"), n, bg, ptr(out, "out"),
+                                                      int(out.nbytes), C.c_void_p(handle) if handle else None))
+            if hasattr(out, "rendered_on"):
+                out.rendered_on(stream)
+            return out
+        if stream is not None or out is not None or n is not None:
+            raise ValueError("stream=, out= and n= go with device=True (host batches are staged and synchronous)")
+        coeffs = np.ascontiguousarray(coeffs, dtype=np.float64)
+        if coeffs.ndim != 2 or coeffs.shape[0] != 27:
+            raise ValueError(f"coeffs must be the [27, n] block of a probe set, not {coeffs.shape}")
+        shape = np.ascontiguousarray(shape_index, dtype=np.int32).reshape(-1)
+        n = shape.shape[0]
+        planes = [rb.planar(point, 3), rb.planar(normal, 3), rb.planar(uv, 2), rb.planar(dirs, 3)]
+        if any(p.shape[1] != n for p in planes):
+            raise ValueError(f"{n} shape indices but {[p.shape[1] for p in planes]} points, normals, (u, v) pairs and directions")
+        buf = np.empty((3, n), dtype=np.float64)
+        _lit_lib.check(L.pt_rays_lit_shade(self.device, block, len(block), C.byref(g), coeffs.ctypes.data_as(C.c_void_p), coeffs.nbytes,
+                                           shape.ctypes.data_as(C.c_void_p), *[p.ctypes.data_as(C.c_void_p) for p in planes], n, bg,
+                                           buf.ctypes.data_as(C.c_void_p), buf.nbytes))
+        return buf.T
+
     def cull_probe(self, cam: abi.Camera, width: int, height: int, x0: int, x1: int, row0: int, row1: int,
                    pixel=None) -> np.ndarray:
         """Diagnostics: which shapes (by ``World.shapes`` index) the conservative cull of the primary rays through

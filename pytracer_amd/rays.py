@@ -36,6 +36,11 @@ through ``DeviceScene.sh_project`` / ``sh_directions`` / ``sh_eval`` (include/pt
 ``WorldQueries.radiance_probes`` / ``probe_directions`` / ``probe_map`` / ``outgoing_probe_map``: :class:`ProbeSet` views the
 answer, :class:`ProbeGrid` places probes on a lattice and blends them.
 
+Its ninth -- the lattice on the device: per record the eight probes around its point blended and evaluated in one kernel, alone
+(``DeviceScene.lit_eval``, ``ProbeGrid.evaluate``) or fused with the material look-up into ``emitted + brdf_color * E``
+(``DeviceScene.lit_shade``, ``WorldQueries.probe_lit_radiance``; include/ptrace_lit.h, libptrace_lit.so).  :func:`lit_eval_host` and
+:func:`lit_shade_host` are the numpy mirrors that define the bits; ``shaders.ProbeLitShader`` renders frames with it.
+
 Layout: planar.  A batch is ``[8, n]`` float64 -- origin xyz, direction xyz, tmin, tmax, the fields of ``Ray`` (ray.py:29-50);
 a result is one buffer, the int32 shape plane first (padded to 8 bytes), then the selected fp64 planes of ``n`` values each.
 """
@@ -741,6 +746,80 @@ class ProbeGrid:
             out.block[:] = out.block + weight[:, c][None, :] * block[:, index[:, c]]
         return out
 
+    def evaluate(self, probes: "ProbeSet", points, dirs, kind: int = SH_RADIANCE, active=None) -> np.ndarray:
+        """What ``blend(probes, points)`` evaluated towards ``dirs`` gives -- ``radiance`` (``kind=SH_RADIANCE``) or
+        ``hemisphere_mean`` (``SH_HEMISPHERE``) -- in every bit, on the device in ONE kernel (``DeviceScene.lit_eval`` of the scene
+        ``probes.evaluator`` belongs to; include/ptrace_lit.h): no blended block is made.  ``points``, ``dirs``: ``[..., 3]``;
+        ``active``: optional int32 per record, negative = zeros -> ``[..., 3]``.  A NaN point gives zeros."""
+        if probes.n != self.n:
+            raise ValueError(f"{probes.n} probes for a lattice of {self.n}")
+        scene = getattr(probes.evaluator, "__self__", None)
+        if scene is None or not callable(getattr(scene, "lit_eval", None)):
+            raise ValueError("this ProbeSet has no device scene behind its evaluator: pass evaluator=DeviceScene.sh_eval (or use rays.lit_eval_host)")
+        p, d = np.asarray(points, dtype=np.float64), np.asarray(dirs, dtype=np.float64)
+        if p.ndim < 1 or p.shape[-1] != 3 or d.shape != p.shape:
+            raise ValueError(f"expected [..., 3] points and as many directions, not {p.shape} and {d.shape}")
+        out = scene.lit_eval(self, probes.block, planar(p, 3), planar(d, 3), active, kind)
+        return np.ascontiguousarray(out.T).reshape(p.shape)
+
+
+def _unit_rows(a) -> np.ndarray:
+    """``Vec.normalize`` / ``Normal.normalize`` (geometry.py:130-136, 219-225) per row, with ``x * x`` for ``x**2`` as the device."""
+    x, y, z = a[..., 0], a[..., 1], a[..., 2]
+    with np.errstate(all="ignore"):  # (a record without a hit holds a zero normal: NaN, as on the device)
+        return a / np.sqrt(x * x + y * y + z * z)[..., None]
+
+
+def mirror_directions(dirs, normals) -> np.ndarray:
+    """The direction ``SpecularBRDF.scatter_ray`` (materials.py:186-192) sends a ray arriving along ``dirs`` at ``normals``
+    (``[..., 3]`` both), as the device's ``scatter_ray`` forms it: ``rd - (nn . rd) * (2.0 * nn)`` of the two normalised vectors."""
+    rd, nn = _unit_rows(np.asarray(dirs, dtype=np.float64)), _unit_rows(np.asarray(normals, dtype=np.float64))
+    dp = nn[..., 0] * rd[..., 0] + nn[..., 1] * rd[..., 1] + nn[..., 2] * rd[..., 2]
+    return rd - dp[..., None] * (2.0 * nn)
+
+
+def lit_eval_host(grid: ProbeGrid, probes: ProbeSet, points, dirs, kind: int = SH_RADIANCE, active=None) -> np.ndarray:
+    """The numpy mirror of the lit query (include/ptrace_lit.h), made of ``ProbeGrid.corners`` / ``blend`` and :func:`sh_evaluate``
+    alone: ``[m, 3]`` points and directions -> ``[m, 3]``.  The one case numpy leaves undefined follows the library's rule: a NaN
+    coordinate gives ``+0.0`` (the record is blended at the lattice's origin, then replaced); ``active < 0`` gives zeros."""
+    p = np.asarray(points, dtype=np.float64).reshape(-1, 3)
+    d = np.asarray(dirs, dtype=np.float64).reshape(-1, 3)
+    nan = np.isnan(p).any(axis=1)
+    with np.errstate(all="ignore"):
+        blended = grid.blend(probes, np.where(nan[:, None], grid.origin[None, :], p))
+        out = sh_evaluate(blended.coefficients, d, kind)
+    out[nan] = 0.0
+    if active is not None:
+        out[np.asarray(active).reshape(-1) < 0] = 0.0
+    return out
+
+
+def lit_shade_host(grid: ProbeGrid, probes: ProbeSet, materials, point, normal, dirs, background=(0.0, 0.0, 0.0)) -> np.ndarray:
+    """The numpy mirror of the shade query (include/ptrace_lit.h), operation for operation.  ``materials``: the records'
+    :class:`SurfaceColors` (``WorldQueries.materials``: BRDF kind, ``brdf_color``, ``emitted``); ``point``, ``normal``, ``dirs``:
+    ``[..., 3]`` as a hit frame or a :class:`RayHits` has them -> ``[..., 3]``: ``background`` where nothing was hit, else
+    ``emitted + brdf_color * E`` with ``E`` the blend at ``point`` (:meth:`ProbeGrid.corners`, :meth:`ProbeGrid.blend`) evaluated
+    (:func:`sh_evaluate`) as the hemisphere mean around the normalised normal (``DiffuseBRDF``) or as the radiance from
+    :func:`mirror_directions` (``SpecularBRDF``).  Records without a hit are not evaluated; a NaN point gives ``E = +0.0``."""
+    kind = np.asarray(materials.brdf_kind)
+    lead = kind.shape
+    kind = kind.reshape(-1)
+    p = np.asarray(point, dtype=np.float64).reshape(-1, 3)
+    nrm = np.asarray(normal, dtype=np.float64).reshape(-1, 3)
+    d = np.asarray(dirs, dtype=np.float64).reshape(-1, 3)
+    bg = (background.r, background.g, background.b) if hasattr(background, "r") else tuple(float(x) for x in background)
+    out = np.empty((kind.shape[0], 3), dtype=np.float64)
+    out[:] = bg
+    pc, em = np.asarray(materials.brdf_color).reshape(-1, 3), np.asarray(materials.emitted).reshape(-1, 3)
+    with np.errstate(all="ignore"):
+        for brdf, sh_kind in ((abi.BRDF_DIFFUSE, SH_HEMISPHERE), (abi.BRDF_SPECULAR, SH_RADIANCE)):
+            rows = np.flatnonzero(kind == brdf)
+            if rows.size == 0:
+                continue
+            towards = _unit_rows(nrm[rows]) if brdf == abi.BRDF_DIFFUSE else mirror_directions(d[rows], nrm[rows])
+            out[rows] = em[rows] + pc[rows] * lit_eval_host(grid, probes, p[rows], towards, sh_kind)
+    return out.reshape(lead + (3,))
+
 
 def texel_centres(width: int, height: int, window=None) -> np.ndarray:
     """``[h, w, 2]``: ``(u, v)`` at the centres of the texels of ``window`` (``(col0, row0, w, h)``; ``None``: all) of a
@@ -830,6 +909,27 @@ class WorldQueries:
             dirs = hits.ray_dir
         out = self.scene.shade_lights(hits.shape_index, hits.point, hits.normal, hits.uv, dirs, ambient, background)
         return out.reshape(hits.shape_index.shape + (3,))
+
+    def probe_lit_radiance(self, grid: "ProbeGrid", probes: "ProbeSet", hits, dirs=None, background=(0.0, 0.0, 0.0)) -> np.ndarray:
+        """Every record of ``hits`` shaded from the lattice ``grid`` of ``probes``: ``background`` where nothing was hit, else
+        ``emitted + brdf_color * E``, ``E`` the eight probes around the hit point blended and evaluated towards the normal
+        (``DiffuseBRDF``: the hemisphere mean) or the mirror direction (``SpecularBRDF``: the radiance) -- one kernel on the device
+        (``DeviceScene.lit_shade``), :func:`lit_shade_host` in every bit.  ``hits``: a :class:`RayHits` or a hit-record frame with
+        ``point``, ``normal`` and ``uv``, or a mapping of plain arrays ``shape_index``, ``point``, ``normal``, ``uv``; ``dirs``: the
+        directions of the rays that were traced (default: a frame's ``ray_dir``) -> ``hits.shape_index.shape + (3,)``."""
+        if probes.n != grid.n:
+            raise ValueError(f"{probes.n} probes for a lattice of {grid.n}")
+        if isinstance(hits, dict):
+            from types import SimpleNamespace
+
+            hits = SimpleNamespace(**{k: np.asarray(v) for k, v in hits.items()})
+        if dirs is None:
+            if not hasattr(hits, "ray_dir"):
+                raise ValueError("dirs= is needed: a ray batch does not carry the rays it was traced from")
+            dirs = hits.ray_dir
+        index = np.asarray(hits.shape_index)
+        out = self.scene.lit_shade(grid, probes.block, index, hits.point, hits.normal, hits.uv, dirs, background)
+        return out.reshape(index.shape + (3,))
 
     def scatter(self, hits, dirs, pcg, roulette: bool = False, channels=SCAT_ALL) -> ScatteredRays:
         """The bounce of ``PathTracer.__call__`` (render.py:107-134, one child) for every record of ``hits`` -- a

@@ -416,6 +416,54 @@ class PathRadianceShader(_HitShader):
         return Color(em.r + cr * k, em.g + cg * k, em.b + cb * k)
 
 
+class ProbeLitShader(_HitShader):
+    """A world lit by a lattice of SH radiance probes, as a hit shader: ``background_color`` where nothing is hit, else
+    ``emitted + brdf_color * E`` with ``E`` the eight probes of ``grid`` (a :class:`pytracer_amd.rays.ProbeGrid`) around the hit
+    point blended and evaluated -- the cosine-weighted hemisphere mean around the normal for a ``DiffuseBRDF``, the radiance from
+    the mirror direction for a ``SpecularBRDF``.  No ray is scattered: a frame costs its hit frame plus one kernel
+    (``WorldQueries.probe_lit_radiance``; include/ptrace_lit.h).  ``probes``: the :class:`pytracer_amd.rays.ProbeSet` of
+    ``grid.points()``; ``tracer``: the ``GpuImageTracer`` whose cached device scene answers (``None`` for a shader that is only
+    ever called ray by ray).  The world may be a baked one (``scenes.baked_world``): a black BRDF leaves its emitted map as it is.
+
+    ``__call__(ray)`` is the numpy mirror (``rays.lit_shade_host``'s arithmetic for one record) on a world that has
+    ``ray_intersection(ray)``; the record's material is ``record.material`` or ``world.shapes[record.shape_index].material``."""
+
+    hit_channels = abi.HIT_ALL
+
+    def __init__(self, world, grid, probes, tracer=None, background_color: Color = BLACK):
+        super().__init__(world, background_color)
+        if probes.n != grid.n:
+            raise ValueError(f"{probes.n} probes for a lattice of {grid.n}")
+        self.grid, self.probes, self.tracer = grid, probes, tracer
+
+    def shade_hits(self, frame) -> np.ndarray:
+        if self.tracer is None:
+            raise TypeError("ProbeLitShader.shade_hits needs the tracer whose device scene holds the world: ProbeLitShader(world, grid, probes, tracer)")
+        return self.tracer.world_queries(self.world).probe_lit_radiance(self.grid, self.probes, frame, None, self.background_color)
+
+    def __call__(self, ray) -> Color:
+        if not callable(getattr(self.world, "ray_intersection", None)):
+            raise TypeError(f"{type(self.world).__name__} has no ray_intersection(ray): it is a parameter holder that cannot trace a ray.  "
+                            "Hand ProbeLitShader to GpuImageTracer.fire_all_rays (the device traces), or give it a pytracer World")
+        return self.shade_record(self.world.ray_intersection(ray), ray)
+
+    def shade_record(self, record, ray) -> Color:
+        from .rays import SH_HEMISPHERE, SH_RADIANCE, _unit_rows, lit_eval_host, mirror_directions
+
+        if record is None:
+            return self.background_color
+        material = getattr(record, "material", None) or self.world.shapes[record.shape_index].material
+        uv, wp, nrm = record.surface_point, record.world_point, record.normal
+        pc, em = pigment_color(material.brdf.pigment, uv), pigment_color(material.emitted_radiance, uv)
+        normal = np.array([[nrm.x, nrm.y, nrm.z]], dtype=np.float64)
+        if type(material.brdf).__name__ == "SpecularBRDF":
+            towards, kind = mirror_directions(np.array([[ray.dir.x, ray.dir.y, ray.dir.z]], dtype=np.float64), normal), SH_RADIANCE
+        else:
+            towards, kind = _unit_rows(normal), SH_HEMISPHERE
+        e = lit_eval_host(self.grid, self.probes, np.array([[wp.x, wp.y, wp.z]], dtype=np.float64), towards, kind)[0]
+        return Color(em.r + pc.r * float(e[0]), em.g + pc.g * float(e[1]), em.b + pc.b * float(e[2]))
+
+
 def scatter_ray(brdf, pcg, in_dir, point, normal):
     """``brdf.scatter_ray`` (materials.py:132-152, 175-196; the orthonormal basis of geometry.py:247-262) in Python floats with
     ``x * x`` for ``x**2``, for a BRDF that may be a parameter holder (by class name) -> (origin, direction, tmin)."""
