@@ -656,8 +656,84 @@ def lit(probes_name, grid, width, height, output, declare_float, device, input_s
     tracer.close()
 
 
+@click.command("denoise")
+@click.option("--width", type=int, default=640, help="Width of the frame")
+@click.option("--height", type=int, default=480, help="Height of the frame")
+@click.option("--samples", type=int, default=4, help="Hemisphere rays per pixel of the gather that is filtered")
+@click.option("--passes", type=int, default=4, help="Filter passes, 1 to 10: pass i has the step 2^i")
+@click.option("--sigma-point", type=float, default=0.1, help="Distance from the centre's tangent plane, per step, at which a tap's weight halves (inf: off)")
+@click.option("--normal-power-log2", type=int, default=5, help="e in 0..10: a tap is weighted by cos^(2^e) of the angle between the normals")
+@click.option("--sigma-colour", type=float, default=float("inf"), help="Colour distance at which a tap's weight halves (default inf: off)")
+@click.option("--max-depth", type=int, default=3, help="Maximum allowed ray depth of the gather's walks")
+@click.option("--init-state", type=int, default=45, help="Initial seed for the random number generator.")
+@click.option("--init-seq", type=int, default=54, help="Identifier of the first random sequence.")
+@click.option("--pfm-output", type=str, default="frame.pfm", help="Name of the PFM file to create")
+@click.option("--png-output", type=str, default=None, help="Name of a PNG file of the tone-mapped frame (default: none)")
+@click.option("--noisy-output", type=str, default=None, help="Name of a PFM file for the same frame without the filter (default: none)")
+@click.option("--declare-float", "-d", type=str, multiple=True, help="Declare a variable: --declare-float=VAR:VALUE")
+@click.option("--device", type=int, default=0, help="GPU to render on")
+@click.argument("input_scene_name", type=str, default="builtin:demo")
+def denoise(width, height, samples, passes, sigma_point, normal_power_log2, sigma_colour, max_depth, init_state, init_seq, pfm_output, png_output,
+            noisy_output, declare_float, device, input_scene_name):
+    """A frame of the scene lit by one bounce of few rays and an edge-avoiding filter: per pixel emitted + brdf_color * E, with E
+    the mean radiance over the hit's hemisphere from --samples rays, filtered over the frame under the guidance of the hit
+    records (shape, point, normal) on the device; black where nothing is hit.  Writes a PFM."""
+    import math
+
+    try:
+        if width < 1 or height < 1:
+            raise UsageError("--width and --height must be at least 1")
+        if samples < 1:
+            raise UsageError("--samples must be at least 1")
+        if not 1 <= passes <= 10:
+            raise UsageError("--passes must be 1 to 10")
+        if not 0 <= normal_power_log2 <= 10:
+            raise UsageError("--normal-power-log2 must be 0 to 10")
+        if not sigma_point > 0.0 or not sigma_colour > 0.0 or math.isnan(sigma_point) or math.isnan(sigma_colour):
+            raise UsageError("--sigma-point and --sigma-colour must be positive (or inf)")
+        if max_depth < 0:
+            raise UsageError("--max-depth must not be negative")
+        world, camera, _ = _load_scene(input_scene_name, parse_float_overrides(declare_float), width, height)
+    except UsageError as e:
+        click.echo(f"pytracer_amd denoise: {e}", err=True)
+        sys.exit(2)
+    from . import _lib, prefer_device_kernargs
+    from .shaders import DenoisedGatherShader
+
+    prefer_device_kernargs()
+    _lib.standalone()  # (torch-free, like `lit`)
+    image = hm.HdrImage(width, height)
+    tracer = GpuImageTracer(image=image, camera=camera, samples_per_side=0, device=device)
+    shader = DenoisedGatherShader(world, tracer, samples, init_state=init_state, init_seq=init_seq, max_depth=max_depth, passes=passes,
+                                  sigma_point=sigma_point, normal_power_log2=normal_power_log2, sigma_colour=sigma_colour)
+    wrote = []
+    started = perf_counter()
+    if noisy_output:
+        shader.filtered = False
+        tracer.fire_all_rays(shader)
+        with open(noisy_output, "wb") as f:
+            image.write_pfm(f)
+        wrote.append(noisy_output)
+        shader.filtered = True
+    tracer.fire_all_rays(shader)
+    wall = perf_counter() - started
+    with open(pfm_output, "wb") as f:
+        image.write_pfm(f)
+    wrote.append(pfm_output)
+    if png_output:
+        image.normalize_image(factor=1.0)
+        image.clamp_image()
+        with open(png_output, "wb") as f:
+            image.write_ldr_image(f, "PNG")
+        wrote.append(png_output)
+    click.echo(f"{width}x{height} px, {len(world.shapes)} shape(s), {samples} ray(s) per pixel, {passes} filter pass(es), "
+               f"{wall:.3f} s: wrote {' and '.join(wrote)}")
+    tracer.close()
+
+
 cli.add_command(render)
 cli.add_command(lit)
+cli.add_command(denoise)
 cli.add_command(hits)
 cli.add_command(rays)
 cli.add_command(radiance)

@@ -908,6 +908,63 @@ class DeviceScene:
                                            buf.ctypes.data_as(C.c_void_p), buf.nbytes))
         return buf.T
 
+    # -- denoise queries (include/ptrace_denoise.h, libptrace_denoise.so): an edge-avoiding filter for noisy frames ---------------
+    def denoise_workspace_bytes(self, width: int, height: int, **params) -> int:
+        """Bytes of the workspace :meth:`denoise` needs on the device for a ``width x height`` frame (``params``: its own)."""
+        from . import _denoise_lib
+
+        L, par = _denoise_lib.lib(), _denoise_lib.params(**params)
+        need = int(L.pt_rays_denoise_workspace_bytes(_denoise_lib._addon.c_int(width, "width"), _denoise_lib._addon.c_int(height, "height"), C.byref(par)))
+        if need == 0 and int(width) * int(height) != 0:
+            raise _lib.PtraceError(-1, _denoise_lib.last_error())
+        return need
+
+    def denoise(self, colour, shape_index, normal, point, width: int, height: int, device: bool = False, stream=None, out=None,
+                workspace=None, **params):
+        """The edge-avoiding a-trous filter of include/ptrace_denoise.h over a ``width x height`` frame: ``passes`` passes of a 5x5
+        B3 stencil with the steps 1, 2, 4, ..., every tap weighted by the guides -- skipped on another shape (``same_shape``), cut by
+        the angle between the unit normals (``cos^(2^normal_power_log2)``), by the distance from the centre's tangent plane
+        (``sigma_point``, per step) and optionally by the colour difference (``sigma_colour``); ``wrap_x`` joins the first and the
+        last column.  ``colour``, ``normal``, ``point``: ``[..., 3]`` with ``width * height`` records, ``shape_index``: int32,
+        negative = copied -> ``[height, width, 3]`` float64, :func:`pytracer_amd.rays.denoise_host` in every bit.  No scene is read.
+        ``device=True``: the planes (``[3, m]`` fp64, int32) are in HBM, the passes are enqueued on ``stream`` -> the output
+        ``DeviceBuffer`` (``out``, or a new one); ``workspace``: a ``DeviceBuffer`` of :meth:`denoise_workspace_bytes` (or a new one)."""
+        from . import _denoise_lib, rays as rb
+
+        L, par = _denoise_lib.lib(), _denoise_lib.params(**params)
+        width, height = _denoise_lib._addon.c_int(width, "width"), _denoise_lib._addon.c_int(height, "height")
+        m = width * height
+        if device:
+            from .devmem import DeviceBuffer
+
+            handle = getattr(stream, "handle", stream)
+            if out is None:
+                out = DeviceBuffer((3, max(m, 1)), np.float64, self.device)
+            if workspace is None:
+                workspace = DeviceBuffer((max(self.denoise_workspace_bytes(width, height, **params), 8),), np.uint8, self.device)
+            ptr = self._plane_ptr
+            _denoise_lib.check(L.pt_rays_denoise_device(self.device, width, height, C.byref(par), ptr(colour, "colour"), ptr(normal, "normal"),
+                                                        ptr(point, "point"), ptr(shape_index, "shape_index"), ptr(out, "out"), int(out.nbytes),
+                                                        ptr(workspace, "workspace"), int(workspace.nbytes), C.c_void_p(handle) if handle else None))
+            for buf in (out, workspace):
+                if hasattr(buf, "rendered_on"):
+                    buf.rendered_on(stream)
+            if hasattr(out, "rendered_on"):
+                out._denoise_workspace = workspace  # in flight on `stream` as long as the output is: freed with it
+            return out
+        if stream is not None or out is not None or workspace is not None:
+            raise ValueError("stream=, out= and workspace= go with device=True (host frames are staged and synchronous)")
+        shape = np.ascontiguousarray(shape_index, dtype=np.int32).reshape(-1)
+        planes = [rb.planar(colour, 3), rb.planar(normal, 3), rb.planar(point, 3)]
+        if shape.shape[0] != m or any(p.shape[1] != m for p in planes):
+            raise ValueError(f"a {width} x {height} frame has {m} records, not {shape.shape[0]} shape indices and "
+                             f"{[p.shape[1] for p in planes]} colours, normals and points")
+        buf = np.empty((3, m), dtype=np.float64)
+        p = lambda a: a.ctypes.data_as(C.c_void_p)  # noqa: E731
+        _denoise_lib.check(L.pt_rays_denoise(self.device, width, height, C.byref(par), p(planes[0]), p(planes[1]), p(planes[2]), p(shape), p(buf),
+                                             buf.nbytes))
+        return np.ascontiguousarray(buf.T).reshape(height, width, 3)
+
     def cull_probe(self, cam: abi.Camera, width: int, height: int, x0: int, x1: int, row0: int, row1: int,
                    pixel=None) -> np.ndarray:
         """Diagnostics: which shapes (by ``World.shapes`` index) the conservative cull of the primary rays through

@@ -41,6 +41,11 @@ Its ninth -- the lattice on the device: per record the eight probes around its p
 (``DeviceScene.lit_shade``, ``WorldQueries.probe_lit_radiance``; include/ptrace_lit.h, libptrace_lit.so).  :func:`lit_eval_host` and
 :func:`lit_shade_host` are the numpy mirrors that define the bits; ``shaders.ProbeLitShader`` renders frames with it.
 
+Its tenth -- a remedy for noise other than more rays: an edge-avoiding a-trous filter over a frame or a light map, guided by the
+records' ``shape``, ``point`` and ``normal`` (``DeviceScene.denoise``, ``WorldQueries.denoised`` / ``denoised_light_map``;
+include/ptrace_denoise.h, libptrace_denoise.so).  :func:`denoise_host` is the numpy mirror that defines the bits;
+``shaders.DenoisedGatherShader`` renders frames with it.
+
 Layout: planar.  A batch is ``[8, n]`` float64 -- origin xyz, direction xyz, tmin, tmax, the fields of ``Ray`` (ray.py:29-50);
 a result is one buffer, the int32 shape plane first (padded to 8 bytes), then the selected fp64 planes of ``n`` values each.
 """
@@ -821,6 +826,78 @@ def lit_shade_host(grid: ProbeGrid, probes: ProbeSet, materials, point, normal, 
     return out.reshape(lead + (3,))
 
 
+DENOISE_KERNEL = (0.0625, 0.25, 0.375, 0.25, 0.0625)  # h of include/ptrace_denoise.h: the B3 spline; every product of two is exact
+
+
+def denoise_host(colour, shape, normal, point, width: int, height: int, passes: int = 4, sigma_point: float = 0.1, normal_power_log2: int = 5,
+                 sigma_colour: float = float("inf"), same_shape: bool = True, wrap_x: bool = False) -> np.ndarray:
+    """The numpy mirror of the denoise query (include/ptrace_denoise.h), operation for operation: vectorised per tap over the whole
+    frame, the taps in the header's order (``dy`` outer, ``dx`` inner), every sum in that order.  ``colour``, ``normal``, ``point``:
+    ``width * height`` records of 3 in row-major order (any leading shape), ``shape``: as many int32, negative = copied ->
+    ``[height, width, 3]``.  Refuses what the library refuses, with a ``ValueError``."""
+    W, H, passes, e = int(width), int(height), int(passes), int(normal_power_log2)
+    sigma_point, sigma_colour = float(sigma_point), float(sigma_colour)
+    if W < 0 or H < 0 or W * H > MAX_RAYS:
+        raise ValueError(f"a frame of {W} x {H} records")
+    if not 1 <= passes <= 10 or not 0 <= e <= 10:
+        raise ValueError(f"passes={passes} (1 to 10), normal_power_log2={e} (0 to 10)")
+    if not sigma_point > 0.0 or not sigma_colour > 0.0:
+        raise ValueError(f"sigma_point={sigma_point}, sigma_colour={sigma_colour}: a sigma is positive (or inf)")
+    cur = np.array(colour, dtype=np.float64).reshape(H, W, 3)
+    sh = np.asarray(shape, dtype=np.int32).reshape(H, W)
+    nrm = np.asarray(normal, dtype=np.float64).reshape(H, W, 3)
+    pnt = np.asarray(point, dtype=np.float64).reshape(H, W, 3)
+    if W * H == 0:
+        return cur
+    active = sh >= 0
+    rows, cols = np.arange(H), np.arange(W)
+    with np.errstate(all="ignore"):
+        unit = nrm / np.sqrt(nrm[..., 0] * nrm[..., 0] + nrm[..., 1] * nrm[..., 1] + nrm[..., 2] * nrm[..., 2])[..., None]
+        for i in range(passes):
+            s = 2 ** i
+            sps = sigma_point * float(s)
+            sc = sigma_colour * 2.0 ** -i
+            sc2 = sc * sc
+            total, wsum = np.zeros((H, W, 3)), np.zeros((H, W))
+            for dy in range(-2, 3):
+                qy = rows + s * dy
+                in_y = (qy >= 0) & (qy < H)
+                qy = np.clip(qy, 0, H - 1)
+                for dx in range(-2, 3):
+                    k = DENOISE_KERNEL[dx + 2] * DENOISE_KERNEL[dy + 2]
+                    if dx == 0 and dy == 0:
+                        total, wsum = total + k * cur, wsum + k
+                        continue
+                    qx = cols + s * dx
+                    if wrap_x:
+                        qx, in_x = qx % W, np.ones(W, dtype=bool)
+                    else:
+                        in_x = (qx >= 0) & (qx < W)
+                        qx = np.clip(qx, 0, W - 1)
+                    at = np.ix_(qy, qx)
+                    sq, nq, pq, cq = sh[at], unit[at], pnt[at], cur[at]
+                    take = in_y[:, None] & in_x[None, :] & (sq >= 0)
+                    if same_shape:
+                        take = take & (sq == sh)
+                    c = unit[..., 0] * nq[..., 0] + unit[..., 1] * nq[..., 1] + unit[..., 2] * nq[..., 2]
+                    c = np.where(c > 0.0, c, 0.0)
+                    for _ in range(e):
+                        c = c * c
+                    d = pq - pnt
+                    dz = unit[..., 0] * d[..., 0] + unit[..., 1] * d[..., 1] + unit[..., 2] * d[..., 2]
+                    t = dz / sps
+                    wp = 1.0 / (1.0 + t * t)
+                    dc = cq - cur
+                    d2 = (dc[..., 0] * dc[..., 0] + dc[..., 1] * dc[..., 1]) + dc[..., 2] * dc[..., 2]
+                    wc = 1.0 / (1.0 + d2 / sc2)
+                    w = ((k * c) * wp) * wc
+                    take = take & (w > 0.0)
+                    total = np.where(take[..., None], total + w[..., None] * cq, total)
+                    wsum = np.where(take, wsum + w, wsum)
+            cur = np.where(active[..., None], total / wsum[..., None], cur)
+    return cur
+
+
 def texel_centres(width: int, height: int, window=None) -> np.ndarray:
     """``[h, w, 2]``: ``(u, v)`` at the centres of the texels of ``window`` (``(col0, row0, w, h)``; ``None``: all) of a
     ``width x height`` map, as the bake forms them: ``(col + 0.5) * (1.0 / width)``, ``(row + 0.5) * (1.0 / height)``."""
@@ -1019,6 +1096,55 @@ class WorldQueries:
             raise ValueError(f"shape {shape} has no DiffuseBRDF: what a mirror sends out depends on where it is seen from, a map cannot hold it")
         baked = self.light_map(shape, width, height, samples, side, jitter, **kw)
         return np.asarray(mat.emitted) + np.asarray(mat.brdf_color) * np.asarray(baked.radiance)
+
+    def denoised(self, values, hits, **params) -> np.ndarray:
+        """``values`` filtered by the edge-avoiding a-trous filter of include/ptrace_denoise.h, guided by ``hits`` -- on the device
+        (``DeviceScene.denoise``), :func:`denoise_host` in every bit.  ``values``: a :class:`GatheredRadiance`, a :class:`BakedMap`
+        or a ``[H, W, 3]`` array -- the DEMODULATED signal, ``E`` before ``emitted + brdf_color * E``, so that pigments stay sharp;
+        ``hits``: a hit-record frame with ONE sample per pixel, a :class:`RayHits` whose records are the frame's ``H * W`` in
+        row-major order, or ``(points, normals, shape)`` arrays (``shape``: one index or one per record).  More samples per pixel
+        are a ``ValueError``: average them first.  ``params``: ``passes``, ``sigma_point``, ``normal_power_log2``,
+        ``sigma_colour``, ``same_shape``, ``wrap_x`` -> ``[H, W, 3]``."""
+        if isinstance(hits, (tuple, list)):
+            if len(hits) != 3:
+                raise ValueError("hits as arrays are (points, normals, shape)")
+            points, normals, index = hits
+        else:
+            points, normals, index = hits.point, hits.normal, hits.shape_index
+        index = np.asarray(index)
+        v = np.asarray(values.radiance if hasattr(values, "radiance") else values, dtype=np.float64)
+        for what, a, lead in (("values", v, v.ndim - 1), ("hits", index, index.ndim)):
+            if lead == 3 and a.shape[0] != 1:
+                raise ValueError(f"{what} hold {a.shape[0]} samples per pixel: the filter takes one record per pixel (average the samples first)")
+        if v.ndim == 4:
+            v = v[0]
+        if index.ndim == 3:
+            index = index[0]
+        if v.ndim == 3 and v.shape[-1] == 3:
+            height, width = v.shape[:2]
+        elif index.ndim == 2 and v.size == index.size * 3:
+            height, width = index.shape
+        else:
+            raise ValueError(f"no frame in values {v.shape} and shape indices {index.shape}: pass the values as [H, W, 3]")
+        if index.size not in (1, height * width):
+            raise ValueError(f"{index.size} shape indices for a frame of {height} x {width}")
+        index = np.broadcast_to(index.reshape(-1) if index.size > 1 else index.reshape(()), (height * width,))
+        return self.scene.denoise(v.reshape(-1, 3), index, np.asarray(normals).reshape(-1, 3), np.asarray(points).reshape(-1, 3), width, height, **params)
+
+    def denoised_light_map(self, shape: int, width: int, height: int, samples: int, wrap_u=None, **kw) -> np.ndarray:
+        """:meth:`light_map` of ``World.shapes[shape]`` (the whole map), then :meth:`surface_points` at the texel centres as guides,
+        then :meth:`denoised` -> ``[height, width, 3]``.  ``wrap_u``: the first and the last column are neighbours (default: for a
+        sphere, whose ``u`` is the longitude; not for a plane).  ``kw``: the filter's ``passes``, ``sigma_point``,
+        ``normal_power_log2``, ``sigma_colour`` and ``same_shape``; everything else is :meth:`light_map`'s."""
+        fpar = {k: kw.pop(k) for k in ("passes", "sigma_point", "normal_power_log2", "sigma_colour", "same_shape") if k in kw}
+        if kw.get("window") is not None:
+            raise ValueError("a window of a map has no neighbours beyond its edge: filter the whole map")
+        kw.setdefault("channels", "none")
+        baked = self.light_map(shape, width, height, samples, **kw)
+        points, normals = self.surface_points(shape, texel_centres(width, height), kw.get("side", 1))
+        if wrap_u is None:
+            wrap_u = int(self.scene.flat.kind[int(shape)]) == abi.SHAPE_SPHERE
+        return self.denoised(baked, (points, normals, int(shape)), wrap_x=bool(wrap_u), **fpar)
 
     def radiance_probes(self, points, samples, init_state: int = 42, init_seq: int = 54, seqs=None, active=None, num_of_rays: int = 1,
                         max_depth: int = 10, russian_roulette_limit: int = 3, background=(0.0, 0.0, 0.0), depth: int = 1,

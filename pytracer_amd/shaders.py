@@ -21,6 +21,9 @@ the recursion's sums in numpy.
 
 :class:`PathRadianceShader` is ``PathTracer`` with any number of rays per hit: the frame's primary rays go to one radiance
 query (``WorldQueries.path_radiance``), which walks every sample's tree depth-first on the device.
+
+:class:`DenoisedGatherShader` trades rays for a guided filter: a few hemisphere rays per hit (``WorldQueries.hemisphere_radiance``),
+the edge-avoiding filter of include/ptrace_denoise.h on that mean (``WorldQueries.denoised``), then the material.
 """
 from __future__ import annotations
 
@@ -462,6 +465,80 @@ class ProbeLitShader(_HitShader):
             towards, kind = _unit_rows(normal), SH_HEMISPHERE
         e = lit_eval_host(self.grid, self.probes, np.array([[wp.x, wp.y, wp.z]], dtype=np.float64), towards, kind)[0]
         return Color(em.r + pc.r * float(e[0]), em.g + pc.g * float(e[1]), em.b + pc.b * float(e[2]))
+
+
+class DenoisedGatherShader(_HitShader):
+    """One-bounce global illumination with few rays and a guided filter, as a hit shader: the hit frame, then
+    ``WorldQueries.hemisphere_radiance`` with ``samples`` rays per pixel, then the edge-avoiding filter of
+    include/ptrace_denoise.h on that mean ``E`` (``WorldQueries.denoised``, guided by the frame's own ``shape_index``, ``point`` and
+    ``normal``), then ``emitted + brdf_color * E`` with the colours of ``WorldQueries.materials``; ``background_color`` where
+    nothing is hit.  The filter sees ``E`` and not the final colour, so a checkered pigment stays sharp.  The frame must hold ONE
+    sample per pixel (``samples_per_side`` 0 or 1).
+
+    ``samples``, ``init_state``, ``init_seq``, ``max_depth`` and ``russian_roulette_limit`` are the gather's (its rays have
+    ``Ray.depth = 1``: the children of a camera ray's hit); ``params`` are the filter's (``passes``, ``sigma_point``,
+    ``normal_power_log2``, ``sigma_colour``, ``same_shape``).  ``filtered=False`` leaves the filter out: the noisy frame it replaces.
+    ``last_gather`` is the :class:`pytracer_amd.rays.GatheredRadiance` of the last frame.
+
+    ``__call__(ray)`` is the UNFILTERED value of one ray -- a filter has no meaning for a single record: ``emitted + brdf_color *
+    E`` with ``E`` the mean of ``samples`` one-ray ``PathRadianceShader`` walks from the hit, drawn from this shader's own ``pcg``."""
+
+    hit_channels = abi.HIT_ALL
+
+    def __init__(self, world, tracer=None, samples: int = 4, background_color: Color = BLACK, init_state: int = 42, init_seq: int = 54,
+                 max_depth: int = 10, russian_roulette_limit: int = 3, filtered: bool = True, pcg=None, **params):
+        super().__init__(world, background_color)
+        from ._denoise_lib import DEFAULTS
+        from .hostmodel import PCG
+
+        if int(samples) < 1:
+            raise ValueError(f"DenoisedGatherShader needs samples >= 1, not {samples}")
+        unknown = set(params) - (set(DEFAULTS) - {"wrap_x"})
+        if unknown:
+            raise TypeError(f"DenoisedGatherShader: unknown filter parameter(s) {sorted(unknown)}")
+        self.tracer, self.samples, self.filtered, self.params = tracer, int(samples), bool(filtered), dict(params)
+        self.init_state, self.init_seq = int(init_state), int(init_seq)
+        self.max_depth, self.russian_roulette_limit = int(max_depth), int(russian_roulette_limit)
+        self.pcg = pcg if pcg is not None else PCG()
+        self.last_gather = None
+
+    def shade_hits(self, frame) -> np.ndarray:
+        if self.tracer is None:
+            raise TypeError("DenoisedGatherShader.shade_hits needs the tracer whose device scene holds the world: DenoisedGatherShader(world, tracer, ...)")
+        index = np.asarray(frame.shape_index)
+        if index.ndim != 3 or index.shape[0] != 1:
+            raise ValueError(f"DenoisedGatherShader filters one record per pixel, not a frame of {index.shape}: build the tracer with samples_per_side=0 or 1")
+        q = self.tracer.world_queries(self.world)
+        gathered = q.hemisphere_radiance(frame, self.samples, self.init_state, None, 1, self.max_depth, self.russian_roulette_limit,
+                                         self.background_color, 1, "none", init_seq=self.init_seq)
+        self.last_gather = gathered
+        e = q.denoised(gathered, frame, **self.params)[None] if self.filtered else np.asarray(gathered.radiance)
+        mat = q.materials(frame)
+        lit = np.asarray(mat.emitted) + np.asarray(mat.brdf_color) * e
+        return np.where(np.asarray(mat.hit)[..., None], lit, self._background(frame))
+
+    def __call__(self, ray) -> Color:
+        if not callable(getattr(self.world, "ray_intersection", None)):
+            raise TypeError(f"{type(self.world).__name__} has no ray_intersection(ray): it is a parameter holder that cannot trace a ray.  "
+                            "Hand DenoisedGatherShader to GpuImageTracer.fire_all_rays (the device traces), or give it a pytracer World")
+        from .hits import HitRay
+        from .hostmodel import DiffuseBRDF, UniformPigment, Vec
+
+        record = self.world.ray_intersection(ray)
+        if record is None:
+            return self.background_color
+        material = getattr(record, "material", None) or self.world.shapes[record.shape_index].material
+        uv, wp, nrm, d = record.surface_point, record.world_point, record.normal, ray.dir
+        pc, em = pigment_color(material.brdf.pigment, uv), pigment_color(material.emitted_radiance, uv)
+        walk = PathRadianceShader(self.world, None, self.background_color, self.pcg, 1, self.max_depth, self.russian_roulette_limit)
+        white = DiffuseBRDF(UniformPigment(Color(1.0, 1.0, 1.0)))
+        r = g = b = 0.0
+        for _ in range(self.samples):
+            o, nd, tmin = scatter_ray(white, self.pcg, (d.x, d.y, d.z), (wp.x, wp.y, wp.z), (nrm.x, nrm.y, nrm.z))
+            c = walk._radiance(HitRay(Vec(*o), Vec(*nd), tmin, float("inf"), 1), 1)
+            r, g, b = r + c.r, g + c.g, b + c.b
+        k = 1.0 / self.samples
+        return Color(em.r + pc.r * (r * k), em.g + pc.g * (g * k), em.b + pc.b * (b * k))
 
 
 def scatter_ray(brdf, pcg, in_dir, point, normal):
