@@ -731,9 +731,94 @@ def denoise(width, height, samples, passes, sigma_point, normal_power_log2, sigm
     tracer.close()
 
 
+@click.command("temporal")
+@click.option("--width", type=int, default=640, help="Width of the frame")
+@click.option("--height", type=int, default=480, help="Height of the frame")
+@click.option("--frames", type=int, default=8, help="Frames to render; the last one is written")
+@click.option("--step-deg", type=float, default=1.0, help="The camera turns by this many degrees about z from one frame to the next")
+@click.option("--samples", type=int, default=4, help="Hemisphere rays per pixel and frame")
+@click.option("--max-history", type=int, default=32, help="Frames after which the running mean becomes an exponential average, 1 to 2^20")
+@click.option("--normal-min", type=float, default=0.9, help="Least cosine between this frame's normal and a history tap's, -1 to 1")
+@click.option("--point-tolerance", type=float, default=0.05, help="Largest distance of a history tap from the pixel's tangent plane (inf: off)")
+@click.option("--passes", type=int, default=4, help="Filter passes behind the accumulation, 1 to 10; 0: no filter")
+@click.option("--sigma-point", type=float, default=0.1, help="The filter's: distance from the tangent plane, per step, at which a tap's weight halves")
+@click.option("--max-depth", type=int, default=3, help="Maximum allowed ray depth of the gather's walks")
+@click.option("--init-state", type=int, default=45, help="Initial seed for the random number generator.")
+@click.option("--init-seq", type=int, default=54, help="Identifier of the first random sequence.")
+@click.option("--pfm-output", type=str, default="frame.pfm", help="Name of the PFM file to create")
+@click.option("--no-history-output", type=str, default=None, help="Name of a PFM file for the same last frame without accumulation (default: none)")
+@click.option("--declare-float", "-d", type=str, multiple=True, help="Declare a variable: --declare-float=VAR:VALUE")
+@click.option("--device", type=int, default=0, help="GPU to render on")
+@click.argument("input_scene_name", type=str, default="builtin:demo")
+def temporal(width, height, frames, step_deg, samples, max_history, normal_min, point_tolerance, passes, sigma_point, max_depth, init_state,
+             init_seq, pfm_output, no_history_output, declare_float, device, input_scene_name):
+    """The last of --frames frames of a camera that turns about z, each lit by one bounce of few rays whose mean is accumulated
+    over the frames: last frame's accumulated mean is reprojected onto this frame's hit points through last frame's camera,
+    checked against the hit records (shape, normal, point) and blended in on the device; then the edge-avoiding filter, then
+    emitted + brdf_color * E.  Writes a PFM."""
+    import math
+
+    try:
+        if width < 1 or height < 1:
+            raise UsageError("--width and --height must be at least 1")
+        if frames < 1:
+            raise UsageError("--frames must be at least 1")
+        if not math.isfinite(step_deg):
+            raise UsageError("--step-deg must be finite")
+        if samples < 1:
+            raise UsageError("--samples must be at least 1")
+        if not 1 <= max_history <= 2 ** 20:
+            raise UsageError("--max-history must be 1 to 2^20")
+        if not -1.0 <= normal_min <= 1.0:
+            raise UsageError("--normal-min must be -1 to 1")
+        if not point_tolerance > 0.0:
+            raise UsageError("--point-tolerance must be positive (or inf)")
+        if not 0 <= passes <= 10:
+            raise UsageError("--passes must be 0 to 10")
+        if not sigma_point > 0.0:
+            raise UsageError("--sigma-point must be positive (or inf)")
+        if max_depth < 0:
+            raise UsageError("--max-depth must not be negative")
+        world, camera, _ = _load_scene(input_scene_name, parse_float_overrides(declare_float), width, height)
+    except UsageError as e:
+        click.echo(f"pytracer_amd temporal: {e}", err=True)
+        sys.exit(2)
+    from . import _lib, prefer_device_kernargs
+    from .shaders import TemporalGatherShader
+
+    prefer_device_kernargs()
+    _lib.standalone()  # (torch-free, like `denoise`)
+    image = hm.HdrImage(width, height)
+    tracer = GpuImageTracer(image=image, camera=camera, samples_per_side=0, device=device)
+    shader = TemporalGatherShader(world, tracer, samples, init_state=init_state, init_seq=init_seq, max_depth=max_depth, filtered=passes > 0,
+                                  passes=max(passes, 1), sigma_point=sigma_point, max_history=max_history, normal_min=normal_min,
+                                  point_tolerance=point_tolerance)
+    wrote = []
+    started = perf_counter()
+    for f in range(frames):
+        tracer.camera = scenes.turned_camera(camera, step_deg * f)
+        if f == frames - 1 and no_history_output:
+            shader.accumulate = False
+            tracer.fire_all_rays(shader)
+            with open(no_history_output, "wb") as out:
+                image.write_pfm(out)
+            wrote.append(no_history_output)
+            shader.accumulate = True
+        tracer.fire_all_rays(shader)
+    wall = perf_counter() - started
+    with open(pfm_output, "wb") as out:
+        image.write_pfm(out)
+    wrote.append(pfm_output)
+    count = shader.accumulator.count
+    click.echo(f"{width}x{height} px, {len(world.shapes)} shape(s), {frames} frame(s) of {samples} ray(s) per pixel, {step_deg:g} degree(s) per frame, "
+               f"longest history {int(count.max())}, {wall:.3f} s: wrote {' and '.join(wrote)}")
+    tracer.close()
+
+
 cli.add_command(render)
 cli.add_command(lit)
 cli.add_command(denoise)
+cli.add_command(temporal)
 cli.add_command(hits)
 cli.add_command(rays)
 cli.add_command(radiance)

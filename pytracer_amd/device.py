@@ -965,6 +965,70 @@ class DeviceScene:
                                              buf.nbytes))
         return np.ascontiguousarray(buf.T).reshape(height, width, 3)
 
+    # -- accumulate queries (include/ptrace_temporal.h, libptrace_temporal.so): last frame's radiance on this frame's hits --------
+    def temporal(self, colour, shape_index, normal, point, prev_colour, prev_shape, prev_normal, prev_point, prev_count, prev_camera,
+                 width: int, height: int, device: bool = False, stream=None, out=None, out_count=None, **params):
+        """The accumulation of include/ptrace_temporal.h over a ``width x height`` frame: every hit point of this frame is projected
+        onto the screen of ``prev_camera`` (a camera object, ``(kind, invm12, screen_distance, aspect_ratio)`` or a
+        ``TemporalCamera``), the previous frame's colour is fetched there from up to four taps -- a tap is skipped without history
+        (``prev_count <= 0``), on another shape (``same_shape``), where the unit normals' cosine is below ``normal_min`` or the tap's
+        point lies more than ``point_tolerance`` from this pixel's tangent plane -- and blended with ``colour``: a running mean up to
+        ``max_history`` frames, an exponential average from there.  ``colour``, ``normal``, ``point`` (and the previous frame's):
+        ``[..., 3]`` with ``width * height`` records; ``shape_index``, ``prev_shape``, ``prev_count``: int32 ->
+        ``(out [height, width, 3] float64, count [height, width] int32)``, :func:`pytracer_amd.rays.temporal_host` in every bit.
+        No scene is read.  ``device=True``: the planes (``[3, m]`` fp64, int32) are in HBM, the one launch is enqueued on ``stream``
+        -> the two output ``DeviceBuffer`` s (``out`` and ``out_count``, or new ones); neither may overlap an input."""
+        from . import _temporal_lib, rays as rb
+
+        L, par, cam = _temporal_lib.lib(), _temporal_lib.params(**params), _temporal_lib.camera(prev_camera)
+        width, height = _temporal_lib._addon.c_int(width, "width"), _temporal_lib._addon.c_int(height, "height")
+        m = width * height
+        if device:
+            from .devmem import DeviceBuffer
+
+            handle = getattr(stream, "handle", stream)
+            if out is None:
+                out = DeviceBuffer((3, max(m, 1)), np.float64, self.device)
+            if out_count is None:
+                out_count = DeviceBuffer((max(m, 1),), np.int32, self.device)
+            ptr = self._plane_ptr
+            _temporal_lib.check(L.pt_rays_temporal_accumulate_device(
+                self.device, width, height, C.byref(par), C.byref(cam), ptr(colour, "colour"), ptr(shape_index, "shape_index"),
+                ptr(normal, "normal"), ptr(point, "point"), ptr(prev_colour, "prev_colour"), ptr(prev_shape, "prev_shape"),
+                ptr(prev_normal, "prev_normal"), ptr(prev_point, "prev_point"), ptr(prev_count, "prev_count"), ptr(out, "out"),
+                int(out.nbytes), ptr(out_count, "out_count"), int(out_count.nbytes), C.c_void_p(handle) if handle else None))
+            for buf in (out, out_count):
+                if hasattr(buf, "rendered_on"):
+                    buf.rendered_on(stream)
+            return out, out_count
+        if stream is not None or out is not None or out_count is not None:
+            raise ValueError("stream=, out= and out_count= go with device=True (host frames are staged and synchronous)")
+        ints = [np.ascontiguousarray(a, dtype=np.int32).reshape(-1) for a in (shape_index, prev_shape, prev_count)]
+        planes = [rb.planar(a, 3) for a in (colour, normal, point, prev_colour, prev_normal, prev_point)]
+        if any(a.shape[0] != m for a in ints) or any(p.shape[1] != m for p in planes):
+            raise ValueError(f"a {width} x {height} frame has {m} records, not {[a.shape[0] for a in ints]} shape indices and counts and "
+                             f"{[p.shape[1] for p in planes]} colours, normals and points")
+        buf, cnt = np.empty((3, m), dtype=np.float64), np.empty((m,), dtype=np.int32)
+        p = lambda a: a.ctypes.data_as(C.c_void_p)  # noqa: E731
+        _temporal_lib.check(L.pt_rays_temporal_accumulate(self.device, width, height, C.byref(par), C.byref(cam), p(planes[0]), p(ints[0]),
+                                                          p(planes[1]), p(planes[2]), p(planes[3]), p(ints[1]), p(planes[4]), p(planes[5]),
+                                                          p(ints[2]), p(buf), buf.nbytes, p(cnt), cnt.nbytes))
+        return np.ascontiguousarray(buf.T).reshape(height, width, 3), cnt.reshape(height, width)
+
+    def temporal_clear(self, count, m=None, stream=None):
+        """An empty history: the ``m`` int32 lengths of the device buffer ``count`` (default: all it holds) become 0 on ``stream``
+        (``pt_rays_temporal_clear_device``) -> ``count``."""
+        from . import _temporal_lib
+
+        handle = getattr(stream, "handle", stream)
+        m = self._device_count(count, m)
+        nbytes = int(count.nbytes) if hasattr(count, "nbytes") else 4 * m
+        _temporal_lib.check(_temporal_lib.lib().pt_rays_temporal_clear_device(self.device, m, self._plane_ptr(count, "count"), nbytes,
+                                                                              C.c_void_p(handle) if handle else None))
+        if hasattr(count, "rendered_on"):
+            count.rendered_on(stream)
+        return count
+
     def cull_probe(self, cam: abi.Camera, width: int, height: int, x0: int, x1: int, row0: int, row1: int,
                    pixel=None) -> np.ndarray:
         """Diagnostics: which shapes (by ``World.shapes`` index) the conservative cull of the primary rays through

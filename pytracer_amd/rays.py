@@ -46,6 +46,11 @@ records' ``shape``, ``point`` and ``normal`` (``DeviceScene.denoise``, ``WorldQu
 include/ptrace_denoise.h, libptrace_denoise.so).  :func:`denoise_host` is the numpy mirror that defines the bits;
 ``shaders.DenoisedGatherShader`` renders frames with it.
 
+Its eleventh -- the filter's companion, which trades rays for time: last frame's accumulated mean reprojected onto this frame's hit
+points through last frame's camera, checked against the records and blended with the new samples (``DeviceScene.temporal``,
+``WorldQueries.accumulated``, :class:`TemporalAccumulator`; include/ptrace_temporal.h, libptrace_temporal.so).
+:func:`temporal_host` is the numpy mirror that defines the bits; ``shaders.TemporalGatherShader`` renders sequences with it.
+
 Layout: planar.  A batch is ``[8, n]`` float64 -- origin xyz, direction xyz, tmin, tmax, the fields of ``Ray`` (ray.py:29-50);
 a result is one buffer, the int32 shape plane first (padded to 8 bytes), then the selected fp64 planes of ``n`` values each.
 """
@@ -898,6 +903,102 @@ def denoise_host(colour, shape, normal, point, width: int, height: int, passes: 
     return cur
 
 
+def temporal_project_host(prev_camera, points, width: int, height: int):
+    """Steps 2 to 5 of include/ptrace_temporal.h, operation for operation: where ``points`` (``[..., 3]``) were on the screen of
+    ``prev_camera`` (anything ``_temporal_lib.camera`` takes), in pixels of a ``width x height`` frame -> ``(fx, fy, ok)``;
+    ``ok`` is False where there is no history (behind the camera, off the screen, NaN) and ``fx``, ``fy`` mean nothing there."""
+    from . import _temporal_lib
+
+    cam = _temporal_lib.camera(prev_camera)
+    if cam.kind not in (abi.CAMERA_ORTHOGONAL, abi.CAMERA_PERSPECTIVE):
+        raise ValueError(f"unknown camera kind {cam.kind}")
+    m, d, a = [float(x) for x in cam.invm], float(cam.screen_distance), float(cam.aspect_ratio)
+    p = np.asarray(points, dtype=np.float64)
+    px, py, pz = p[..., 0], p[..., 1], p[..., 2]
+    with np.errstate(all="ignore"):
+        qx = ((m[0] * px + m[1] * py) + m[2] * pz) + m[3]
+        qy = ((m[4] * px + m[5] * py) + m[6] * pz) + m[7]
+        qz = ((m[8] * px + m[9] * py) + m[10] * pz) + m[11]
+        if cam.kind == abi.CAMERA_PERSPECTIVE:
+            tn = qx + d
+            s = d / tn
+            u = (1.0 - (qy * s) / a) * 0.5
+            v = (1.0 + qz * s) * 0.5
+        else:
+            tn = qx + 1.0
+            u = (1.0 - qy / a) * 0.5
+            v = (1.0 + qz) * 0.5
+        fx = u * float(int(width)) - 0.5
+        fy = (1.0 - v) * float(int(height)) - 0.5
+        ok = (tn > 0.0) & (fx > -1.0) & (fx < float(int(width))) & (fy > -1.0) & (fy < float(int(height)))
+    return fx, fy, ok
+
+
+def temporal_host(colour, shape, normal, point, prev_colour, prev_shape, prev_normal, prev_point, prev_count, prev_camera, width: int,
+                  height: int, max_history: int = 32, same_shape: bool = True, normal_min: float = 0.9, point_tolerance: float = 0.05,
+                  _tap_order=(0, 1, 2, 3)):
+    """The numpy mirror of the accumulate query (include/ptrace_temporal.h), operation for operation: vectorised per tap over the
+    whole frame, the four taps in the header's order, every sum in that order.  The planes: ``width * height`` records in row-major
+    order (any leading shape), the previous frame's like the current one's plus ``prev_count``; ``prev_camera``: anything
+    ``_temporal_lib.camera`` takes -> ``(out [height, width, 3] float64, count [height, width] int32)``.  Refuses what the library
+    refuses, with a ``ValueError``.  (``_tap_order`` is for the test that the order of the sums reaches the bits.)"""
+    W, H, max_history = int(width), int(height), int(max_history)
+    normal_min, point_tolerance = float(normal_min), float(point_tolerance)
+    if W < 0 or H < 0 or W * H > MAX_RAYS:
+        raise ValueError(f"a frame of {W} x {H} records")
+    if not 1 <= max_history <= 2 ** 20:
+        raise ValueError(f"max_history={max_history}: 1 to 2^20")
+    if not -1.0 <= normal_min <= 1.0 or not point_tolerance > 0.0:
+        raise ValueError(f"normal_min={normal_min} (a cosine, -1 to 1), point_tolerance={point_tolerance} (positive, or inf)")
+    cur = np.array(colour, dtype=np.float64).reshape(H, W, 3)
+    sh = np.asarray(shape, dtype=np.int32).reshape(H, W)
+    nrm = np.asarray(normal, dtype=np.float64).reshape(H, W, 3)
+    pnt = np.asarray(point, dtype=np.float64).reshape(H, W, 3)
+    pcol = np.asarray(prev_colour, dtype=np.float64).reshape(H, W, 3)
+    psh = np.asarray(prev_shape, dtype=np.int32).reshape(H, W)
+    pnrm = np.asarray(prev_normal, dtype=np.float64).reshape(H, W, 3)
+    ppnt = np.asarray(prev_point, dtype=np.float64).reshape(H, W, 3)
+    pcnt = np.asarray(prev_count, dtype=np.int32).reshape(H, W)
+    fx, fy, ok = temporal_project_host(prev_camera, pnt, W, H)
+    if W * H == 0:
+        return cur, np.zeros((H, W), dtype=np.int32)
+    hit = sh >= 0
+    ok = ok & hit
+    with np.errstate(all="ignore"):
+        unit = nrm / np.sqrt(nrm[..., 0] * nrm[..., 0] + nrm[..., 1] * nrm[..., 1] + nrm[..., 2] * nrm[..., 2])[..., None]
+        punit = pnrm / np.sqrt(pnrm[..., 0] * pnrm[..., 0] + pnrm[..., 1] * pnrm[..., 1] + pnrm[..., 2] * pnrm[..., 2])[..., None]
+        fx, fy = np.where(ok, fx, 0.0), np.where(ok, fy, 0.0)
+        x0f, y0f = np.floor(fx), np.floor(fy)
+        ax, ay = fx - x0f, fy - y0f
+        x0, y0 = x0f.astype(np.int64), y0f.astype(np.int64)
+        bx, by = (1.0 - ax, ax), (1.0 - ay, ay)
+        hs, ws = np.zeros((H, W, 3)), np.zeros((H, W))
+        nmax, some = np.zeros((H, W), dtype=np.int64), np.zeros((H, W), dtype=bool)
+        for t in _tap_order:
+            x, y = x0 + (t & 1), y0 + (t >> 1)
+            take = ok & (x >= 0) & (x < W) & (y >= 0) & (y < H)
+            at = (np.clip(y, 0, H - 1), np.clip(x, 0, W - 1))
+            sq, nq, nu, pq, cq = psh[at], pcnt[at].astype(np.int64), punit[at], ppnt[at], pcol[at]
+            take = take & (nq > 0) & (sq >= 0)
+            if same_shape:
+                take = take & (sq == sh)
+            c = unit[..., 0] * nu[..., 0] + unit[..., 1] * nu[..., 1] + unit[..., 2] * nu[..., 2]
+            d = pq - pnt
+            dz = unit[..., 0] * d[..., 0] + unit[..., 1] * d[..., 1] + unit[..., 2] * d[..., 2]
+            b = bx[t & 1] * by[t >> 1]
+            take = take & (c >= normal_min) & (np.abs(dz) <= point_tolerance) & (b > 0.0)
+            hs = np.where(take[..., None], hs + b[..., None] * cq, hs)
+            ws = np.where(take, ws + b, ws)
+            nmax = np.where(take, np.maximum(nmax, nq), nmax)
+            some = some | take
+        n = np.minimum(nmax + 1, max_history)
+        alpha = 1.0 / n.astype(np.float64)
+        hist = hs / ws[..., None]
+        out = np.where(some[..., None], hist + (cur - hist) * alpha[..., None], cur)
+    count = np.where(hit, np.where(some, n, 1), 0).astype(np.int32)
+    return out, count
+
+
 def texel_centres(width: int, height: int, window=None) -> np.ndarray:
     """``[h, w, 2]``: ``(u, v)`` at the centres of the texels of ``window`` (``(col0, row0, w, h)``; ``None``: all) of a
     ``width x height`` map, as the bake forms them: ``(col + 0.5) * (1.0 / width)``, ``(row + 0.5) * (1.0 / height)``."""
@@ -951,6 +1052,37 @@ def planar(values, components: int) -> np.ndarray:
     if a.ndim < 1 or a.shape[-1] != components:
         raise ValueError(f"expected [..., {components}], not {a.shape}")
     return np.ascontiguousarray(np.moveaxis(a, -1, 0)).reshape(components, -1)
+
+
+def _one_record_frame(values, hits, taker: str):
+    """``values`` (a :class:`GatheredRadiance`, a :class:`BakedMap` or an array) and ``hits`` (a hit frame, a :class:`RayHits` or
+    ``(points, normals, shape)``) as the frame ``taker`` reads: ONE record per pixel -> ``(values [H, W, 3] or [m, 3], shape
+    indices [m], normals, points, width, height)``."""
+    if isinstance(hits, (tuple, list)):
+        if len(hits) != 3:
+            raise ValueError("hits as arrays are (points, normals, shape)")
+        points, normals, index = hits
+    else:
+        points, normals, index = hits.point, hits.normal, hits.shape_index
+    index = np.asarray(index)
+    v = np.asarray(values.radiance if hasattr(values, "radiance") else values, dtype=np.float64)
+    for what, a, lead in (("values", v, v.ndim - 1), ("hits", index, index.ndim)):
+        if lead == 3 and a.shape[0] != 1:
+            raise ValueError(f"{what} hold {a.shape[0]} samples per pixel: {taker} takes one record per pixel (average the samples first)")
+    if v.ndim == 4:
+        v = v[0]
+    if index.ndim == 3:
+        index = index[0]
+    if v.ndim == 3 and v.shape[-1] == 3:
+        height, width = v.shape[:2]
+    elif index.ndim == 2 and v.size == index.size * 3:
+        height, width = index.shape
+    else:
+        raise ValueError(f"no frame in values {v.shape} and shape indices {index.shape}: pass the values as [H, W, 3]")
+    if index.size not in (1, height * width):
+        raise ValueError(f"{index.size} shape indices for a frame of {height} x {width}")
+    index = np.broadcast_to(index.reshape(-1) if index.size > 1 else index.reshape(()), (height * width,))
+    return v, index, normals, points, width, height
 
 
 class WorldQueries:
@@ -1105,30 +1237,7 @@ class WorldQueries:
         row-major order, or ``(points, normals, shape)`` arrays (``shape``: one index or one per record).  More samples per pixel
         are a ``ValueError``: average them first.  ``params``: ``passes``, ``sigma_point``, ``normal_power_log2``,
         ``sigma_colour``, ``same_shape``, ``wrap_x`` -> ``[H, W, 3]``."""
-        if isinstance(hits, (tuple, list)):
-            if len(hits) != 3:
-                raise ValueError("hits as arrays are (points, normals, shape)")
-            points, normals, index = hits
-        else:
-            points, normals, index = hits.point, hits.normal, hits.shape_index
-        index = np.asarray(index)
-        v = np.asarray(values.radiance if hasattr(values, "radiance") else values, dtype=np.float64)
-        for what, a, lead in (("values", v, v.ndim - 1), ("hits", index, index.ndim)):
-            if lead == 3 and a.shape[0] != 1:
-                raise ValueError(f"{what} hold {a.shape[0]} samples per pixel: the filter takes one record per pixel (average the samples first)")
-        if v.ndim == 4:
-            v = v[0]
-        if index.ndim == 3:
-            index = index[0]
-        if v.ndim == 3 and v.shape[-1] == 3:
-            height, width = v.shape[:2]
-        elif index.ndim == 2 and v.size == index.size * 3:
-            height, width = index.shape
-        else:
-            raise ValueError(f"no frame in values {v.shape} and shape indices {index.shape}: pass the values as [H, W, 3]")
-        if index.size not in (1, height * width):
-            raise ValueError(f"{index.size} shape indices for a frame of {height} x {width}")
-        index = np.broadcast_to(index.reshape(-1) if index.size > 1 else index.reshape(()), (height * width,))
+        v, index, normals, points, width, height = _one_record_frame(values, hits, "the filter")
         return self.scene.denoise(v.reshape(-1, 3), index, np.asarray(normals).reshape(-1, 3), np.asarray(points).reshape(-1, 3), width, height, **params)
 
     def denoised_light_map(self, shape: int, width: int, height: int, samples: int, wrap_u=None, **kw) -> np.ndarray:
@@ -1145,6 +1254,25 @@ class WorldQueries:
         if wrap_u is None:
             wrap_u = int(self.scene.flat.kind[int(shape)]) == abi.SHAPE_SPHERE
         return self.denoised(baked, (points, normals, int(shape)), wrap_x=bool(wrap_u), **fpar)
+
+    def accumulated(self, values, hits, prev: "TemporalHistory", prev_camera, **params) -> "TemporalHistory":
+        """``values`` blended with the previous frame's accumulated values where this frame's ``hits`` were seen before -- on the
+        device (``DeviceScene.temporal``), :func:`temporal_host` in every bit.  ``values`` and ``hits``: as :meth:`denoised` takes
+        them, ONE record per pixel, the DEMODULATED signal; ``prev``: the :class:`TemporalHistory` of the previous frame (what this
+        method returned for it, or ``TemporalHistory.empty`` at the start); ``prev_camera``: the camera that frame was seen from.
+        ``params``: ``max_history``, ``same_shape``, ``normal_min``, ``point_tolerance`` -> the :class:`TemporalHistory` of this
+        frame: ``colour`` ``[H, W, 3]`` is the accumulated frame, ``count`` ``[H, W]`` the history lengths."""
+        v, index, normals, points, width, height = _one_record_frame(values, hits, "the accumulation")
+        index = np.ascontiguousarray(index, dtype=np.int32).reshape(height, width)
+        normals = np.asarray(normals, dtype=np.float64).reshape(height, width, 3)
+        points = np.asarray(points, dtype=np.float64).reshape(height, width, 3)
+        if np.asarray(prev.count).shape != (height, width):
+            raise ValueError(f"a history of {np.asarray(prev.count).shape} for a frame of {height} x {width}")
+        out, count = self.scene.temporal(v.reshape(-1, 3), index.reshape(-1), normals.reshape(-1, 3), points.reshape(-1, 3),
+                                         np.asarray(prev.colour).reshape(-1, 3), np.asarray(prev.shape_index).reshape(-1),
+                                         np.asarray(prev.normal).reshape(-1, 3), np.asarray(prev.point).reshape(-1, 3),
+                                         np.asarray(prev.count).reshape(-1), prev_camera, width, height, **params)
+        return TemporalHistory(out, index, normals, points, count)
 
     def radiance_probes(self, points, samples, init_state: int = 42, init_seq: int = 54, seqs=None, active=None, num_of_rays: int = 1,
                         max_depth: int = 10, russian_roulette_limit: int = 3, background=(0.0, 0.0, 0.0), depth: int = 1,
@@ -1189,3 +1317,116 @@ class WorldQueries:
         if not np.all(np.asarray(mat.brdf_kind) == abi.BRDF_DIFFUSE):
             raise ValueError(f"shape {shape} has no DiffuseBRDF: what a mirror sends out depends on where it is seen from, a map cannot hold it")
         return np.asarray(mat.emitted) + np.asarray(mat.brdf_color) * self.probe_map(shape, width, height, probes, probe, side)
+
+
+# ---- accumulation over frames (include/ptrace_temporal.h) ---------------------------------------------------------------------------
+class TemporalHistory:
+    """What one frame hands to the next: the accumulated ``colour`` ``[H, W, 3]``, the guides it was made for (``shape_index``
+    ``[H, W]`` int32, ``normal`` and ``point`` ``[H, W, 3]``) and the history lengths ``count`` ``[H, W]`` int32."""
+
+    def __init__(self, colour, shape_index, normal, point, count):
+        self.colour, self.shape_index, self.normal, self.point, self.count = colour, shape_index, normal, point, count
+
+    @classmethod
+    def empty(cls, width: int, height: int) -> "TemporalHistory":
+        """The history before the first frame: every length 0, so nothing of it is ever read."""
+        h, w = int(height), int(width)
+        return cls(np.zeros((h, w, 3)), np.full((h, w), -1, dtype=np.int32), np.zeros((h, w, 3)), np.zeros((h, w, 3)),
+                   np.zeros((h, w), dtype=np.int32))
+
+
+class DeviceGuides:
+    """The guides of a frame that lies in HBM: ``shape_index`` (``m`` int32), ``normal`` and ``point`` (``[3, m]`` fp64) as
+    ``DeviceBuffer`` s, device tensors or raw addresses.  ``keep``: whatever owns the memory (held, not used)."""
+
+    def __init__(self, shape_index, normal, point, keep=None):
+        self.shape_index, self.normal, self.point, self.keep = shape_index, normal, point, keep
+
+    @classmethod
+    def of_hit_buffer(cls, buffer, params, channels=abi.HIT_ALL) -> "DeviceGuides":
+        """The planes of a hit-record frame of ONE sample per pixel that ``DeviceScene.render_hits_into`` wrote into ``buffer``."""
+        channels = abi.hit_channels(channels)
+        if not (channels & abi.HIT_POINT and channels & abi.HIT_NORMAL):
+            raise ValueError("the hit frame must carry the point and normal channels")
+        base = int(buffer.data_ptr()) if callable(getattr(buffer, "data_ptr", None)) else int(buffer)
+        return cls(base, base + abi.hits_plane_offset(params, channels, abi.HIT_NORMAL, 0),
+                   base + abi.hits_plane_offset(params, channels, abi.HIT_POINT, 0), keep=buffer)
+
+    def addresses(self) -> tuple:
+        return tuple(int(x.data_ptr()) if callable(getattr(x, "data_ptr", None)) else int(x) for x in (self.shape_index, self.normal, self.point))
+
+
+class TemporalAccumulator:
+    """The accumulate query over a sequence of frames: ``update(values, hits, camera)`` blends this frame's demodulated ``values``
+    with what the previous ``update`` left, reprojected through the previous camera (``WorldQueries.accumulated``), and keeps the
+    result, this frame's guides, the history lengths and the camera for the next call.  ONE sample per pixel, like
+    ``WorldQueries.denoised``.  It starts from a history of zero lengths, so the first frame takes the path of every other.
+    ``params``: ``max_history``, ``same_shape``, ``normal_min``, ``point_tolerance``.
+
+    ``device=False``: ``values`` and ``hits`` as ``WorldQueries.accumulated`` takes them; ``update`` returns the accumulated ``E``
+    ``[H, W, 3]`` and ``count`` holds the lengths ``[H, W]``; the history is kept on the host and staged by every call.
+
+    ``device=True``: everything stays in HBM.  ``values``: the ``[3, m]`` fp64 planes of a device gather (a ``DeviceBuffer`` or a
+    raw address), ``hits``: a :class:`DeviceGuides`, with ``width=`` and ``height=``; the one launch is enqueued on ``stream``.
+    Two colour and two count buffers are ping-ponged: ``update`` returns the colour ``DeviceBuffer`` it wrote (``[3, m]``; valid
+    until the next but one ``update``), ``count`` is the count buffer.  The previous frame's guides are read where the caller left
+    them: alternate two hit buffers."""
+
+    def __init__(self, queries, device: bool = False, stream=None, **params):
+        from ._temporal_lib import DEFAULTS
+
+        unknown = set(params) - set(DEFAULTS)
+        if unknown:
+            raise TypeError(f"TemporalAccumulator: unknown accumulation parameter(s) {sorted(unknown)}")
+        if stream is not None and not device:
+            raise ValueError("stream= goes with device=True (host frames are staged and synchronous)")
+        self.queries, self.device, self.stream, self.params = queries, bool(device), stream, dict(params)
+        self._buffers, self._m = None, -1
+        self.reset()
+
+    def reset(self) -> None:
+        """Forget the history: the next ``update`` starts a sequence."""
+        self._prev, self._camera, self.count, self.frames = None, None, None, 0
+
+    def update(self, values, hits, camera, width=None, height=None):
+        from . import _temporal_lib
+
+        cam = _temporal_lib.camera(camera)
+        cam = _temporal_lib.TemporalCamera.from_buffer_copy(cam)  # (the caller's camera may move on)
+        if not self.device:
+            if width is not None or height is not None:
+                raise ValueError("width= and height= go with device=True (a host frame brings its own)")
+            prev, prev_camera = self._prev, self._camera
+            if prev is None:
+                _, _, _, _, w, h = _one_record_frame(values, hits, "the accumulation")
+                prev, prev_camera = TemporalHistory.empty(w, h), cam
+            new = self.queries.accumulated(values, hits, prev, prev_camera, **self.params)
+            self._prev, self._camera, self.count = new, cam, new.count
+            self.frames += 1
+            return new.colour
+        from .devmem import DeviceBuffer
+
+        if width is None or height is None:
+            raise ValueError("device=True needs width= and height=: planes in HBM do not say what frame they are")
+        if not isinstance(hits, DeviceGuides):
+            raise TypeError(f"device=True takes hits as a DeviceGuides, not {type(hits).__name__}")
+        scene = self.queries.scene
+        m = int(width) * int(height)
+        if self._buffers is None or self._m != m:
+            self._buffers = [(DeviceBuffer((3, max(m, 1)), np.float64, scene.device), DeviceBuffer((max(m, 1),), np.int32, scene.device))
+                             for _ in range(2)]
+            self._m = m
+            self.reset()
+        out, out_count = self._buffers[self.frames & 1]
+        prev_colour, prev_count = self._buffers[(self.frames & 1) ^ 1]
+        prev, prev_camera = self._prev, self._camera
+        if prev is None:  # (lengths of 0: neither the other colour buffer nor the guides handed in as the previous ones are read)
+            scene.temporal_clear(prev_count, m, self.stream)
+            prev, prev_camera = hits, cam
+        elif set(prev.addresses()) & set(hits.addresses()):
+            raise ValueError("this frame's guides lie where the previous frame's did: alternate two hit buffers")
+        scene.temporal(values, hits.shape_index, hits.normal, hits.point, prev_colour, prev.shape_index, prev.normal, prev.point, prev_count,
+                       prev_camera, width, height, device=True, stream=self.stream, out=out, out_count=out_count, **self.params)
+        self._prev, self._camera, self.count = hits, cam, out_count
+        self.frames += 1
+        return out

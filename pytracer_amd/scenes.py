@@ -79,6 +79,17 @@ def demo_world(clock: float = 150.0) -> Tuple[World, PerspectiveCamera]:
     return world, camera
 
 
+def turned_camera(camera, degrees: float):
+    """A copy of ``camera`` turned by ``degrees`` about the world's z axis (``rotation_z(degrees) * camera.transformation``): the
+    camera of the next frame of a sequence."""
+    import copy
+
+    base = camera.transformation
+    out = copy.copy(camera)
+    out.transformation = rotation_z(float(degrees)) * Transformation([list(r) for r in base.m], [list(r) for r in base.invm])
+    return out
+
+
 def baked_world(world, maps) -> World:
     """``world`` with the outgoing radiance of some of its shapes baked in: ``maps`` is ``{shape_index: [H, W, 3] array}``
     (``WorldQueries.outgoing_map``), and every listed shape comes back with the material ``DiffuseBRDF(UniformPigment(BLACK))``,

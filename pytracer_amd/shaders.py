@@ -24,6 +24,9 @@ query (``WorldQueries.path_radiance``), which walks every sample's tree depth-fi
 
 :class:`DenoisedGatherShader` trades rays for a guided filter: a few hemisphere rays per hit (``WorldQueries.hemisphere_radiance``),
 the edge-avoiding filter of include/ptrace_denoise.h on that mean (``WorldQueries.denoised``), then the material.
+
+:class:`TemporalGatherShader` trades rays for time as well: between the gather and the filter, last frame's accumulated mean is
+reprojected onto this frame's hits and blended in (``rays.TemporalAccumulator``; include/ptrace_temporal.h).
 """
 from __future__ import annotations
 
@@ -539,6 +542,65 @@ class DenoisedGatherShader(_HitShader):
             r, g, b = r + c.r, g + c.g, b + c.b
         k = 1.0 / self.samples
         return Color(em.r + pc.r * (r * k), em.g + pc.g * (g * k), em.b + pc.b * (b * k))
+
+
+class TemporalGatherShader(DenoisedGatherShader):
+    """:class:`DenoisedGatherShader` over a sequence of frames: the hit frame, then ``WorldQueries.hemisphere_radiance`` with
+    ``samples`` rays per pixel, then the accumulation of include/ptrace_temporal.h on that mean ``E``
+    (``rays.TemporalAccumulator.update``: last frame's accumulated ``E`` reprojected through last frame's camera and blended in), then
+    the filter (when ``filtered``), then ``emitted + brdf_color * E``.  The camera is the tracer's at the time of the call: move it
+    between two ``fire_all_rays``.  Frame ``f`` (``frame_no``, counted from 0) draws fresh generators: its gather starts at stream
+    ``init_seq + f * m * samples``, ``m`` the frame's pixels, so no two frames share a stream.
+
+    ``params`` are told apart by name -- the filter's ``passes``, ``sigma_point``, ``normal_power_log2``, ``sigma_colour``,
+    ``same_shape``; the accumulation's ``max_history``, ``normal_min``, ``point_tolerance`` and ``history_same_shape`` (its
+    ``same_shape``) -- and anything else is a ``TypeError``.  ``accumulate=False`` renders the frame ``frame_no`` WOULD be without
+    its history, and leaves history and ``frame_no`` as they are: the frame to compare with.  ``reset()`` starts a new sequence.
+    ``accumulator.count`` holds the history lengths of the last frame."""
+
+    def __init__(self, world, tracer=None, samples: int = 4, background_color: Color = BLACK, init_state: int = 42, init_seq: int = 54,
+                 max_depth: int = 10, russian_roulette_limit: int = 3, filtered: bool = True, pcg=None, accumulate: bool = True, **params):
+        from ._denoise_lib import DEFAULTS as FILTER
+        from ._temporal_lib import DEFAULTS as HISTORY
+
+        mine = {"history_same_shape" if k == "same_shape" else k for k in HISTORY}
+        unknown = set(params) - (set(FILTER) - {"wrap_x"}) - mine
+        if unknown:
+            raise TypeError(f"TemporalGatherShader: unknown filter or accumulation parameter(s) {sorted(unknown)}")
+        history = {("same_shape" if k == "history_same_shape" else k): params.pop(k) for k in sorted(mine) if k in params}
+        super().__init__(world, tracer, samples, background_color, init_state, init_seq, max_depth, russian_roulette_limit, filtered, pcg, **params)
+        self.history_params, self.accumulate = history, bool(accumulate)
+        self.accumulator, self.frame_no = None, 0
+
+    def reset(self) -> None:
+        self.frame_no = 0
+        if self.accumulator is not None:
+            self.accumulator.reset()
+
+    def shade_hits(self, frame) -> np.ndarray:
+        from .rays import TemporalAccumulator
+
+        if self.tracer is None:
+            raise TypeError("TemporalGatherShader.shade_hits needs the tracer whose device scene holds the world: TemporalGatherShader(world, tracer, ...)")
+        index = np.asarray(frame.shape_index)
+        if index.ndim != 3 or index.shape[0] != 1:
+            raise ValueError(f"TemporalGatherShader keeps one record per pixel, not a frame of {index.shape}: build the tracer with samples_per_side=0 or 1")
+        q = self.tracer.world_queries(self.world)
+        seq = self.init_seq + self.frame_no * (index.shape[1] * index.shape[2]) * self.samples
+        gathered = q.hemisphere_radiance(frame, self.samples, self.init_state, None, 1, self.max_depth, self.russian_roulette_limit,
+                                         self.background_color, 1, "none", init_seq=seq)
+        self.last_gather = gathered
+        e = np.asarray(gathered.radiance)[0]
+        if self.accumulate:
+            if self.accumulator is None or self.accumulator.queries.scene is not q.scene:
+                self.accumulator = TemporalAccumulator(q, **self.history_params)
+            e = self.accumulator.update(e, frame, self.tracer.camera)
+            self.frame_no += 1
+        if self.filtered:
+            e = q.denoised(e, frame, **self.params)
+        mat = q.materials(frame)
+        lit = np.asarray(mat.emitted) + np.asarray(mat.brdf_color) * e[None]
+        return np.where(np.asarray(mat.hit)[..., None], lit, self._background(frame))
 
 
 def scatter_ray(brdf, pcg, in_dir, point, normal):
