@@ -19,6 +19,7 @@ after libptrace.so, in the order of ``ADDONS`` (csrc/ptrace_NAME.hip, include/pt
 * lit: hit records shaded from a lattice of those probes (corners, blend, evaluation and the material in one kernel)
 * denoise: an edge-avoiding a-trous filter for the noisy frames and maps of the steps above, guided by their hit records
 * temporal: last frame's demodulated radiance reprojected onto this frame's hit records and blended with the new samples
+* variance: luminance moments for that accumulation, the per-pixel variance they give, and an a-trous filter guided by it
 """
 from __future__ import annotations
 
@@ -74,9 +75,15 @@ TEMPORAL_ADDONS = {name: ([f"ptrace_{name}.hip"], os.path.join(HERE, f"libptrace
 TEMPORAL_TARGETS = tuple((FLAGS[:-1] + [f"-cuid={cuid}"], lib, sources) for sources, lib, cuid in TEMPORAL_ADDONS.values())
 ((TEMPORAL_FLAGS, TEMPORAL_LIB, TEMPORAL_SOURCES),) = TEMPORAL_TARGETS
 FRAME_TARGETS = WALK_TARGETS + TEMPORAL_TARGETS
+# The add-ons since interface 1.10.  FRAME_TARGETS keeps the value it had at interface 1.9 (tests/test_temporal_host.py pins it:
+# eleven rows, the temporal library's last), so what came later is listed here and GUIDED_TARGETS is what build() and needs_build() walk.
+VARIANCE_ADDONS = {name: ([f"ptrace_{name}.hip"], os.path.join(HERE, f"libptrace_{name}.so"), f"libptrace_{name}") for name in ("variance",)}
+VARIANCE_TARGETS = tuple((FLAGS[:-1] + [f"-cuid={cuid}"], lib, sources) for sources, lib, cuid in VARIANCE_ADDONS.values())
+((VARIANCE_FLAGS, VARIANCE_LIB, VARIANCE_SOURCES),) = VARIANCE_TARGETS
+GUIDED_TARGETS = FRAME_TARGETS + VARIANCE_TARGETS
 # every file the translation units include: all of csrc/ (tests/test_host.py checks this list against the #include lines)
 DEPS = sorted(f for f in os.listdir(CSRC) if f.endswith((".hip", ".h"))) + [
-    os.path.join("..", "..", "include", h) for h in ["ptrace.h", "ptrace_debug.h"] + [f"ptrace_{name}.h" for name in list(ADDONS) + list(LATER_ADDONS) + list(NEWER_ADDONS) + list(NEWEST_ADDONS) + list(DENOISE_ADDONS) + list(TEMPORAL_ADDONS)]]
+    os.path.join("..", "..", "include", h) for h in ["ptrace.h", "ptrace_debug.h"] + [f"ptrace_{name}.h" for name in list(ADDONS) + list(LATER_ADDONS) + list(NEWER_ADDONS) + list(NEWEST_ADDONS) + list(DENOISE_ADDONS) + list(TEMPORAL_ADDONS) + list(VARIANCE_ADDONS)]]
 
 
 def code_hash(lib: str = LIB) -> str:
@@ -115,17 +122,17 @@ def _hipcc() -> str:
 
 
 def needs_build() -> bool:
-    libs = [lib for _, lib, _ in FRAME_TARGETS]
+    libs = [lib for _, lib, _ in GUIDED_TARGETS]
     if not all(os.path.exists(lib) for lib in libs):
         return True
-    t = min(os.path.getmtime(lib) for lib in libs)  # (one list of files for all eleven: they share the headers)
+    t = min(os.path.getmtime(lib) for lib in libs)  # (one list of files for all twelve: they share the headers)
     return any(os.path.getmtime(os.path.join(CSRC, d)) > t for d in DEPS)
 
 
 def build(force: bool = False, verbose: bool = False) -> str:
     if not force and not needs_build():
         return LIB
-    for flags, lib, sources in FRAME_TARGETS:
+    for flags, lib, sources in GUIDED_TARGETS:
         cmd = [_hipcc()] + flags + ["-o", lib] + [os.path.join(CSRC, s) for s in sources]
         if verbose:
             print(" ".join(cmd), file=sys.stderr)

@@ -815,10 +815,107 @@ def temporal(width, height, frames, step_deg, samples, max_history, normal_min, 
     tracer.close()
 
 
+@click.command("variance")
+@click.option("--width", type=int, default=640, help="Width of the frame")
+@click.option("--height", type=int, default=480, help="Height of the frame")
+@click.option("--frames", type=int, default=8, help="Frames to render; the last one is written")
+@click.option("--step-deg", type=float, default=1.0, help="The camera turns by this many degrees about z from one frame to the next")
+@click.option("--samples", type=int, default=4, help="Hemisphere rays per pixel and frame")
+@click.option("--max-history", type=int, default=32, help="Frames after which the running mean becomes an exponential average, 1 to 2^20")
+@click.option("--min-history", type=int, default=4, help="History length below which the variance is estimated over a 7x7 window, 1 to 2^20")
+@click.option("--normal-min", type=float, default=0.9, help="Least cosine between this frame's normal and a history or window tap's, -1 to 1")
+@click.option("--point-tolerance", type=float, default=0.05, help="Largest distance of such a tap from the pixel's tangent plane (inf: off)")
+@click.option("--passes", type=int, default=4, help="Filter passes behind the accumulation, 1 to 10; 0: no filter")
+@click.option("--sigma-point", type=float, default=0.1, help="The filter's: distance from the tangent plane, per step, at which a tap's weight halves")
+@click.option("--sigma-luminance", type=float, default=1.0,
+              help="The filter's: luminance difference, in standard deviations of the pixel, at which a tap's weight halves (inf: off)")
+@click.option("--epsilon", type=float, default=1e-10, help="The filter's: what is added to the scaled variance, positive and finite")
+@click.option("--max-depth", type=int, default=3, help="Maximum allowed ray depth of the gather's walks")
+@click.option("--init-state", type=int, default=45, help="Initial seed for the random number generator.")
+@click.option("--init-seq", type=int, default=54, help="Identifier of the first random sequence.")
+@click.option("--pfm-output", type=str, default="frame.pfm", help="Name of the PFM file to create")
+@click.option("--variance-output", type=str, default=None, help="Name of a PFM file (grey) of the last frame's variance before the filter (default: none)")
+@click.option("--declare-float", "-d", type=str, multiple=True, help="Declare a variable: --declare-float=VAR:VALUE")
+@click.option("--device", type=int, default=0, help="GPU to render on")
+@click.argument("input_scene_name", type=str, default="builtin:demo")
+def variance(width, height, frames, step_deg, samples, max_history, min_history, normal_min, point_tolerance, passes, sigma_point, sigma_luminance,
+             epsilon, max_depth, init_state, init_seq, pfm_output, variance_output, declare_float, device, input_scene_name):
+    """The last of --frames frames of a camera that turns about z, each lit by one bounce of few rays whose mean AND whose luminance
+    moments are accumulated over the frames; from the moments a variance per pixel, and then an edge-avoiding filter whose
+    luminance weight is scaled by that variance, so that it blurs a pixel as hard as the pixel is still noisy; then emitted +
+    brdf_color * E.  Writes a PFM."""
+    import math
+
+    try:
+        if width < 1 or height < 1:
+            raise UsageError("--width and --height must be at least 1")
+        if frames < 1:
+            raise UsageError("--frames must be at least 1")
+        if not math.isfinite(step_deg):
+            raise UsageError("--step-deg must be finite")
+        if samples < 1:
+            raise UsageError("--samples must be at least 1")
+        if not 1 <= max_history <= 2 ** 20:
+            raise UsageError("--max-history must be 1 to 2^20")
+        if not 1 <= min_history <= 2 ** 20:
+            raise UsageError("--min-history must be 1 to 2^20")
+        if not -1.0 <= normal_min <= 1.0:
+            raise UsageError("--normal-min must be -1 to 1")
+        if not point_tolerance > 0.0:
+            raise UsageError("--point-tolerance must be positive (or inf)")
+        if not 0 <= passes <= 10:
+            raise UsageError("--passes must be 0 to 10")
+        if not sigma_point > 0.0:
+            raise UsageError("--sigma-point must be positive (or inf)")
+        if not sigma_luminance > 0.0:
+            raise UsageError("--sigma-luminance must be positive (or inf)")
+        if not (epsilon > 0.0 and math.isfinite(epsilon)):
+            raise UsageError("--epsilon must be positive and finite")
+        if max_depth < 0:
+            raise UsageError("--max-depth must not be negative")
+        world, camera, _ = _load_scene(input_scene_name, parse_float_overrides(declare_float), width, height)
+    except UsageError as e:
+        click.echo(f"pytracer_amd variance: {e}", err=True)
+        sys.exit(2)
+    import numpy as np
+
+    from . import _lib, prefer_device_kernargs
+    from .shaders import VarianceGuidedGatherShader
+
+    prefer_device_kernargs()
+    _lib.standalone()  # (torch-free, like `temporal`)
+    image = hm.HdrImage(width, height)
+    tracer = GpuImageTracer(image=image, camera=camera, samples_per_side=0, device=device)
+    shader = VarianceGuidedGatherShader(world, tracer, samples, init_state=init_state, init_seq=init_seq, max_depth=max_depth, filtered=passes > 0,
+                                        passes=max(passes, 1), sigma_point=sigma_point, sigma_luminance=sigma_luminance, epsilon=epsilon,
+                                        max_history=max_history, min_history=min_history, normal_min=normal_min, point_tolerance=point_tolerance)
+    wrote = []
+    started = perf_counter()
+    for f in range(frames):
+        tracer.camera = scenes.turned_camera(camera, step_deg * f)
+        tracer.fire_all_rays(shader)
+    wall = perf_counter() - started
+    with open(pfm_output, "wb") as out:
+        image.write_pfm(out)
+    wrote.append(pfm_output)
+    last = np.asarray(shader.last_variance, dtype=np.float64)
+    if variance_output:
+        grey = hm.HdrImage(width, height)
+        grey.set_array(np.repeat(last.reshape(height, width, 1), 3, axis=-1))
+        with open(variance_output, "wb") as out:
+            grey.write_pfm(out)
+        wrote.append(variance_output)
+    count = shader.accumulator.count
+    click.echo(f"{width}x{height} px, {len(world.shapes)} shape(s), {frames} frame(s) of {samples} ray(s) per pixel, {step_deg:g} degree(s) per frame, "
+               f"longest history {int(count.max())}, mean variance {float(last.mean()):.3e}, {wall:.3f} s: wrote {' and '.join(wrote)}")
+    tracer.close()
+
+
 cli.add_command(render)
 cli.add_command(lit)
 cli.add_command(denoise)
 cli.add_command(temporal)
+cli.add_command(variance)
 cli.add_command(hits)
 cli.add_command(rays)
 cli.add_command(radiance)

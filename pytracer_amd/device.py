@@ -1029,6 +1029,145 @@ class DeviceScene:
             count.rendered_on(stream)
         return count
 
+    # -- variance queries (include/ptrace_variance.h, libptrace_variance.so): moments, a per-pixel variance and a filter guided by it --
+    @staticmethod
+    def _variance_frame(width, height):
+        from . import _addon
+
+        width, height = _addon.c_int(width, "width"), _addon.c_int(height, "height")
+        return width, height, width * height
+
+    def variance_moments(self, colour, shape_index, width: int, height: int, device: bool = False, stream=None, out=None):
+        """The luminance moments of include/ptrace_variance.h of a ``width x height`` frame: per record ``(l, l * l, 0)`` with ``l``
+        the luminosity of ``colour`` (``[..., 3]``), zeros where ``shape_index`` is negative -> ``[height, width, 3]`` float64,
+        :func:`pytracer_amd.rays.luminance_moments_host` in every bit: a frame for :meth:`temporal`, as its ``colour``.
+        ``device=True``: the planes (``[3, m]`` fp64, int32) are in HBM, the launch is enqueued on ``stream`` -> the output
+        ``DeviceBuffer`` (``out``, or a new one)."""
+        from . import _variance_lib, rays as rb
+
+        L = _variance_lib.lib()
+        width, height, m = self._variance_frame(width, height)
+        if device:
+            from .devmem import DeviceBuffer
+
+            handle = getattr(stream, "handle", stream)
+            if out is None:
+                out = DeviceBuffer((3, max(m, 1)), np.float64, self.device)
+            ptr = self._plane_ptr
+            _variance_lib.check(L.pt_rays_variance_moments_device(self.device, width, height, ptr(colour, "colour"), ptr(shape_index, "shape_index"),
+                                                                  ptr(out, "out"), int(out.nbytes), C.c_void_p(handle) if handle else None))
+            if hasattr(out, "rendered_on"):
+                out.rendered_on(stream)
+            return out
+        if stream is not None or out is not None:
+            raise ValueError("stream= and out= go with device=True (host frames are staged and synchronous)")
+        shape = np.ascontiguousarray(shape_index, dtype=np.int32).reshape(-1)
+        col = rb.planar(colour, 3)
+        if shape.shape[0] != m or col.shape[1] != m:
+            raise ValueError(f"a {width} x {height} frame has {m} records, not {shape.shape[0]} shape indices and {col.shape[1]} colours")
+        buf = np.empty((3, m), dtype=np.float64)
+        p = lambda a: a.ctypes.data_as(C.c_void_p)  # noqa: E731
+        _variance_lib.check(L.pt_rays_variance_moments(self.device, width, height, p(col), p(shape), p(buf), buf.nbytes))
+        return np.ascontiguousarray(buf.T).reshape(height, width, 3)
+
+    def variance_estimate(self, moments, count, shape_index, normal, point, width: int, height: int, device: bool = False, stream=None, out=None,
+                          **params):
+        """The variance estimate of include/ptrace_variance.h over a ``width x height`` frame, from the accumulated ``moments``
+        (``[..., 3]``: first and second luminance moment, and a third channel that is not read) and the history lengths ``count``:
+        ``max(mu2 - mu1^2, 0) / n`` where ``n >= min_history``, else the same from the means of the moments over the accepted taps
+        of a 7x7 window (``same_shape``, ``wrap_x``, ``normal_min``, ``point_tolerance``) -> ``[height, width]`` float64,
+        :func:`pytracer_amd.rays.variance_estimate_host` in every bit.  ``device=True``: the planes are in HBM, the launch is
+        enqueued on ``stream`` -> the output ``DeviceBuffer`` of ``m`` fp64 (``out``, or a new one)."""
+        from . import _variance_lib, rays as rb
+
+        L, par = _variance_lib.lib(), _variance_lib.params(**params)
+        width, height, m = self._variance_frame(width, height)
+        if device:
+            from .devmem import DeviceBuffer
+
+            handle = getattr(stream, "handle", stream)
+            if out is None:
+                out = DeviceBuffer((max(m, 1),), np.float64, self.device)
+            ptr = self._plane_ptr
+            _variance_lib.check(L.pt_rays_variance_estimate_device(self.device, width, height, C.byref(par), ptr(moments, "moments"),
+                                                                   ptr(count, "count"), ptr(shape_index, "shape_index"), ptr(normal, "normal"),
+                                                                   ptr(point, "point"), ptr(out, "out"), int(out.nbytes),
+                                                                   C.c_void_p(handle) if handle else None))
+            if hasattr(out, "rendered_on"):
+                out.rendered_on(stream)
+            return out
+        if stream is not None or out is not None:
+            raise ValueError("stream= and out= go with device=True (host frames are staged and synchronous)")
+        ints = [np.ascontiguousarray(a, dtype=np.int32).reshape(-1) for a in (count, shape_index)]
+        planes = [rb.planar(a, 3) for a in (moments, normal, point)]
+        if any(a.shape[0] != m for a in ints) or any(p.shape[1] != m for p in planes):
+            raise ValueError(f"a {width} x {height} frame has {m} records, not {[a.shape[0] for a in ints]} counts and shape indices and "
+                             f"{[p.shape[1] for p in planes]} moments, normals and points")
+        buf = np.empty((m,), dtype=np.float64)
+        p = lambda a: a.ctypes.data_as(C.c_void_p)  # noqa: E731
+        _variance_lib.check(L.pt_rays_variance_estimate(self.device, width, height, C.byref(par), p(planes[0]), p(ints[0]), p(ints[1]), p(planes[1]),
+                                                        p(planes[2]), p(buf), buf.nbytes))
+        return buf.reshape(height, width)
+
+    def variance_workspace_bytes(self, width: int, height: int, **params) -> int:
+        """Bytes of the workspace :meth:`variance_filter` needs on the device for a ``width x height`` frame (``params``: its own)."""
+        from . import _variance_lib
+
+        L, par = _variance_lib.lib(), _variance_lib.params(**params)
+        width, height, m = self._variance_frame(width, height)
+        need = int(L.pt_rays_variance_workspace_bytes(width, height, C.byref(par)))
+        if need == 0 and m != 0:
+            raise _lib.PtraceError(-1, _variance_lib.last_error())
+        return need
+
+    def variance_filter(self, colour, variance, shape_index, normal, point, width: int, height: int, device: bool = False, stream=None, out=None,
+                        out_variance=None, workspace=None, **params):
+        """The variance-guided a-trous filter of include/ptrace_variance.h over a ``width x height`` frame: the stencil, the passes
+        and the geometric weights of :meth:`denoise`, with its colour weight replaced by ``1 / (1 + dl^2 / (sigma_luminance^2 * g +
+        epsilon))`` -- ``dl`` the luminance difference, ``g`` the 3x3-prefiltered ``variance`` at the pixel -- and the variance
+        filtered along with the colour (weights squared) -> ``(colour [height, width, 3], variance [height, width])`` float64,
+        :func:`pytracer_amd.rays.variance_filter_host` in every bit.  No scene is read.  ``device=True``: the planes (``[3, m]`` and
+        ``[m]`` fp64, int32) are in HBM, the passes are enqueued on ``stream`` -> the two output ``DeviceBuffer`` s (``out`` and
+        ``out_variance``, or new ones); ``workspace``: a ``DeviceBuffer`` of :meth:`variance_workspace_bytes` (or a new one)."""
+        from . import _variance_lib, rays as rb
+
+        L, par = _variance_lib.lib(), _variance_lib.params(**params)
+        width, height, m = self._variance_frame(width, height)
+        if device:
+            from .devmem import DeviceBuffer
+
+            handle = getattr(stream, "handle", stream)
+            if out is None:
+                out = DeviceBuffer((3, max(m, 1)), np.float64, self.device)
+            if out_variance is None:
+                out_variance = DeviceBuffer((max(m, 1),), np.float64, self.device)
+            if workspace is None:
+                workspace = DeviceBuffer((max(self.variance_workspace_bytes(width, height, **params), 8),), np.uint8, self.device)
+            ptr = self._plane_ptr
+            _variance_lib.check(L.pt_rays_variance_filter_device(
+                self.device, width, height, C.byref(par), ptr(colour, "colour"), ptr(variance, "variance"), ptr(normal, "normal"),
+                ptr(point, "point"), ptr(shape_index, "shape_index"), ptr(out, "out"), int(out.nbytes), ptr(out_variance, "out_variance"),
+                int(out_variance.nbytes), ptr(workspace, "workspace"), int(workspace.nbytes), C.c_void_p(handle) if handle else None))
+            for buf in (out, out_variance, workspace):
+                if hasattr(buf, "rendered_on"):
+                    buf.rendered_on(stream)
+            if hasattr(out, "rendered_on"):
+                out._variance_workspace = workspace  # in flight on `stream` as long as the output is: freed with it
+            return out, out_variance
+        if stream is not None or out is not None or out_variance is not None or workspace is not None:
+            raise ValueError("stream=, out=, out_variance= and workspace= go with device=True (host frames are staged and synchronous)")
+        shape = np.ascontiguousarray(shape_index, dtype=np.int32).reshape(-1)
+        var = np.ascontiguousarray(variance, dtype=np.float64).reshape(-1)
+        planes = [rb.planar(colour, 3), rb.planar(normal, 3), rb.planar(point, 3)]
+        if shape.shape[0] != m or var.shape[0] != m or any(p.shape[1] != m for p in planes):
+            raise ValueError(f"a {width} x {height} frame has {m} records, not {shape.shape[0]} shape indices, {var.shape[0]} variances and "
+                             f"{[p.shape[1] for p in planes]} colours, normals and points")
+        buf, vbuf = np.empty((3, m), dtype=np.float64), np.empty((m,), dtype=np.float64)
+        p = lambda a: a.ctypes.data_as(C.c_void_p)  # noqa: E731
+        _variance_lib.check(L.pt_rays_variance_filter(self.device, width, height, C.byref(par), p(planes[0]), p(var), p(planes[1]), p(planes[2]),
+                                                      p(shape), p(buf), buf.nbytes, p(vbuf), vbuf.nbytes))
+        return np.ascontiguousarray(buf.T).reshape(height, width, 3), vbuf.reshape(height, width)
+
     def cull_probe(self, cam: abi.Camera, width: int, height: int, x0: int, x1: int, row0: int, row1: int,
                    pixel=None) -> np.ndarray:
         """Diagnostics: which shapes (by ``World.shapes`` index) the conservative cull of the primary rays through

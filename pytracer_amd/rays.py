@@ -999,6 +999,194 @@ def temporal_host(colour, shape, normal, point, prev_colour, prev_shape, prev_no
     return out, count
 
 
+# ---- the mirrors of the variance queries (include/ptrace_variance.h) -------------------------------------------------------------------
+def _luminance(c) -> np.ndarray:
+    """``lum(c)`` of include/ptrace_variance.h over ``[..., 3]``: ``Color.luminosity`` written with comparisons."""
+    c0, c1, c2 = c[..., 0], c[..., 1], c[..., 2]
+    mx = np.where(c1 > c0, c1, c0)
+    mx = np.where(c2 > mx, c2, mx)
+    mn = np.where(c1 < c0, c1, c0)
+    mn = np.where(c2 < mn, c2, mn)
+    with np.errstate(all="ignore"):
+        return (mx + mn) / 2.0
+
+
+def _variance_params(W, H, passes=4, sigma_point=0.1, normal_power_log2=5, sigma_luminance=1.0, epsilon=1e-10, min_history=4, normal_min=0.9,
+                     point_tolerance=0.05, same_shape=True, wrap_x=False):
+    """The checks of ``pt_variance_params`` and of the frame, as ``ValueError`` s -> the values as Python numbers."""
+    passes, e, min_history = int(passes), int(normal_power_log2), int(min_history)
+    sigma_point, sigma_luminance, epsilon = float(sigma_point), float(sigma_luminance), float(epsilon)
+    normal_min, point_tolerance = float(normal_min), float(point_tolerance)
+    if W < 0 or H < 0 or W * H > MAX_RAYS:
+        raise ValueError(f"a frame of {W} x {H} records")
+    if not 1 <= passes <= 10 or not 0 <= e <= 10:
+        raise ValueError(f"passes={passes} (1 to 10), normal_power_log2={e} (0 to 10)")
+    if not 1 <= min_history <= 2 ** 20:
+        raise ValueError(f"min_history={min_history}: 1 to 2^20")
+    if not sigma_point > 0.0 or not sigma_luminance > 0.0:
+        raise ValueError(f"sigma_point={sigma_point}, sigma_luminance={sigma_luminance}: a sigma is positive (or inf)")
+    if not (epsilon > 0.0 and epsilon < float("inf")):
+        raise ValueError(f"epsilon={epsilon}: positive and finite")
+    if not -1.0 <= normal_min <= 1.0 or not point_tolerance > 0.0:
+        raise ValueError(f"normal_min={normal_min} (a cosine, -1 to 1), point_tolerance={point_tolerance} (positive, or inf)")
+    return passes, e, min_history, sigma_point, sigma_luminance, epsilon, normal_min, point_tolerance, bool(same_shape), bool(wrap_x)
+
+
+def luminance_moments_host(colour, shape, width: int, height: int) -> np.ndarray:
+    """The numpy mirror of the moments query (include/ptrace_variance.h): ``(l, l * l, 0)`` per record, zeros where ``shape`` is
+    negative -> ``[height, width, 3]``."""
+    W, H = int(width), int(height)
+    if W < 0 or H < 0 or W * H > MAX_RAYS:
+        raise ValueError(f"a frame of {W} x {H} records")
+    col = np.asarray(colour, dtype=np.float64).reshape(H, W, 3)
+    hit = np.asarray(shape, dtype=np.int32).reshape(H, W) >= 0
+    with np.errstate(all="ignore"):
+        l = _luminance(col)
+        l2 = l * l
+    out = np.zeros((H, W, 3))
+    out[..., 0], out[..., 1] = np.where(hit, l, 0.0), np.where(hit, l2, 0.0)
+    return out
+
+
+def _wrapped_columns(cols, offset, W, wrap_x):
+    """Columns ``cols + offset`` of a frame ``W`` wide -> (the columns, clipped or wrapped into the frame; which of them exist)."""
+    qx = cols + offset
+    if wrap_x:
+        return qx % W, np.ones(qx.shape, dtype=bool)
+    return np.clip(qx, 0, W - 1), (qx >= 0) & (qx < W)
+
+
+def variance_estimate_host(moments, count, shape, normal, point, width: int, height: int, **params) -> np.ndarray:
+    """The numpy mirror of the estimate query (include/ptrace_variance.h), operation for operation: vectorised per tap over the whole
+    frame, the 49 taps in the header's order.  ``moments``: ``[..., 3]`` (the third channel is not read), ``count`` and ``shape``:
+    int32, ``normal`` and ``point``: ``[..., 3]``, all ``width * height`` records; ``params``: ``min_history``, ``normal_min``,
+    ``point_tolerance``, ``same_shape``, ``wrap_x`` (the filter's are checked and not used) -> ``[height, width]``."""
+    W, H = int(width), int(height)
+    _, _, min_history, _, _, _, normal_min, point_tolerance, same_shape, wrap_x = _variance_params(W, H, **params)
+    mom = np.asarray(moments, dtype=np.float64).reshape(H, W, 3)
+    cnt = np.asarray(count, dtype=np.int32).reshape(H, W)
+    sh = np.asarray(shape, dtype=np.int32).reshape(H, W)
+    nrm = np.asarray(normal, dtype=np.float64).reshape(H, W, 3)
+    pnt = np.asarray(point, dtype=np.float64).reshape(H, W, 3)
+    if W * H == 0:
+        return np.zeros((H, W))
+    rows, cols = np.arange(H), np.arange(W)
+    mu1, mu2 = mom[..., 0], mom[..., 1]
+    with np.errstate(all="ignore"):
+        unit = nrm / np.sqrt(nrm[..., 0] * nrm[..., 0] + nrm[..., 1] * nrm[..., 1] + nrm[..., 2] * nrm[..., 2])[..., None]
+        s1, s2, k = np.zeros((H, W)), np.zeros((H, W)), np.zeros((H, W))
+        for dy in range(-3, 4):
+            qy = rows + dy
+            in_y = (qy >= 0) & (qy < H)
+            qy = np.clip(qy, 0, H - 1)
+            for dx in range(-3, 4):
+                qx, in_x = _wrapped_columns(cols, dx, W, wrap_x)
+                at = np.ix_(qy, qx)
+                take = in_y[:, None] & in_x[None, :]
+                if dx != 0 or dy != 0:
+                    sq, nq, pq = sh[at], unit[at], pnt[at]
+                    take = take & (sq >= 0) & (cnt[at] >= 1)
+                    if same_shape:
+                        take = take & (sq == sh)
+                    c = unit[..., 0] * nq[..., 0] + unit[..., 1] * nq[..., 1] + unit[..., 2] * nq[..., 2]
+                    d = pq - pnt
+                    dz = unit[..., 0] * d[..., 0] + unit[..., 1] * d[..., 1] + unit[..., 2] * d[..., 2]
+                    take = take & (c >= normal_min) & (np.abs(dz) <= point_tolerance)
+                s1 = np.where(take, s1 + mu1[at], s1)
+                s2 = np.where(take, s2 + mu2[at], s2)
+                k = np.where(take, k + 1.0, k)
+        mean = s1 / k
+        spatial = s2 / k - mean * mean
+        v = np.where(cnt >= min_history, mu2 - mu1 * mu1, spatial)
+        v = np.where(v > 0.0, v, 0.0)
+        v = v / cnt.astype(np.float64)
+    return np.where((sh < 0) | (cnt < 1), 0.0, v)
+
+
+def variance_filter_host(colour, variance, shape, normal, point, width: int, height: int, **params):
+    """The numpy mirror of the filter query (include/ptrace_variance.h), operation for operation: vectorised per tap over the whole
+    frame, the taps in the header's order (``dy`` outer, ``dx`` inner), every sum in that order.  ``colour``, ``normal``, ``point``:
+    ``width * height`` records of 3 in row-major order (any leading shape), ``variance``: as many fp64, ``shape``: as many int32,
+    negative = copied; ``params``: ``passes``, ``sigma_point``, ``normal_power_log2``, ``sigma_luminance``, ``epsilon``,
+    ``same_shape``, ``wrap_x`` (the estimate's are checked and not used) -> ``(colour [height, width, 3], variance [height, width])``.
+    Refuses what the library refuses, with a ``ValueError``."""
+    W, H = int(width), int(height)
+    passes, e, _, sigma_point, sigma_luminance, epsilon, _, _, same_shape, wrap_x = _variance_params(W, H, **params)
+    cur = np.array(colour, dtype=np.float64).reshape(H, W, 3)
+    var = np.array(variance, dtype=np.float64).reshape(H, W)
+    sh = np.asarray(shape, dtype=np.int32).reshape(H, W)
+    nrm = np.asarray(normal, dtype=np.float64).reshape(H, W, 3)
+    pnt = np.asarray(point, dtype=np.float64).reshape(H, W, 3)
+    if W * H == 0:
+        return cur, var
+    active = sh >= 0
+    rows, cols = np.arange(H), np.arange(W)
+    sl2 = sigma_luminance * sigma_luminance
+    sl_inf = sl2 == float("inf")
+    with np.errstate(all="ignore"):
+        unit = nrm / np.sqrt(nrm[..., 0] * nrm[..., 0] + nrm[..., 1] * nrm[..., 1] + nrm[..., 2] * nrm[..., 2])[..., None]
+        for i in range(passes):
+            s = 2 ** i
+            sps = sigma_point * float(s)
+            # the prefiltered variance: 3x3 at step 1, the centre a tap like the others
+            gs, gw = np.zeros((H, W)), np.zeros((H, W))
+            for dy in range(-1, 2):
+                qy = rows + dy
+                in_y = (qy >= 0) & (qy < H)
+                qy = np.clip(qy, 0, H - 1)
+                for dx in range(-1, 2):
+                    kw = (0.5 if dx == 0 else 0.25) * (0.5 if dy == 0 else 0.25)
+                    qx, in_x = _wrapped_columns(cols, dx, W, wrap_x)
+                    at = np.ix_(qy, qx)
+                    sq, vq = sh[at], var[at]
+                    take = in_y[:, None] & in_x[None, :] & (sq >= 0) & (vq >= 0.0)
+                    if same_shape:
+                        take = take & (sq == sh)
+                    gs = np.where(take, gs + kw * vq, gs)
+                    gw = np.where(take, gw + kw, gw)
+            g = np.where(gw > 0.0, gs / gw, 0.0)
+            den = sl2 * g + epsilon
+            lum = _luminance(cur)
+            total, wsum, vs = np.zeros((H, W, 3)), np.zeros((H, W)), np.zeros((H, W))
+            for dy in range(-2, 3):
+                qy = rows + s * dy
+                in_y = (qy >= 0) & (qy < H)
+                qy = np.clip(qy, 0, H - 1)
+                for dx in range(-2, 3):
+                    k = DENOISE_KERNEL[dx + 2] * DENOISE_KERNEL[dy + 2]
+                    if dx == 0 and dy == 0:
+                        total, wsum, vs = total + k * cur, wsum + k, vs + (k * k) * var
+                        continue
+                    qx, in_x = _wrapped_columns(cols, s * dx, W, wrap_x)
+                    at = np.ix_(qy, qx)
+                    sq, nq, pq, cq, lq, vq = sh[at], unit[at], pnt[at], cur[at], lum[at], var[at]
+                    take = in_y[:, None] & in_x[None, :] & (sq >= 0)
+                    if same_shape:
+                        take = take & (sq == sh)
+                    c = unit[..., 0] * nq[..., 0] + unit[..., 1] * nq[..., 1] + unit[..., 2] * nq[..., 2]
+                    c = np.where(c > 0.0, c, 0.0)
+                    for _ in range(e):
+                        c = c * c
+                    d = pq - pnt
+                    dz = unit[..., 0] * d[..., 0] + unit[..., 1] * d[..., 1] + unit[..., 2] * d[..., 2]
+                    t = dz / sps
+                    wp = 1.0 / (1.0 + t * t)
+                    dl = lq - lum
+                    dl2 = dl * dl
+                    if sl_inf:
+                        wl = np.where(dl2 < float("inf"), 1.0, float("nan"))
+                    else:
+                        wl = 1.0 / (1.0 + dl2 / den)
+                    w = ((k * c) * wp) * wl
+                    take = take & (w > 0.0)
+                    total = np.where(take[..., None], total + w[..., None] * cq, total)
+                    wsum = np.where(take, wsum + w, wsum)
+                    vs = np.where(take, vs + (w * w) * vq, vs)
+            cur = np.where(active[..., None], total / wsum[..., None], cur)
+            var = np.where(active, vs / (wsum * wsum), var)
+    return cur, var
+
+
 def texel_centres(width: int, height: int, window=None) -> np.ndarray:
     """``[h, w, 2]``: ``(u, v)`` at the centres of the texels of ``window`` (``(col0, row0, w, h)``; ``None``: all) of a
     ``width x height`` map, as the bake forms them: ``(col + 0.5) * (1.0 / width)``, ``(row + 0.5) * (1.0 / height)``."""
@@ -1274,6 +1462,29 @@ class WorldQueries:
                                          np.asarray(prev.count).reshape(-1), prev_camera, width, height, **params)
         return TemporalHistory(out, index, normals, points, count)
 
+    def variance_filtered(self, values, hits, variance=None, count=None, **params):
+        """``values`` filtered by the variance-guided a-trous filter of include/ptrace_variance.h, guided by ``hits`` -- on the
+        device (``DeviceScene.variance_filter``), :func:`variance_filter_host` in every bit.  ``values`` and ``hits``: as
+        :meth:`denoised` takes them, ONE record per pixel, the DEMODULATED signal; ``variance``: ``[H, W]``, the variance of
+        ``values`` per pixel (what :class:`VarianceAccumulator` returns).  ``variance=None`` is the single-frame route, for one
+        gather or one light map: the luminance moments of this frame, ``count`` 1 everywhere (so the estimate is the spatial one
+        over a 7x7 window; ``count=``: other history lengths ``[H, W]``), then the filter.  ``params``: those of
+        ``_variance_lib.DEFAULTS`` -> ``(colour [H, W, 3], variance [H, W])``."""
+        v, index, normals, points, width, height = _one_record_frame(values, hits, "the filter")
+        index = np.ascontiguousarray(index, dtype=np.int32).reshape(-1)
+        normals, points = np.asarray(normals).reshape(-1, 3), np.asarray(points).reshape(-1, 3)
+        if variance is None:
+            moments = self.scene.variance_moments(v.reshape(-1, 3), index, width, height)
+            count = np.ones(height * width, dtype=np.int32) if count is None else np.asarray(count, dtype=np.int32).reshape(-1)
+            if count.shape[0] != height * width:
+                raise ValueError(f"{count.shape[0]} history lengths for a frame of {height} x {width}")
+            variance = self.scene.variance_estimate(moments.reshape(-1, 3), count, index, normals, points, width, height, **params)
+        elif count is not None:
+            raise ValueError("count= goes with variance=None (a variance handed in is used as it is)")
+        if np.asarray(variance).size != height * width:
+            raise ValueError(f"a variance of {np.asarray(variance).shape} for a frame of {height} x {width}")
+        return self.scene.variance_filter(v.reshape(-1, 3), np.asarray(variance).reshape(-1), index, normals, points, width, height, **params)
+
     def radiance_probes(self, points, samples, init_state: int = 42, init_seq: int = 54, seqs=None, active=None, num_of_rays: int = 1,
                         max_depth: int = 10, russian_roulette_limit: int = 3, background=(0.0, 0.0, 0.0), depth: int = 1,
                         channels="all") -> ProbeSet:
@@ -1430,3 +1641,81 @@ class TemporalAccumulator:
         self._prev, self._camera, self.count = hits, cam, out_count
         self.frames += 1
         return out
+
+
+class VarianceAccumulator:
+    """The accumulate query twice over a sequence of frames -- once for the demodulated ``values``, once for their luminance moments
+    (``DeviceScene.variance_moments``; the same guides, cameras and parameters, so the same taps and the same ``count``) -- and the
+    variance estimate of include/ptrace_variance.h from the accumulated moments: ``update(values, hits, camera)`` returns
+    ``(accumulated E, variance)``, the two inputs of ``WorldQueries.variance_filtered`` / ``DeviceScene.variance_filter``.  It owns
+    two :class:`TemporalAccumulator` s (``colour`` and ``moments``).  ``params``: ``max_history`` (the accumulation's),
+    ``min_history`` (the estimate's), and ``same_shape``, ``normal_min``, ``point_tolerance``, which both read.
+
+    ``device=False``: ``values`` and ``hits`` as ``WorldQueries.accumulated`` takes them; ``update`` returns ``E`` ``[H, W, 3]`` and
+    the variance ``[H, W]``; ``count`` holds the lengths ``[H, W]``.
+
+    ``device=True``: everything stays in HBM, with the buffer lifetimes of :class:`TemporalAccumulator`: ``values`` are ``[3, m]``
+    fp64 planes, ``hits`` a :class:`DeviceGuides` (alternate two hit buffers), with ``width=`` and ``height=``; the four launches
+    are enqueued on ``stream``; ``update`` returns the colour ``DeviceBuffer`` (``[3, m]``) and the variance ``DeviceBuffer``
+    (``[m]``), both valid until the next but one ``update``; ``count`` is the count buffer."""
+
+    HISTORY_KEYS = ("max_history", "same_shape", "normal_min", "point_tolerance")
+    ESTIMATE_KEYS = ("min_history", "same_shape", "normal_min", "point_tolerance")
+
+    def __init__(self, queries, device: bool = False, stream=None, **params):
+        unknown = set(params) - set(self.HISTORY_KEYS) - set(self.ESTIMATE_KEYS)
+        if unknown:
+            raise TypeError(f"VarianceAccumulator: unknown accumulation or estimate parameter(s) {sorted(unknown)}")
+        self.history_params = {k: v for k, v in params.items() if k in self.HISTORY_KEYS}
+        self.estimate_params = {k: v for k, v in params.items() if k in self.ESTIMATE_KEYS}
+        self.queries, self.device, self.stream = queries, bool(device), stream
+        self.colour = TemporalAccumulator(queries, device, stream, **self.history_params)
+        self.moments = TemporalAccumulator(queries, device, stream, **self.history_params)
+        self._scratch, self._m = None, -1
+        self.count = None
+
+    @property
+    def frames(self) -> int:
+        return self.colour.frames
+
+    def reset(self) -> None:
+        """Forget the history: the next ``update`` starts a sequence."""
+        self.colour.reset()
+        self.moments.reset()
+        self.count = None
+
+    def update(self, values, hits, camera, width=None, height=None):
+        scene = self.queries.scene
+        if not self.device:
+            if width is not None or height is not None:
+                raise ValueError("width= and height= go with device=True (a host frame brings its own)")
+            v, index, normals, points, w, h = _one_record_frame(values, hits, "the accumulation")
+            index = np.ascontiguousarray(index, dtype=np.int32).reshape(-1)
+            moments = scene.variance_moments(v.reshape(-1, 3), index, w, h)
+            guides = (np.asarray(points).reshape(h, w, 3), np.asarray(normals).reshape(h, w, 3), index.reshape(h, w))
+            colour = self.colour.update(v.reshape(h, w, 3), guides, camera)
+            mu = self.moments.update(moments, guides, camera)
+            self.count = self.colour.count
+            variance = scene.variance_estimate(np.asarray(mu).reshape(-1, 3), np.asarray(self.count).reshape(-1), index, guides[1].reshape(-1, 3),
+                                               guides[0].reshape(-1, 3), w, h, **self.estimate_params)
+            return colour, variance
+        from .devmem import DeviceBuffer
+
+        if width is None or height is None:
+            raise ValueError("device=True needs width= and height=: planes in HBM do not say what frame they are")
+        if not isinstance(hits, DeviceGuides):
+            raise TypeError(f"device=True takes hits as a DeviceGuides, not {type(hits).__name__}")
+        m = int(width) * int(height)
+        if self._scratch is None or self._m != m:
+            self._scratch = (DeviceBuffer((3, max(m, 1)), np.float64, scene.device),
+                             [DeviceBuffer((max(m, 1),), np.float64, scene.device) for _ in range(2)])
+            self._m = m
+        frame, variances = self._scratch
+        out_variance = variances[self.colour.frames & 1]
+        scene.variance_moments(values, hits.shape_index, width, height, device=True, stream=self.stream, out=frame)
+        colour = self.colour.update(values, hits, camera, width, height)
+        mu = self.moments.update(frame, hits, camera, width, height)
+        self.count = self.colour.count
+        scene.variance_estimate(mu, self.count, hits.shape_index, hits.normal, hits.point, width, height, device=True, stream=self.stream,
+                                out=out_variance, **self.estimate_params)
+        return colour, out_variance

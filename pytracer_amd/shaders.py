@@ -603,6 +603,69 @@ class TemporalGatherShader(DenoisedGatherShader):
         return np.where(np.asarray(mat.hit)[..., None], lit, self._background(frame))
 
 
+class VarianceGuidedGatherShader(DenoisedGatherShader):
+    """:class:`TemporalGatherShader` with a filter that knows how noisy every pixel still is: the hit frame, then
+    ``WorldQueries.hemisphere_radiance`` with ``samples`` rays per pixel, then ``rays.VarianceAccumulator.update`` (the accumulation of
+    that mean ``E`` AND of its luminance moments, and the variance of include/ptrace_variance.h from them), then the variance-guided
+    filter (``WorldQueries.variance_filtered``, when ``filtered``), then ``emitted + brdf_color * E``.  The camera, the frame numbers
+    and the generators are :class:`TemporalGatherShader`'s.
+
+    ``params`` are told apart by name -- the filter's ``passes``, ``sigma_point``, ``normal_power_log2``, ``sigma_luminance``,
+    ``epsilon``, ``same_shape``; the accumulation's and the estimate's ``max_history``, ``min_history``, ``normal_min``,
+    ``point_tolerance`` and ``history_same_shape`` (their ``same_shape``) -- and anything else is a ``TypeError``.
+    ``accumulate=False`` filters the frame ``frame_no`` WOULD be without its history by the single-frame route (a spatial variance
+    estimate), and leaves history and ``frame_no`` as they are.  ``reset()`` starts a new sequence.  ``accumulator.count`` holds the
+    history lengths and ``last_variance`` the variance (before the filter) of the last accumulated frame."""
+
+    FILTER_KEYS = ("passes", "sigma_point", "normal_power_log2", "sigma_luminance", "epsilon", "same_shape")
+    HISTORY_KEYS = ("max_history", "min_history", "normal_min", "point_tolerance", "history_same_shape")
+
+    def __init__(self, world, tracer=None, samples: int = 4, background_color: Color = BLACK, init_state: int = 42, init_seq: int = 54,
+                 max_depth: int = 10, russian_roulette_limit: int = 3, filtered: bool = True, pcg=None, accumulate: bool = True, **params):
+        unknown = set(params) - set(self.FILTER_KEYS) - set(self.HISTORY_KEYS)
+        if unknown:
+            raise TypeError(f"VarianceGuidedGatherShader: unknown filter or accumulation parameter(s) {sorted(unknown)}")
+        super().__init__(world, tracer, samples, background_color, init_state, init_seq, max_depth, russian_roulette_limit, filtered, pcg)
+        self.params = {k: params[k] for k in self.FILTER_KEYS if k in params}
+        self.history_params = {("same_shape" if k == "history_same_shape" else k): params[k] for k in self.HISTORY_KEYS if k in params}
+        self.accumulate = bool(accumulate)
+        self.accumulator, self.frame_no, self.last_variance = None, 0, None
+
+    def reset(self) -> None:
+        self.frame_no = 0
+        if self.accumulator is not None:
+            self.accumulator.reset()
+
+    def shade_hits(self, frame) -> np.ndarray:
+        from .rays import VarianceAccumulator
+
+        if self.tracer is None:
+            raise TypeError("VarianceGuidedGatherShader.shade_hits needs the tracer whose device scene holds the world: "
+                            "VarianceGuidedGatherShader(world, tracer, ...)")
+        index = np.asarray(frame.shape_index)
+        if index.ndim != 3 or index.shape[0] != 1:
+            raise ValueError(f"VarianceGuidedGatherShader keeps one record per pixel, not a frame of {index.shape}: build the tracer with "
+                             "samples_per_side=0 or 1")
+        q = self.tracer.world_queries(self.world)
+        seq = self.init_seq + self.frame_no * (index.shape[1] * index.shape[2]) * self.samples
+        gathered = q.hemisphere_radiance(frame, self.samples, self.init_state, None, 1, self.max_depth, self.russian_roulette_limit,
+                                         self.background_color, 1, "none", init_seq=seq)
+        self.last_gather = gathered
+        e, variance = np.asarray(gathered.radiance)[0], None
+        if self.accumulate:
+            if self.accumulator is None or self.accumulator.queries.scene is not q.scene:
+                self.accumulator = VarianceAccumulator(q, **self.history_params)
+            e, variance = self.accumulator.update(e, frame, self.tracer.camera)
+            self.last_variance = variance
+            self.frame_no += 1
+        if self.filtered:
+            estimate = {} if self.accumulate else {k: v for k, v in self.history_params.items() if k in ("min_history", "normal_min", "point_tolerance")}
+            e, _ = q.variance_filtered(e, frame, variance=variance, **self.params, **estimate)
+        mat = q.materials(frame)
+        lit = np.asarray(mat.emitted) + np.asarray(mat.brdf_color) * e[None]
+        return np.where(np.asarray(mat.hit)[..., None], lit, self._background(frame))
+
+
 def scatter_ray(brdf, pcg, in_dir, point, normal):
     """``brdf.scatter_ray`` (materials.py:132-152, 175-196; the orthonormal basis of geometry.py:247-262) in Python floats with
     ``x * x`` for ``x**2``, for a BRDF that may be a parameter holder (by class name) -> (origin, direction, tmin)."""
