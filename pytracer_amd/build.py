@@ -20,6 +20,7 @@ after libptrace.so, in the order of ``ADDONS`` (csrc/ptrace_NAME.hip, include/pt
 * denoise: an edge-avoiding a-trous filter for the noisy frames and maps of the steps above, guided by their hit records
 * temporal: last frame's demodulated radiance reprojected onto this frame's hit records and blended with the new samples
 * variance: luminance moments for that accumulation, the per-pixel variance they give, and an a-trous filter guided by it
+* adaptive: sample counts from that variance, their prefix sum, and a gather whose sample count is a per-record plane
 """
 from __future__ import annotations
 
@@ -81,9 +82,15 @@ VARIANCE_ADDONS = {name: ([f"ptrace_{name}.hip"], os.path.join(HERE, f"libptrace
 VARIANCE_TARGETS = tuple((FLAGS[:-1] + [f"-cuid={cuid}"], lib, sources) for sources, lib, cuid in VARIANCE_ADDONS.values())
 ((VARIANCE_FLAGS, VARIANCE_LIB, VARIANCE_SOURCES),) = VARIANCE_TARGETS
 GUIDED_TARGETS = FRAME_TARGETS + VARIANCE_TARGETS
+# The add-ons since interface 1.11.  GUIDED_TARGETS keeps the value it had at interface 1.10 (tests/test_variance_host.py pins it:
+# twelve rows, the variance library's last), so what came later is listed here and SAMPLED_TARGETS is what build() and needs_build() walk.
+ADAPTIVE_ADDONS = {name: ([f"ptrace_{name}.hip"], os.path.join(HERE, f"libptrace_{name}.so"), f"libptrace_{name}") for name in ("adaptive",)}
+ADAPTIVE_TARGETS = tuple((FLAGS[:-1] + [f"-cuid={cuid}"], lib, sources) for sources, lib, cuid in ADAPTIVE_ADDONS.values())
+((ADAPTIVE_FLAGS, ADAPTIVE_LIB, ADAPTIVE_SOURCES),) = ADAPTIVE_TARGETS
+SAMPLED_TARGETS = GUIDED_TARGETS + ADAPTIVE_TARGETS
 # every file the translation units include: all of csrc/ (tests/test_host.py checks this list against the #include lines)
 DEPS = sorted(f for f in os.listdir(CSRC) if f.endswith((".hip", ".h"))) + [
-    os.path.join("..", "..", "include", h) for h in ["ptrace.h", "ptrace_debug.h"] + [f"ptrace_{name}.h" for name in list(ADDONS) + list(LATER_ADDONS) + list(NEWER_ADDONS) + list(NEWEST_ADDONS) + list(DENOISE_ADDONS) + list(TEMPORAL_ADDONS) + list(VARIANCE_ADDONS)]]
+    os.path.join("..", "..", "include", h) for h in ["ptrace.h", "ptrace_debug.h"] + [f"ptrace_{name}.h" for name in list(ADDONS) + list(LATER_ADDONS) + list(NEWER_ADDONS) + list(NEWEST_ADDONS) + list(DENOISE_ADDONS) + list(TEMPORAL_ADDONS) + list(VARIANCE_ADDONS) + list(ADAPTIVE_ADDONS)]]
 
 
 def code_hash(lib: str = LIB) -> str:
@@ -122,17 +129,17 @@ def _hipcc() -> str:
 
 
 def needs_build() -> bool:
-    libs = [lib for _, lib, _ in GUIDED_TARGETS]
+    libs = [lib for _, lib, _ in SAMPLED_TARGETS]
     if not all(os.path.exists(lib) for lib in libs):
         return True
-    t = min(os.path.getmtime(lib) for lib in libs)  # (one list of files for all twelve: they share the headers)
+    t = min(os.path.getmtime(lib) for lib in libs)  # (one list of files for all thirteen: they share the headers)
     return any(os.path.getmtime(os.path.join(CSRC, d)) > t for d in DEPS)
 
 
 def build(force: bool = False, verbose: bool = False) -> str:
     if not force and not needs_build():
         return LIB
-    for flags, lib, sources in GUIDED_TARGETS:
+    for flags, lib, sources in SAMPLED_TARGETS:
         cmd = [_hipcc()] + flags + ["-o", lib] + [os.path.join(CSRC, s) for s in sources]
         if verbose:
             print(" ".join(cmd), file=sys.stderr)

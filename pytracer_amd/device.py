@@ -1168,6 +1168,161 @@ class DeviceScene:
                                                       p(shape), p(buf), buf.nbytes, p(vbuf), vbuf.nbytes))
         return np.ascontiguousarray(buf.T).reshape(height, width, 3), vbuf.reshape(height, width)
 
+    # -- adaptive queries (include/ptrace_adaptive.h, libptrace_adaptive.so): sample counts from a variance, their prefix sum, a ragged gather --
+    def sample_counts(self, variance, colour, shape_index, device: bool = False, stream=None, out=None, m=None, **params):
+        """The counts query of include/ptrace_adaptive.h: per record ``ceil(gain * variance / (tolerance * max(lum(colour),
+        luminance_floor))^2)`` clamped into ``[min_samples, max_samples]``, ``max_samples`` where the variance is negative or NaN, 0
+        where ``shape_index`` is negative -> ``int32[m]``, :func:`pytracer_amd.rays.sample_counts_host` in every bit.  ``variance``
+        ``[m]``, ``colour`` ``[m, 3]``.  ``device=True``: the planes (``[m]`` and ``[3, m]`` fp64, int32) are in HBM (``m=`` where they
+        are raw addresses), the launch is enqueued on ``stream`` -> the output ``DeviceBuffer`` of ``m`` int32 (``out``, or a new one)."""
+        from . import _adaptive_lib, rays as rb
+
+        L, par = _adaptive_lib.lib(), _adaptive_lib.count_params(**params)
+        if device:
+            from .devmem import DeviceBuffer
+
+            handle = getattr(stream, "handle", stream)
+            if m is None:
+                if not hasattr(variance, "nbytes"):
+                    raise ValueError("m= is needed when the variance is a raw device address")
+                m = int(variance.nbytes) // 8
+            m = int(m)
+            if out is None:
+                out = DeviceBuffer((max(m, 1),), np.int32, self.device)
+            ptr = self._plane_ptr
+            _adaptive_lib.check(L.pt_rays_adaptive_counts_device(self.device, m, C.byref(par), ptr(variance, "variance"), ptr(colour, "colour"),
+                                                                 ptr(shape_index, "shape_index"), ptr(out, "out"), int(out.nbytes),
+                                                                 C.c_void_p(handle) if handle else None))
+            if hasattr(out, "rendered_on"):
+                out.rendered_on(stream)
+            return out
+        if stream is not None or out is not None or m is not None:
+            raise ValueError("stream=, out= and m= go with device=True (host planes are staged and synchronous)")
+        var = np.ascontiguousarray(variance, dtype=np.float64).reshape(-1)
+        shape = np.ascontiguousarray(shape_index, dtype=np.int32).reshape(-1)
+        col = rb.planar(colour, 3)
+        m = var.shape[0]
+        if shape.shape[0] != m or col.shape[1] != m:
+            raise ValueError(f"{m} variances, {col.shape[1]} colours and {shape.shape[0]} shape indices")
+        buf = np.zeros((m,), dtype=np.int32)
+        p = lambda a: a.ctypes.data_as(C.c_void_p)  # noqa: E731
+        _adaptive_lib.check(L.pt_rays_adaptive_counts(self.device, m, C.byref(par), p(var), p(col), p(shape), p(buf), buf.nbytes))
+        return buf
+
+    def sample_offsets(self, counts, device: bool = False, stream=None, out=None, workspace=None, n=None):
+        """The offsets query of include/ptrace_adaptive.h: ``int64[n + 1]``, the exclusive prefix sum of ``max(counts, 0)`` taken on
+        the device (three launches: sums of 256, their scan, the final pass); the last value is the total.
+        :func:`pytracer_amd.rays.sample_offsets_host` in every bit.  ``device=True``: ``counts`` is int32 in HBM (``n=`` where it is
+        a raw address), the launches are enqueued on ``stream`` -> the output ``DeviceBuffer`` of ``n + 1`` int64 (``out``, or a new
+        one); ``workspace``: ``pt_rays_adaptive_offsets_workspace_bytes(n)`` bytes (or a new buffer)."""
+        from . import _adaptive_lib
+
+        L = _adaptive_lib.lib()
+        if device:
+            from .devmem import DeviceBuffer
+
+            handle = getattr(stream, "handle", stream)
+            n = self._device_count(counts, n)
+            if out is None:
+                out = DeviceBuffer((n + 1,), np.int64, self.device)
+            if workspace is None:
+                workspace = DeviceBuffer((max(int(L.pt_rays_adaptive_offsets_workspace_bytes(n)), 8),), np.uint8, self.device)
+                out._offsets_workspace = workspace  # in flight on `stream` as long as the output is: freed with it
+            ptr = self._plane_ptr
+            _adaptive_lib.check(L.pt_rays_adaptive_offsets_device(self.device, n, ptr(counts, "counts"), ptr(out, "out"), int(out.nbytes),
+                                                                  ptr(workspace, "workspace"), int(workspace.nbytes),
+                                                                  C.c_void_p(handle) if handle else None))
+            for buf in (out, workspace):
+                if hasattr(buf, "rendered_on"):
+                    buf.rendered_on(stream)
+            return out
+        if stream is not None or out is not None or workspace is not None or n is not None:
+            raise ValueError("stream=, out=, workspace= and n= go with device=True (host planes are staged and synchronous)")
+        counts = np.ascontiguousarray(np.asarray(counts).reshape(-1), dtype=np.int32)
+        buf = np.zeros((counts.shape[0] + 1,), dtype=np.int64)
+        _adaptive_lib.check(L.pt_rays_adaptive_offsets(self.device, counts.shape[0], counts.ctypes.data_as(C.c_void_p), buf.ctypes.data_as(C.c_void_p),
+                                                       buf.nbytes))
+        return buf
+
+    def adaptive_workspace_bytes(self, n: int, capacity: int, num_of_rays: int = 1, max_depth: int = 10, depth: int = 0) -> int:
+        """Bytes of the workspace ``gather_ragged(device=True)`` needs for ``n`` records and sample planes of ``capacity`` samples
+        (``pt_rays_adaptive_workspace_bytes``: the node stacks, sized by the lanes a launch keeps resident, and four 8-byte planes of
+        ``capacity`` values)."""
+        from . import _adaptive_lib
+
+        need = int(_adaptive_lib.lib().pt_rays_adaptive_workspace_bytes(self.device, int(n), int(capacity), int(num_of_rays), int(max_depth),
+                                                                        int(depth)))
+        if need == 0:
+            raise ValueError(f"no workspace size for these arguments: {_adaptive_lib.last_error()}")
+        return need
+
+    def gather_ragged(self, points, normals, counts, offsets, capacity: int, init_state: int = 42, seqs=None, active=None, num_of_rays: int = 1,
+                      max_depth: int = 10, russian_roulette_limit: int = 3, background=(0.0, 0.0, 0.0), depth: int = 0, channels="all",
+                      init_seq: int = 54, device: bool = False, stream=None, out=None, workspace=None, n=None):
+        """:meth:`gather` with ``samples`` replaced by the per-record planes ``counts`` (``int32[n]``) and ``offsets`` (``int64[n +
+        1]``, :meth:`sample_offsets` of those counts): record ``i`` takes ``K_i = min(max(counts[i], 0), max(capacity - offsets[i],
+        0))`` samples, sample ``k`` from ``PCG(init_state, seqs[i] + k)`` (``seqs=None``: ``init_seq + offsets[i]``), and its radiance
+        and count are bit for bit :meth:`gather` 's for that record alone with ``samples = K_i`` (include/ptrace_adaptive.h).
+        ``capacity``: the samples the workspace's planes hold -- the hard budget.  ``channels``: ``"count"``, ``"taken"``, ``"all"``,
+        ``"none"`` or ``PT_ADAPTIVE_*`` bits -> :class:`pytracer_amd.rays.RaggedRadiance`.  ``device=True``: every plane is a
+        ``DeviceBuffer``, a device tensor or a raw address (then with ``n=``); the batch is enqueued on ``stream`` with ``workspace``
+        (:meth:`adaptive_workspace_bytes` bytes; ``None``: a new buffer) -> the output ``DeviceBuffer`` (``out``, or a new one)."""
+        from . import _adaptive_lib, rays as rb
+
+        L, block, bits = _adaptive_lib.lib(), self.kernel_args(), rb.adaptive_channels(channels)
+        par = _adaptive_lib.params(num_of_rays, max_depth, russian_roulette_limit, depth, init_state, init_seq, background, capacity)
+        if device:
+            from .devmem import DeviceBuffer
+
+            handle = getattr(stream, "handle", stream)
+            if n is None:
+                if not hasattr(points, "nbytes"):
+                    raise ValueError("n= is needed when the points are a raw device address")
+                n = int(points.nbytes) // 24
+            n = int(n)
+            if out is None:
+                out = DeviceBuffer((max(rb.adaptive_bytes(n, bits), 8),), np.uint8, self.device)
+            if workspace is None and n > 0:
+                # (0: arguments the library refuses -- the call below then says which, with its own error code)
+                need = int(L.pt_rays_adaptive_workspace_bytes(self.device, n, par.capacity, par.num_of_rays, par.max_depth, par.depth0))
+                if need:
+                    workspace = DeviceBuffer((need,), np.uint8, self.device)
+                    out._gather_workspace = workspace  # in flight on `stream` as long as the output is: freed with it
+            ptr = self._plane_ptr
+            _adaptive_lib.check(L.pt_rays_adaptive_gather_device(
+                self.device, block, len(block), ptr(points, "points"), ptr(normals, "normals"), ptr(active, "active"), ptr(seqs, "seqs"),
+                ptr(counts, "counts"), ptr(offsets, "offsets"), n, C.byref(par), bits, ptr(workspace, "workspace"),
+                int(workspace.nbytes) if workspace is not None else 0, ptr(out, "out"), int(out.nbytes), C.c_void_p(handle) if handle else None))
+            if hasattr(out, "rendered_on"):
+                out.rendered_on(stream)
+            if hasattr(workspace, "rendered_on"):
+                workspace.rendered_on(stream)
+            return out
+        if stream is not None or out is not None or n is not None or workspace is not None:
+            raise ValueError("stream=, out=, workspace= and n= go with device=True (host batches are staged and synchronous)")
+        points = np.ascontiguousarray(points, dtype=np.float64)
+        normals = np.ascontiguousarray(normals, dtype=np.float64)
+        if points.ndim != 2 or points.shape[0] != 3 or normals.shape != points.shape:
+            raise ValueError(f"points and normals must both be planar [3, n] (pytracer_amd.rays.planar), not {points.shape} and {normals.shape}")
+        n = points.shape[1]
+        counts = np.ascontiguousarray(np.asarray(counts).reshape(-1), dtype=np.int32)
+        offsets = np.ascontiguousarray(np.asarray(offsets).reshape(-1), dtype=np.int64)
+        if counts.shape != (n,) or offsets.shape != (n + 1,):
+            raise ValueError(f"{n} records take {n} counts and {n + 1} offsets, not {counts.shape[0]} and {offsets.shape[0]}")
+        if seqs is not None:
+            seqs = rb.stream_numbers(seqs)
+            if seqs.shape != (n,):
+                raise ValueError(f"seqs must hold one stream number per record ({n}), not {seqs.shape}")
+        if active is not None:
+            active = np.ascontiguousarray(np.asarray(active).reshape(-1), dtype=np.int32)
+            if active.shape != (n,):
+                raise ValueError(f"active must hold one int32 per record ({n}), not {active.shape}")
+        buf = np.zeros(rb.adaptive_bytes(n, bits), dtype=np.uint8)
+        p = lambda a: a.ctypes.data_as(C.c_void_p) if a is not None else None  # noqa: E731
+        _adaptive_lib.check(L.pt_rays_adaptive_gather(self.device, block, len(block), p(points), p(normals), p(active), p(seqs), p(counts),
+                                                      p(offsets), n, C.byref(par), bits, p(buf), buf.nbytes))
+        return rb.RaggedRadiance(buf, n, bits)
+
     def cull_probe(self, cam: abi.Camera, width: int, height: int, x0: int, x1: int, row0: int, row1: int,
                    pixel=None) -> np.ndarray:
         """Diagnostics: which shapes (by ``World.shapes`` index) the conservative cull of the primary rays through

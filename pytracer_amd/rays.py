@@ -84,6 +84,11 @@ GATHER_COUNT, GATHER_ALL = 1, 1  # PT_GATHER_* of include/ptrace_gather.h
 _GATHER_OF = {"count": GATHER_COUNT}
 
 
+ADAPTIVE_COUNT, ADAPTIVE_TAKEN, ADAPTIVE_ALL = 1, 2, 3  # PT_ADAPTIVE_* of include/ptrace_adaptive.h
+_ADAPTIVE_OF = {"count": ADAPTIVE_COUNT, "taken": ADAPTIVE_TAKEN}
+MAX_SAMPLES = 2 ** 20  # PT_ADAPTIVE_MAX_SAMPLES
+
+
 BAKE_COUNT, BAKE_ALL = 1, 1  # PT_BAKE_* of include/ptrace_bake.h
 _BAKE_OF = {"count": BAKE_COUNT}
 
@@ -526,6 +531,71 @@ class GatheredRadiance(_BatchViews):
         out = {"radiance": self.radiance}
         if self.has("count"):
             out["n_rays"] = self.n_rays
+        return out
+
+
+def adaptive_channels(channels) -> int:
+    """``PT_ADAPTIVE_*`` bits from an int, names (``"count"``, ``"taken"``, ``"count,taken"``), ``"all"`` or ``"none"``."""
+    return _parse_channels(channels, _ADAPTIVE_OF, ADAPTIVE_ALL, "adaptive")
+
+
+def adaptive_bytes(n: int, channels: int) -> int:
+    """Mirror of ``pt_rays_adaptive_bytes``: 0 for arguments the library refuses.  The ``taken`` plane (int32) is padded to 8 bytes."""
+    if not (0 <= n <= MAX_RAYS and 0 <= channels <= ADAPTIVE_ALL):
+        return 0
+    return n * 24 + (n * 8 if channels & ADAPTIVE_COUNT else 0) + ((n * 4 + 7) // 8 * 8 if channels & ADAPTIVE_TAKEN else 0)
+
+
+def adaptive_plane_offset(n: int, channels: int, channel: int, component: int = 0) -> int:
+    """Mirror of ``pt_rays_adaptive_plane_offset`` (bytes; ``channel`` 0: the three radiance planes, ``ADAPTIVE_COUNT``,
+    ``ADAPTIVE_TAKEN``; < 0: not selected)."""
+    if not (0 <= n <= MAX_RAYS and 0 <= channels <= ADAPTIVE_ALL) or component < 0:
+        return -1
+    if channel == 0:
+        return n * 8 * component if component < 3 else -1
+    if component > 0:
+        return -1
+    if channel == ADAPTIVE_COUNT and channels & ADAPTIVE_COUNT:
+        return n * 24
+    if channel == ADAPTIVE_TAKEN and channels & ADAPTIVE_TAKEN:
+        return n * 24 + (n * 8 if channels & ADAPTIVE_COUNT else 0)
+    return -1
+
+
+class RaggedRadiance(_BatchViews):
+    """Views over the buffer of a ragged gather (``buf``: ``pt_rays_adaptive_bytes`` bytes, contiguous ``uint8``).  Nothing here
+    copies.  ``radiance``: per record the mean of ``PathTracer(...)(ray)`` over the ``taken`` hemisphere rays it was given, summed in
+    sample order, with the component as last axis (black where ``taken`` is 0); ``n_rays``: the rays handed to a world query for the
+    record (``uint64``); ``taken``: the samples the record took (``int32``).  ``shape``: what the records' axis is viewed as."""
+
+    _names, _all, _what = _ADAPTIVE_OF, ADAPTIVE_ALL, "adaptive"
+    _bytes, _offset = staticmethod(adaptive_bytes), staticmethod(adaptive_plane_offset)
+
+    def __init__(self, buf, n: int, channels=ADAPTIVE_ALL, shape=None):
+        super().__init__(buf, n, channels, shape)
+        self.radiance = np.moveaxis(self.buffer[: self.n * 24].view(np.float64).reshape((3,) + self.shape), 0, -1)
+
+    def has(self, name: str) -> bool:  # (any other name is a channel this batch does not have, not an error)
+        return name in _ADAPTIVE_OF and super().has(name)
+
+    @property
+    def n_rays(self) -> np.ndarray:
+        return self._plane_views(ADAPTIVE_COUNT, 1, np.uint64)[0].reshape(self.shape)
+
+    @property
+    def taken(self) -> np.ndarray:
+        if not self.channels & ADAPTIVE_TAKEN:
+            raise KeyError(f"channel 'taken' was not selected for this adaptive batch (channels = {self.channels:#x})")
+        off = adaptive_plane_offset(self.n, self.channels, ADAPTIVE_TAKEN)
+        return self.buffer[off: off + self.n * 4].view(np.int32).reshape(self.shape)
+
+    def planes(self) -> dict:
+        """name -> view, for every selected channel."""
+        out = {"radiance": self.radiance}
+        if self.has("count"):
+            out["n_rays"] = self.n_rays
+        if self.has("taken"):
+            out["taken"] = self.taken
         return out
 
 
@@ -1187,6 +1257,96 @@ def variance_filter_host(colour, variance, shape, normal, point, width: int, hei
     return cur, var
 
 
+# ---- the mirrors of the adaptive queries (include/ptrace_adaptive.h) -------------------------------------------------------------------
+def _count_params(min_samples=1, max_samples=32, tolerance=0.05, luminance_floor=1.0, gain=1.0):
+    """The checks of ``pt_adaptive_count_params``, as ``ValueError`` s -> the values as Python numbers."""
+    lo, hi = int(min_samples), int(max_samples)
+    tolerance, floor, gain = float(tolerance), float(luminance_floor), float(gain)
+    if not 0 <= lo <= hi <= MAX_SAMPLES:
+        raise ValueError(f"min_samples={lo}, max_samples={hi}: 0 <= min <= max <= 2^20")
+    if not tolerance > 0.0:
+        raise ValueError(f"tolerance={tolerance}: positive (or inf)")
+    if not (floor > 0.0 and floor < float("inf")):
+        raise ValueError(f"luminance_floor={floor}: positive and finite")
+    if not (gain > 0.0 and gain < float("inf")):
+        raise ValueError(f"gain={gain}: positive and finite")
+    return lo, hi, tolerance, floor, gain
+
+
+def sample_counts_host(variance, colour, shape, **params) -> np.ndarray:
+    """The numpy mirror of the counts query (include/ptrace_adaptive.h), bit for bit: per pixel ``ceil(gain * variance / (tolerance
+    * max(lum(colour), luminance_floor))^2)`` clamped into ``[min_samples, max_samples]``; ``max_samples`` where the variance is
+    negative or NaN; 0 where ``shape`` is negative.  ``variance`` ``[...]``, ``colour`` ``[..., 3]``, ``shape`` ``[...]`` ->
+    ``int32`` shaped like ``variance``."""
+    lo, hi, tolerance, floor, gain = _count_params(**params)
+    v = np.asarray(variance, dtype=np.float64)
+    col = np.asarray(colour, dtype=np.float64).reshape(-1, 3)
+    index = np.asarray(shape, dtype=np.int32).reshape(-1)
+    flat = v.reshape(-1)
+    if col.shape[0] != flat.shape[0] or index.shape[0] != flat.shape[0]:
+        raise ValueError(f"{flat.shape[0]} variances, {col.shape[0]} colours and {index.shape[0]} shape indices")
+    with np.errstate(all="ignore"):
+        l = _luminance(col)
+        l = np.where(l > floor, l, floor)
+        tl = tolerance * l
+        want = (gain * flat) / (tl * tl)
+        ok = (flat >= 0.0) & (want < float(hi))
+        w = np.where(ok, want, 0.0)
+        t = w.astype(np.int64)
+        k = t + (t.astype(np.float64) < w)
+    k = np.maximum(k, lo)
+    out = np.where(ok, k, hi)
+    return np.where(index < 0, 0, out).astype(np.int32).reshape(v.shape)
+
+
+def sample_offsets_host(counts) -> np.ndarray:
+    """The numpy mirror of the offsets query: ``int64[n + 1]``, the exclusive prefix sum of ``max(counts, 0)``; the last value is
+    the total."""
+    c = np.asarray(counts).reshape(-1).astype(np.int64)
+    out = np.zeros(c.shape[0] + 1, dtype=np.int64)
+    np.cumsum(np.maximum(c, 0), out=out[1:])
+    return out
+
+
+def samples_taken_host(counts, offsets, capacity) -> np.ndarray:
+    """``K_i = min(max(counts[i], 0), max(capacity - offsets[i], 0))`` of include/ptrace_adaptive.h: what a ragged gather whose
+    sample planes hold ``capacity`` samples takes per record -- a batch beyond ``capacity`` is truncated in record order."""
+    c = np.maximum(np.asarray(counts).reshape(-1).astype(np.int64), 0)
+    off = np.asarray(offsets, dtype=np.int64).reshape(-1)
+    if off.shape[0] != c.shape[0] + 1:
+        raise ValueError(f"{c.shape[0]} counts need {c.shape[0] + 1} offsets, not {off.shape[0]}")
+    return np.minimum(c, np.maximum(int(capacity) - off[:-1], 0)).astype(np.int32)
+
+
+def gain_for_budget(variance, colour, shape, budget, **params) -> float:
+    """The largest ``gain`` (a positive finite double) at which :func:`sample_counts_host` of these planes sums to no more than
+    ``budget`` -- the total is monotone in ``gain``, so this is a bisection over the doubles (by their bit patterns: the result is
+    exact, the next double above it exceeds the budget unless nothing finite does).  A ``ValueError`` if even the smallest gain
+    exceeds it (``min_samples`` alone costs more).  For experiments that compare at equal cost, not for the hot path: it runs the
+    mirror some 62 times.  ``params``: the count query's, without ``gain``."""
+    if "gain" in params:
+        raise TypeError("gain_for_budget finds the gain: do not pass one")
+    budget = int(budget)
+
+    def total(bits: int) -> int:
+        gain = float(np.array([bits], dtype=np.int64).view(np.float64)[0])
+        return int(sample_counts_host(variance, colour, shape, gain=gain, **params).astype(np.int64).sum())
+
+    lo, hi = 1, int(np.array([np.finfo(np.float64).max]).view(np.int64)[0])  # the smallest and the largest positive finite double
+    if total(lo) > budget:
+        raise ValueError(f"no gain keeps the total within {budget} samples: the least it can be is {total(lo)}")
+    if total(hi) > budget:
+        while hi - lo > 1:  # total(lo) <= budget < total(hi)
+            mid = (lo + hi) // 2
+            if total(mid) <= budget:
+                lo = mid
+            else:
+                hi = mid
+    else:
+        lo = hi
+    return float(np.array([lo], dtype=np.int64).view(np.float64)[0])
+
+
 def texel_centres(width: int, height: int, window=None) -> np.ndarray:
     """``[h, w, 2]``: ``(u, v)`` at the centres of the texels of ``window`` (``(col0, row0, w, h)``; ``None``: all) of a
     ``width x height`` map, as the bake forms them: ``(col + 0.5) * (1.0 / width)``, ``(row + 0.5) * (1.0 / height)``."""
@@ -1375,6 +1535,45 @@ class WorldQueries:
         out = self.scene.gather(planar(points, 3), planar(normals, 3), samples, init_state, seqs, active, num_of_rays, max_depth,
                                 russian_roulette_limit, background, depth, bits, init_seq=init_seq)
         return GatheredRadiance(out.buffer, out.n, bits, shape=shape)
+
+    def sample_counts(self, values, hits, variance, **params) -> np.ndarray:
+        """How many hemisphere rays every pixel should get next, from how noisy its estimate still is -- on the device
+        (``DeviceScene.sample_counts``), :func:`sample_counts_host` in every bit.  ``values`` and ``hits``: as :meth:`denoised`
+        takes them, ONE record per pixel, the estimate ``E``; ``variance``: ``[H, W]``, the variance of ``values`` per pixel (what
+        :class:`VarianceAccumulator` returns).  ``params``: ``min_samples``, ``max_samples``, ``tolerance``, ``luminance_floor``,
+        ``gain`` -> ``int32 [H, W]``, 0 where nothing was hit."""
+        v, index, _, _, width, height = _one_record_frame(values, hits, "the sample counts")
+        if np.asarray(variance).size != height * width:
+            raise ValueError(f"a variance of {np.asarray(variance).shape} for a frame of {height} x {width}")
+        counts = self.scene.sample_counts(np.asarray(variance).reshape(-1), v.reshape(-1, 3), np.ascontiguousarray(index, dtype=np.int32), **params)
+        return counts.reshape(height, width)
+
+    def hemisphere_radiance_ragged(self, hits, counts, capacity=None, init_state: int = 42, seqs=None, num_of_rays: int = 1,
+                                   max_depth: int = 10, russian_roulette_limit: int = 3, background=(0.0, 0.0, 0.0), depth: int = 0,
+                                   channels="all", normals=None, active=None, init_seq: int = 54) -> RaggedRadiance:
+        """:meth:`hemisphere_radiance` with a sample count PER RECORD (``counts``: int32, shaped like the records; zero and negative:
+        no samples, black): the offsets query and the ragged gather of include/ptrace_adaptive.h, one behind the other.  Record
+        ``i``'s sample ``k`` draws from ``PCG(init_state, seqs[i] + k)``; ``seqs=None``: ``init_seq + offsets[i]``, which keeps all
+        streams disjoint.  Every record's radiance and count are, bit for bit, what :meth:`hemisphere_radiance` returns for it alone
+        with ``samples = taken[i]``.  ``capacity``: the hard ray budget -- a total beyond it is truncated in record order;
+        ``None``: the total itself, read back once from the offsets -> :class:`RaggedRadiance`, shaped like the records."""
+        if normals is None:
+            if not (hasattr(hits, "point") and hasattr(hits, "normal")):
+                raise ValueError("hits must carry point and normal (a RayHits or a hit frame), or pass the points with normals=")
+            points, normals, shape = hits.point, hits.normal, np.asarray(hits.shape_index).shape
+            if active is None:
+                active = hits.shape_index
+        else:
+            points = np.asarray(hits, dtype=np.float64)
+            shape = points.shape[:-1]
+        bits = adaptive_channels(channels)
+        counts = np.ascontiguousarray(np.asarray(counts).reshape(-1), dtype=np.int32)
+        offsets = self.scene.sample_offsets(counts)
+        if capacity is None:
+            capacity = int(offsets[-1])
+        out = self.scene.gather_ragged(planar(points, 3), planar(normals, 3), counts, offsets, capacity, init_state, seqs, active, num_of_rays,
+                                       max_depth, russian_roulette_limit, background, depth, bits, init_seq=init_seq)
+        return RaggedRadiance(out.buffer, out.n, bits, shape=shape)
 
     def surface_points(self, shape, uv, side=1):
         """The world point and unit normal at ``uv`` (``[..., 2]``) of ``World.shapes[shape]`` (``shape``: one index, or one per

@@ -666,6 +666,83 @@ class VarianceGuidedGatherShader(DenoisedGatherShader):
         return np.where(np.asarray(mat.hit)[..., None], lit, self._background(frame))
 
 
+class AdaptiveGatherShader(VarianceGuidedGatherShader):
+    """:class:`VarianceGuidedGatherShader` whose rays go where the estimate is still noisy: frame 0 is its uniform gather of
+    ``samples`` rays per pixel; from frame 1 on the previous frame's accumulated ``E`` and its variance (before the filter) give a
+    sample count per pixel (``WorldQueries.sample_counts``, include/ptrace_adaptive.h) and the gather is the ragged one
+    (``WorldQueries.hemisphere_radiance_ragged``).  The counts are read at THIS frame's pixels from LAST frame's planes: the camera
+    is assumed to move little between two frames, as the accumulation assumes it.  Frame ``f`` starts at the stream behind
+    everything the frames before it drew, so no two frames share a stream.
+
+    ``min_samples`` must be at least 1: a hit pixel without a sample would hand the accumulation a black estimate.  ``params``:
+    :class:`VarianceGuidedGatherShader` 's, and the counts' ``min_samples``, ``max_samples``, ``tolerance``, ``luminance_floor``,
+    ``gain``; ``budget`` (samples per frame, or ``None``) caps every ragged gather -- a total beyond it is truncated in record order.
+    ``last_counts`` holds the counts of the last frame (``None`` for a uniform one), ``last_total`` the samples it took.
+
+    OUT OF SCOPE: ``rays.TemporalAccumulator`` weights every frame equally whatever it cost, so a pixel's 32-sample frame counts
+    as much as its 1-sample frame.  Weighting frames by their samples would be a change to the accumulate query."""
+
+    COUNT_KEYS = ("min_samples", "max_samples", "tolerance", "luminance_floor", "gain")
+
+    def __init__(self, world, tracer=None, samples: int = 4, background_color: Color = BLACK, init_state: int = 42, init_seq: int = 54,
+                 max_depth: int = 10, russian_roulette_limit: int = 3, filtered: bool = True, pcg=None, accumulate: bool = True, budget=None,
+                 **params):
+        from ._adaptive_lib import DEFAULTS
+
+        count_params = dict(DEFAULTS, **{k: params.pop(k) for k in self.COUNT_KEYS if k in params})
+        if int(count_params["min_samples"]) < 1:
+            raise ValueError(f"AdaptiveGatherShader needs min_samples >= 1, not {count_params['min_samples']}")
+        try:
+            super().__init__(world, tracer, samples, background_color, init_state, init_seq, max_depth, russian_roulette_limit, filtered, pcg,
+                             accumulate, **params)
+        except TypeError as e:
+            raise TypeError(str(e).replace("VarianceGuidedGatherShader", "AdaptiveGatherShader")) from None
+        self.count_params, self.budget = count_params, None if budget is None else int(budget)
+        self.last_counts, self.last_total, self._next_seq, self._previous = None, 0, self.init_seq, None
+
+    def reset(self) -> None:
+        super().reset()
+        self.last_counts, self.last_total, self._next_seq, self._previous = None, 0, self.init_seq, None
+
+    def shade_hits(self, frame) -> np.ndarray:
+        from .rays import VarianceAccumulator
+
+        if self.tracer is None:
+            raise TypeError("AdaptiveGatherShader.shade_hits needs the tracer whose device scene holds the world: AdaptiveGatherShader(world, tracer, ...)")
+        index = np.asarray(frame.shape_index)
+        if index.ndim != 3 or index.shape[0] != 1:
+            raise ValueError(f"AdaptiveGatherShader keeps one record per pixel, not a frame of {index.shape}: build the tracer with samples_per_side=0 or 1")
+        q = self.tracer.world_queries(self.world)
+        m = index.shape[1] * index.shape[2]
+        if self._previous is not None and self._previous[1].size == m:
+            e_prev, var_prev = self._previous
+            counts = q.sample_counts(e_prev, frame, var_prev, **self.count_params)
+            gathered = q.hemisphere_radiance_ragged(frame, counts[None], self.budget, self.init_state, None, 1, self.max_depth,
+                                                    self.russian_roulette_limit, self.background_color, 1, "taken", init_seq=self._next_seq)
+            total = int(np.maximum(counts, 0).sum(dtype=np.int64))
+            self.last_counts, self.last_total = counts, int(np.asarray(gathered.taken).sum(dtype=np.int64))
+        else:
+            gathered = q.hemisphere_radiance(frame, self.samples, self.init_state, None, 1, self.max_depth, self.russian_roulette_limit,
+                                             self.background_color, 1, "none", init_seq=self._next_seq)
+            total = m * self.samples
+            self.last_counts, self.last_total = None, int((index >= 0).sum()) * self.samples
+        self.last_gather = gathered
+        e, variance = np.asarray(gathered.radiance)[0], None
+        if self.accumulate:
+            if self.accumulator is None or self.accumulator.queries.scene is not q.scene:
+                self.accumulator = VarianceAccumulator(q, **self.history_params)
+            e, variance = self.accumulator.update(e, frame, self.tracer.camera)
+            self.last_variance, self._previous = variance, (e, variance)
+            self.frame_no += 1
+            self._next_seq += total  # (the streams this frame's records were given, taken or not)
+        if self.filtered:
+            estimate = {} if self.accumulate else {k: v for k, v in self.history_params.items() if k in ("min_history", "normal_min", "point_tolerance")}
+            e, _ = q.variance_filtered(e, frame, variance=variance, **self.params, **estimate)
+        mat = q.materials(frame)
+        lit = np.asarray(mat.emitted) + np.asarray(mat.brdf_color) * e[None]
+        return np.where(np.asarray(mat.hit)[..., None], lit, self._background(frame))
+
+
 def scatter_ray(brdf, pcg, in_dir, point, normal):
     """``brdf.scatter_ray`` (materials.py:132-152, 175-196; the orthonormal basis of geometry.py:247-262) in Python floats with
     ``x * x`` for ``x**2``, for a BRDF that may be a parameter holder (by class name) -> (origin, direction, tmin)."""
