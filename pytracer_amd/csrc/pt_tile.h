@@ -968,6 +968,20 @@ PT_DEV void sphere_roots1(const PtKArgs &a, int slot, bool active, bool inside, 
   PT_SPHERE_ROOTS_IN(slot, inside);
 }
 
+// The lane's four pixel indices (pixel k: quadrant (k & 1, k >> 1) of the tile whose first local row is lr0; idle lanes stand
+// on a real pixel).  Made where a path STORES -- the dome shortcut, the shading -- not in front of the survivor loop: they are
+// eight vector registers that the loop does not read.  Every path still makes them once (profiles/r12_tile4_straight_ab.txt).
+PT_DEV void tile4_pixels(int lane, int tx, int lr0, int W, int rows_local, long long (&pix)[4]) {
+  const int colA = tx * 16 + (lane & 7), colB = colA + 8;
+  const int lrowA = lr0 + (lane >> 3), lrowB = lrowA + 8;
+  const int ccA = colA < W ? colA : W - 1, ccB = colB < W ? colB : W - 1;
+  const int crA = lrowA < rows_local ? lrowA : rows_local - 1, crB = lrowB < rows_local ? lrowB : rows_local - 1;
+  pix[0] = (long long)crA * W + ccA;
+  pix[1] = (long long)crA * W + ccB;
+  pix[2] = (long long)crB * W + ccA;
+  pix[3] = (long long)crB * W + ccB;
+}
+
 // SLDS (small worlds, Flat): every wave copies the scene's Flat palette (pt_layout.h: PtFlatPal, 32 B per shape, behind aux[])
 //   into its own slice of the dynamic LDS block, and step (a) of the shading gathers the pixels' colours from there instead of
 //   through the vector memory path.  The copy is asynchronous (one or two global -> LDS loads issued at the top, no register
@@ -1067,8 +1081,7 @@ __global__ __launch_bounds__(PT_BLOCK) __attribute__((amdgpu_waves_per_eu(PT_TIL
   // palette loads, the shading phase.  `valid` and `shade` are wave-uniform and only ever skip a phase's WORK, never the wait.
   bool shade = false;
   bool act[4];
-  long long pix[4];
-  V3 org, dir[4];
+  V3 dir[4];
   double bgx, bgy, bgz;
   Hit4 h4;
   const double tmin = 1.0e-5;
@@ -1114,12 +1127,6 @@ __global__ __launch_bounds__(PT_BLOCK) __attribute__((amdgpu_waves_per_eu(PT_TIL
     act[1] = okcB && okrA;
     act[2] = okcA && okrB;
     act[3] = okcB && okrB;
-    const int ccA = okcA ? colA : W - 1, ccB = okcB ? colB : W - 1;  // idle lanes stand on a real pixel
-    const int crA = okrA ? lrowA : rows_local - 1, crB = okrB ? lrowB : rows_local - 1;
-    pix[0] = (long long)crA * W + ccA;
-    pix[1] = (long long)crA * W + ccB;
-    pix[2] = (long long)crB * W + ccA;
-    pix[3] = (long long)crB * W + ccB;
     bool done = false;
     // ---- the dome shortcut (see pt_tile_kernel): one survivor, the camera well inside it, uniform pigments ----
     if (dome_on && nsurv == 1 && only < a.n_spheres) {
@@ -1140,6 +1147,8 @@ __global__ __launch_bounds__(PT_BLOCK) __attribute__((amdgpu_waves_per_eu(PT_TIL
           c.y = p1.y + p2.y;
           c.z = p1.z + p2.z;
         }
+        long long pix[4];
+        tile4_pixels(lane, tx, ty * TH, W, rows_local, pix);
 #pragma unroll
         for (int k = 0; k < NPX; ++k)
           if (act[k]) {
@@ -1172,9 +1181,9 @@ __global__ __launch_bounds__(PT_BLOCK) __attribute__((amdgpu_waves_per_eu(PT_TIL
         const double vA = 1.0 - __shfl(quot, 16 + (lane >> 3), 64), vB = 1.0 - __shfl(quot, 24 + (lane >> 3), 64);
         const double dyA = (1.0 - 2.0 * uA) * aspect, dyB = (1.0 - 2.0 * uB) * aspect;
         const double dzA = 2.0 * vA - 1.0, dzB = 2.0 * vB - 1.0;
-        const double m0 = c->cam_m[0], m1 = c->cam_m[1], m2 = c->cam_m[2], m3 = c->cam_m[3];
-        const double m4 = c->cam_m[4], m5 = c->cam_m[5], m6 = c->cam_m[6], m7 = c->cam_m[7];
-        const double m8 = c->cam_m[8], m9 = c->cam_m[9], m10 = c->cam_m[10], m11 = c->cam_m[11];
+        const double m0 = c->cam_m[0], m1 = c->cam_m[1], m2 = c->cam_m[2];
+        const double m4 = c->cam_m[4], m5 = c->cam_m[5], m6 = c->cam_m[6];
+        const double m8 = c->cam_m[8], m9 = c->cam_m[9], m10 = c->cam_m[10];
         // xf_vec: (d.x*m[0] + d.y*m[1]) + d.z*m[2] -- the bracket depends on the column only
         const double xA = dist * m0 + dyA * m1, xB = dist * m0 + dyB * m1;
         const double yA = dist * m4 + dyA * m5, yB = dist * m4 + dyB * m5;
@@ -1183,11 +1192,6 @@ __global__ __launch_bounds__(PT_BLOCK) __attribute__((amdgpu_waves_per_eu(PT_TIL
         dir[1] = {xB + dzA * m2, yB + dzA * m6, zB + dzA * m10};
         dir[2] = {xA + dzB * m2, yA + dzB * m6, zA + dzB * m10};
         dir[3] = {xB + dzB * m2, yB + dzB * m6, zB + dzB * m10};
-        // xf_point of (-dist, 0, 0): ((o.x*m[0] + 0*m[1]) + 0*m[2]) + m[3], exactly as primary_ray evaluates it
-        const double ox_ = -dist, oy_ = 0.0, oz_ = 0.0;
-        org.x = ox_ * m0 + oy_ * m1 + oz_ * m2 + m3;
-        org.y = ox_ * m4 + oy_ * m5 + oz_ * m6 + m7;
-        org.z = ox_ * m8 + oy_ * m9 + oz_ * m10 + m11;
         bgx = c->bg[0];
         bgy = c->bg[1];
         bgz = c->bg[2];
@@ -1200,7 +1204,7 @@ __global__ __launch_bounds__(PT_BLOCK) __attribute__((amdgpu_waves_per_eu(PT_TIL
         h4.best_t[k] = INFINITY;
         h4.best[k] = -1;
         Ray rk;
-        rk.o = org;
+        rk.o = {0.0, 0.0, 0.0};  // (wave_guard<true> reads the direction alone: the origin is hoisted)
         rk.d = dir[k];
         rk.tmin = tmin;
         fast = fast && wave_guard<true>(rk, act[k]).fast;
@@ -1272,6 +1276,8 @@ __global__ __launch_bounds__(PT_BLOCK) __attribute__((amdgpu_waves_per_eu(PT_TIL
   if (valid) PT_T4(8);  // (section 8 was the wait at the workgroup barrier; it is the wait for the wave's own loads now)
   if (shade) {
     // ---- shade + store ----
+    long long pix[4];
+    tile4_pixels(lane, tx, ty * TH, W, rows_local, pix);
     if constexpr (RENDERER == PT_RENDERER_ONOFF) {  // render.py:52-53
       pt_kargs ca = cold_args(a);
       const V3 on = {ca->onoff[0], ca->onoff[1], ca->onoff[2]}, bg = {bgx, bgy, bgz};
@@ -1414,6 +1420,17 @@ __global__ __launch_bounds__(PT_BLOCK) __attribute__((amdgpu_waves_per_eu(PT_TIL
       PT_T4(6);
       if (any_left) {
         // ---- the remainder: patterned spheres and image pigments, per pixel, as before the loop existed ----
+        // The rays' common origin, xf_point of (-dist, 0, 0): ((o.x*m[0] + 0*m[1]) + 0*m[2]) + m[3], exactly as primary_ray
+        // evaluates it.  Made here, where alone it is read (the loop's origins are hoisted per shape): it is wave-uniform but
+        // its fp64 sums live in vector registers, six of them across the survivor loop if made with the rays.
+        V3 org;
+        {
+          pt_kargs c = cold_args(a);
+          const double ox_ = -c->cam_dist, oy_ = 0.0, oz_ = 0.0;
+          org.x = ox_ * c->cam_m[0] + oy_ * c->cam_m[1] + oz_ * c->cam_m[2] + c->cam_m[3];
+          org.y = ox_ * c->cam_m[4] + oy_ * c->cam_m[5] + oz_ * c->cam_m[6] + c->cam_m[7];
+          org.z = ox_ * c->cam_m[8] + oy_ * c->cam_m[9] + oz_ * c->cam_m[10] + c->cam_m[11];
+        }
 #pragma unroll
         for (int k = 0; k < NPX; ++k) {
           const int hit = left[k];
