@@ -1015,12 +1015,124 @@ def adaptive(width, height, frames, step_deg, samples, min_samples, max_samples,
     tracer.close()
 
 
+@click.command("weighted")
+@click.option("--width", type=int, default=640, help="Width of the frame")
+@click.option("--height", type=int, default=480, help="Height of the frame")
+@click.option("--frames", type=int, default=8, help="Frames to render; the last one is written")
+@click.option("--step-deg", type=float, default=1.0, help="The camera turns by this many degrees about z from one frame to the next")
+@click.option("--samples", type=int, default=4, help="Hemisphere rays per pixel of the first frame, which is sampled uniformly")
+@click.option("--min-samples", type=int, default=1, help="Least rays a hit pixel gets in a later frame, 0 to --max-samples")
+@click.option("--max-samples", type=int, default=32, help="Most rays a pixel gets in a later frame, up to 2^20")
+@click.option("--tolerance", type=float, default=0.05, help="Relative standard error of a pixel's luminance the counts aim at, positive")
+@click.option("--luminance-floor", type=float, default=1.0, help="Least luminance the tolerance is relative to, positive and finite")
+@click.option("--gain", type=float, default=1.0, help="Scales every count, positive and finite")
+@click.option("--budget", type=int, default=None,
+              help="Most rays a later frame may take; beyond it the frame is cut off in pixel order and keeps its history (default: none)")
+@click.option("--max-history", type=int, default=32, help="The longest history length that is counted, 1 to 2^20")
+@click.option("--max-weight", type=float, default=128.0, help="Samples after which the weighted mean becomes an exponential average, 0 to inf")
+@click.option("--blend-weight", is_flag=True, help="A history's weight is the blend of its taps' weights, not the largest of them")
+@click.option("--min-history", type=int, default=4, help="History length below which the variance is estimated over a 7x7 window, 1 to 2^20")
+@click.option("--passes", type=int, default=4, help="Filter passes behind the accumulation, 1 to 10; 0: no filter")
+@click.option("--sigma-luminance", type=float, default=1.0,
+              help="The filter's: luminance difference, in standard deviations of the pixel, at which a tap's weight halves (inf: off)")
+@click.option("--max-depth", type=int, default=3, help="Maximum allowed ray depth of the gather's walks")
+@click.option("--init-state", type=int, default=45, help="Initial seed for the random number generator.")
+@click.option("--init-seq", type=int, default=54, help="Identifier of the first random sequence.")
+@click.option("--pfm-output", type=str, default="frame.pfm", help="Name of the PFM file to create")
+@click.option("--counts-output", type=str, default=None, help="Name of a PFM file (grey) of the last frame's sample counts (default: none)")
+@click.option("--declare-float", "-d", type=str, multiple=True, help="Declare a variable: --declare-float=VAR:VALUE")
+@click.option("--device", type=int, default=0, help="GPU to render on")
+@click.argument("input_scene_name", type=str, default="builtin:demo")
+def weighted(width, height, frames, step_deg, samples, min_samples, max_samples, tolerance, luminance_floor, gain, budget, max_history, max_weight,
+             blend_weight, min_history, passes, sigma_luminance, max_depth, init_state, init_seq, pfm_output, counts_output, declare_float, device,
+             input_scene_name):
+    """The `adaptive` command with an accumulation that weights every frame by the rays it took: a pixel's 31-ray frame counts 31 times
+    its 1-ray frame, a pixel that got no ray (--min-samples 0, or a --budget that ran out) keeps its history, and the accumulation
+    and the variance estimate are two launches.  Writes a PFM."""
+    import math
+
+    try:
+        if width < 1 or height < 1:
+            raise UsageError("--width and --height must be at least 1")
+        if frames < 1:
+            raise UsageError("--frames must be at least 1")
+        if not math.isfinite(step_deg):
+            raise UsageError("--step-deg must be finite")
+        if samples < 1:
+            raise UsageError("--samples must be at least 1")
+        if not 0 <= min_samples <= max_samples:
+            raise UsageError("--min-samples must be 0 to --max-samples")
+        if max_samples > 2 ** 20:
+            raise UsageError("--max-samples must be at most 2^20")
+        if not tolerance > 0.0:
+            raise UsageError("--tolerance must be positive (or inf)")
+        if not (luminance_floor > 0.0 and math.isfinite(luminance_floor)):
+            raise UsageError("--luminance-floor must be positive and finite")
+        if not (gain > 0.0 and math.isfinite(gain)):
+            raise UsageError("--gain must be positive and finite")
+        if budget is not None and not 0 <= budget <= 2 ** 31 - 1:
+            raise UsageError("--budget must be 0 to 2^31 - 1")
+        if not 1 <= max_history <= 2 ** 20:
+            raise UsageError("--max-history must be 1 to 2^20")
+        if not max_weight >= 0.0:
+            raise UsageError("--max-weight must not be negative (inf: no cap)")
+        if not 1 <= min_history <= 2 ** 20:
+            raise UsageError("--min-history must be 1 to 2^20")
+        if not 0 <= passes <= 10:
+            raise UsageError("--passes must be 0 to 10")
+        if not sigma_luminance > 0.0:
+            raise UsageError("--sigma-luminance must be positive (or inf)")
+        if max_depth < 0:
+            raise UsageError("--max-depth must not be negative")
+        world, camera, _ = _load_scene(input_scene_name, parse_float_overrides(declare_float), width, height)
+    except UsageError as e:
+        click.echo(f"pytracer_amd weighted: {e}", err=True)
+        sys.exit(2)
+    import numpy as np
+
+    from . import _lib, prefer_device_kernargs
+    from .shaders import WeightedAdaptiveGatherShader
+
+    prefer_device_kernargs()
+    _lib.standalone()  # (torch-free, like `adaptive`)
+    image = hm.HdrImage(width, height)
+    tracer = GpuImageTracer(image=image, camera=camera, samples_per_side=0, device=device)
+    shader = WeightedAdaptiveGatherShader(world, tracer, samples, init_state=init_state, init_seq=init_seq, max_depth=max_depth,
+                                          filtered=passes > 0, budget=budget, passes=max(passes, 1), sigma_luminance=sigma_luminance,
+                                          max_history=max_history, max_weight=max_weight, blend_weight=blend_weight, min_history=min_history,
+                                          min_samples=min_samples, max_samples=max_samples, tolerance=tolerance, luminance_floor=luminance_floor,
+                                          gain=gain)
+    wrote, totals = [], []
+    started = perf_counter()
+    for f in range(frames):
+        tracer.camera = scenes.turned_camera(camera, step_deg * f)
+        tracer.fire_all_rays(shader)
+        totals.append(shader.last_total)
+    wall = perf_counter() - started
+    with open(pfm_output, "wb") as out:
+        image.write_pfm(out)
+    wrote.append(pfm_output)
+    if counts_output:
+        last = np.zeros((height, width)) if shader.last_counts is None else np.asarray(shader.last_counts, dtype=np.float64)
+        grey = hm.HdrImage(width, height)
+        grey.set_array(np.repeat(last.reshape(height, width, 1), 3, axis=-1))
+        with open(counts_output, "wb") as out:
+            grey.write_pfm(out)
+        wrote.append(counts_output)
+    count, weight = shader.accumulator.count, shader.accumulator.weight
+    click.echo(f"{width}x{height} px, {len(world.shapes)} shape(s), {frames} frame(s), {step_deg:g} degree(s) per frame, "
+               f"rays per frame {' '.join(str(t) for t in totals)}, longest history {int(count.max())}, largest weight {float(np.max(weight)):g}, "
+               f"{wall:.3f} s: wrote {' and '.join(wrote)}")
+    tracer.close()
+
+
 cli.add_command(render)
 cli.add_command(lit)
 cli.add_command(denoise)
 cli.add_command(temporal)
 cli.add_command(variance)
 cli.add_command(adaptive)
+cli.add_command(weighted)
 cli.add_command(hits)
 cli.add_command(rays)
 cli.add_command(radiance)

@@ -1029,6 +1029,76 @@ class DeviceScene:
             count.rendered_on(stream)
         return count
 
+    # -- weighted accumulate queries (include/ptrace_weighted.h, libptrace_weighted.so): frames count by the samples they took -------
+    def weighted(self, colour, samples, shape_index, normal, point, prev_colour, prev_moments, prev_shape, prev_normal, prev_point, prev_count,
+                 prev_camera, width: int, height: int, device: bool = False, stream=None, out=None, out_moments=None, out_count=None, **params):
+        """The accumulation of include/ptrace_weighted.h over a ``width x height`` frame: the taps of :meth:`temporal` found once, and
+        from them the colour, the luminance moments ``(M1, M2)`` and the accumulated weight ``S`` blended with this frame's, whose
+        weight is ``samples`` (int32 per record; ``None``: one everywhere; 0 or less: nothing was sampled there and the reprojected
+        history is carried).  ``prev_moments``: ``[..., 3]`` = (M1, M2, S) of the previous frame.  ``params``: ``max_history``,
+        ``max_weight`` (the cap of the history's weight, inf: none), ``blend_weight`` (the history's weight is the taps' blend, not
+        their largest), ``same_shape``, ``normal_min``, ``point_tolerance`` -> ``(out [height, width, 3], moments [height, width, 3],
+        count [height, width] int32)``, :func:`pytracer_amd.rays.weighted_host` in every bit; ``moments`` and ``count`` are what
+        :meth:`variance_estimate` reads.  No scene is read.  ``device=True``: the planes (``[3, m]`` fp64, int32) are in HBM --
+        ``samples`` may be the address of the ``TAKEN`` plane of a ragged gather -- the one launch is enqueued on ``stream`` -> the
+        three output ``DeviceBuffer`` s (``out``, ``out_moments`` and ``out_count``, or new ones); none may overlap an input."""
+        from . import _weighted_lib, rays as rb
+
+        L, par, cam = _weighted_lib.lib(), _weighted_lib.params(**params), _weighted_lib.camera(prev_camera)
+        width, height = _weighted_lib._addon.c_int(width, "width"), _weighted_lib._addon.c_int(height, "height")
+        m = width * height
+        if device:
+            from .devmem import DeviceBuffer
+
+            handle = getattr(stream, "handle", stream)
+            if out is None:
+                out = DeviceBuffer((3, max(m, 1)), np.float64, self.device)
+            if out_moments is None:
+                out_moments = DeviceBuffer((3, max(m, 1)), np.float64, self.device)
+            if out_count is None:
+                out_count = DeviceBuffer((max(m, 1),), np.int32, self.device)
+            ptr = self._plane_ptr
+            _weighted_lib.check(L.pt_rays_weighted_accumulate_device(
+                self.device, width, height, C.byref(par), C.byref(cam), ptr(colour, "colour"), ptr(samples, "samples"),
+                ptr(shape_index, "shape_index"), ptr(normal, "normal"), ptr(point, "point"), ptr(prev_colour, "prev_colour"),
+                ptr(prev_moments, "prev_moments"), ptr(prev_shape, "prev_shape"), ptr(prev_normal, "prev_normal"), ptr(prev_point, "prev_point"),
+                ptr(prev_count, "prev_count"), ptr(out, "out"), int(out.nbytes), ptr(out_moments, "out_moments"), int(out_moments.nbytes),
+                ptr(out_count, "out_count"), int(out_count.nbytes), C.c_void_p(handle) if handle else None))
+            for buf in (out, out_moments, out_count):
+                if hasattr(buf, "rendered_on"):
+                    buf.rendered_on(stream)
+            return out, out_moments, out_count
+        if stream is not None or out is not None or out_moments is not None or out_count is not None:
+            raise ValueError("stream=, out=, out_moments= and out_count= go with device=True (host frames are staged and synchronous)")
+        ints = [np.ascontiguousarray(a, dtype=np.int32).reshape(-1) for a in (shape_index, prev_shape, prev_count)]
+        taken = None if samples is None else np.ascontiguousarray(samples, dtype=np.int32).reshape(-1)
+        planes = [rb.planar(a, 3) for a in (colour, normal, point, prev_colour, prev_moments, prev_normal, prev_point)]
+        if any(a.shape[0] != m for a in ints) or any(p.shape[1] != m for p in planes) or (taken is not None and taken.shape[0] != m):
+            raise ValueError(f"a {width} x {height} frame has {m} records, not {[a.shape[0] for a in ints]} shape indices and counts, "
+                             f"{None if taken is None else taken.shape[0]} sample counts and {[p.shape[1] for p in planes]} colours, normals, "
+                             "points and moments")
+        buf, mom, cnt = np.empty((3, m), dtype=np.float64), np.empty((3, m), dtype=np.float64), np.empty((m,), dtype=np.int32)
+        p = lambda a: a.ctypes.data_as(C.c_void_p) if a is not None else None  # noqa: E731
+        _weighted_lib.check(L.pt_rays_weighted_accumulate(self.device, width, height, C.byref(par), C.byref(cam), p(planes[0]), p(taken), p(ints[0]),
+                                                          p(planes[1]), p(planes[2]), p(planes[3]), p(planes[4]), p(ints[1]), p(planes[5]),
+                                                          p(planes[6]), p(ints[2]), p(buf), buf.nbytes, p(mom), mom.nbytes, p(cnt), cnt.nbytes))
+        return (np.ascontiguousarray(buf.T).reshape(height, width, 3), np.ascontiguousarray(mom.T).reshape(height, width, 3),
+                cnt.reshape(height, width))
+
+    def weighted_clear(self, count, m=None, stream=None):
+        """An empty history: the ``m`` int32 lengths of the device buffer ``count`` (default: all it holds) become 0 on ``stream``
+        (``pt_rays_weighted_clear_device``) -> ``count``.  With lengths of 0 no colour, moment or weight of the history is read."""
+        from . import _weighted_lib
+
+        handle = getattr(stream, "handle", stream)
+        m = self._device_count(count, m)
+        nbytes = int(count.nbytes) if hasattr(count, "nbytes") else 4 * m
+        _weighted_lib.check(_weighted_lib.lib().pt_rays_weighted_clear_device(self.device, m, self._plane_ptr(count, "count"), nbytes,
+                                                                              C.c_void_p(handle) if handle else None))
+        if hasattr(count, "rendered_on"):
+            count.rendered_on(stream)
+        return count
+
     # -- variance queries (include/ptrace_variance.h, libptrace_variance.so): moments, a per-pixel variance and a filter guided by it --
     @staticmethod
     def _variance_frame(width, height):

@@ -1118,6 +1118,93 @@ def luminance_moments_host(colour, shape, width: int, height: int) -> np.ndarray
     return out
 
 
+# ---- the mirror of the weighted accumulate query (include/ptrace_weighted.h) ------------------------------------------------------------
+def weighted_host(colour, samples, shape, normal, point, prev_colour, prev_moments, prev_shape, prev_normal, prev_point, prev_count, prev_camera,
+                  width: int, height: int, max_history: int = 32, same_shape: bool = True, blend_weight: bool = False, normal_min: float = 0.9,
+                  point_tolerance: float = 0.05, max_weight: float = 128.0):
+    """The numpy mirror of the weighted accumulate query (include/ptrace_weighted.h), operation for operation: the projection and
+    the four taps of :func:`temporal_host`, in its order, for the colour, the luminance moments and the weight at once.  The planes
+    as :func:`temporal_host` takes them, plus ``samples`` (int32 per record, or ``None``: one everywhere) and ``prev_moments``
+    (``[..., 3]``: M1, M2 and the accumulated weight S) -> ``(out [height, width, 3] float64, moments [height, width, 3] float64,
+    count [height, width] int32)``.  Refuses what the library refuses, with a ``ValueError``."""
+    W, H, max_history = int(width), int(height), int(max_history)
+    normal_min, point_tolerance, max_weight = float(normal_min), float(point_tolerance), float(max_weight)
+    if W < 0 or H < 0 or W * H > MAX_RAYS:
+        raise ValueError(f"a frame of {W} x {H} records")
+    if not 1 <= max_history <= 2 ** 20:
+        raise ValueError(f"max_history={max_history}: 1 to 2^20")
+    if not -1.0 <= normal_min <= 1.0 or not point_tolerance > 0.0:
+        raise ValueError(f"normal_min={normal_min} (a cosine, -1 to 1), point_tolerance={point_tolerance} (positive, or inf)")
+    if not max_weight >= 0.0:
+        raise ValueError(f"max_weight={max_weight}: not negative (or inf)")
+    cur = np.array(colour, dtype=np.float64).reshape(H, W, 3)
+    k = np.ones((H, W), dtype=np.int32) if samples is None else np.asarray(samples, dtype=np.int32).reshape(H, W)
+    sh = np.asarray(shape, dtype=np.int32).reshape(H, W)
+    nrm = np.asarray(normal, dtype=np.float64).reshape(H, W, 3)
+    pnt = np.asarray(point, dtype=np.float64).reshape(H, W, 3)
+    pcol = np.asarray(prev_colour, dtype=np.float64).reshape(H, W, 3)
+    pmom = np.asarray(prev_moments, dtype=np.float64).reshape(H, W, 3)
+    psh = np.asarray(prev_shape, dtype=np.int32).reshape(H, W)
+    pnrm = np.asarray(prev_normal, dtype=np.float64).reshape(H, W, 3)
+    ppnt = np.asarray(prev_point, dtype=np.float64).reshape(H, W, 3)
+    pcnt = np.asarray(prev_count, dtype=np.int32).reshape(H, W)
+    fx, fy, ok = temporal_project_host(prev_camera, pnt, W, H)
+    if W * H == 0:
+        return cur, np.zeros((H, W, 3)), np.zeros((H, W), dtype=np.int32)
+    hit = sh >= 0
+    ok = ok & hit
+    with np.errstate(all="ignore"):
+        unit = nrm / np.sqrt(nrm[..., 0] * nrm[..., 0] + nrm[..., 1] * nrm[..., 1] + nrm[..., 2] * nrm[..., 2])[..., None]
+        punit = pnrm / np.sqrt(pnrm[..., 0] * pnrm[..., 0] + pnrm[..., 1] * pnrm[..., 1] + pnrm[..., 2] * pnrm[..., 2])[..., None]
+        fx, fy = np.where(ok, fx, 0.0), np.where(ok, fy, 0.0)
+        x0f, y0f = np.floor(fx), np.floor(fy)
+        ax, ay = fx - x0f, fy - y0f
+        x0, y0 = x0f.astype(np.int64), y0f.astype(np.int64)
+        bx, by = (1.0 - ax, ax), (1.0 - ay, ay)
+        hs, hm, ws, smax = np.zeros((H, W, 3)), np.zeros((H, W, 3)), np.zeros((H, W)), np.zeros((H, W))
+        nmax, some = np.zeros((H, W), dtype=np.int64), np.zeros((H, W), dtype=bool)
+        for t in range(4):
+            x, y = x0 + (t & 1), y0 + (t >> 1)
+            take = ok & (x >= 0) & (x < W) & (y >= 0) & (y < H)
+            at = (np.clip(y, 0, H - 1), np.clip(x, 0, W - 1))
+            sq, nq, nu, pq, cq, mq = psh[at], pcnt[at].astype(np.int64), punit[at], ppnt[at], pcol[at], pmom[at]
+            take = take & (nq > 0) & (sq >= 0)
+            if same_shape:
+                take = take & (sq == sh)
+            c = unit[..., 0] * nu[..., 0] + unit[..., 1] * nu[..., 1] + unit[..., 2] * nu[..., 2]
+            d = pq - pnt
+            dz = unit[..., 0] * d[..., 0] + unit[..., 1] * d[..., 1] + unit[..., 2] * d[..., 2]
+            b = bx[t & 1] * by[t >> 1]
+            take = take & (c >= normal_min) & (np.abs(dz) <= point_tolerance) & (b > 0.0)
+            hs = np.where(take[..., None], hs + b[..., None] * cq, hs)
+            hm = np.where(take[..., None], hm + b[..., None] * mq, hm)  # (M1, M2 and S: three sums of their own)
+            ws = np.where(take, ws + b, ws)
+            nmax = np.where(take, np.maximum(nmax, nq), nmax)
+            smax = np.where(take & (mq[..., 2] > smax), mq[..., 2], smax)
+            some = some | take
+        l = _luminance(cur)
+        l2 = l * l
+        kd = k.astype(np.float64)
+        hist = hs / ws[..., None]
+        m1, m2 = hm[..., 0] / ws, hm[..., 1] / ws
+        Sh = hm[..., 2] / ws if blend_weight else smax
+        Sh = np.where(Sh > 0.0, Sh, 0.0)
+        Sh = np.where(Sh > max_weight, max_weight, Sh)
+        total = Sh + kd
+        alpha = kd / total
+        blended = hist + (cur - hist) * alpha[..., None]
+        M1 = m1 + (l - m1) * alpha
+        M2 = m2 + (l2 - m2) * alpha
+    took = k > 0
+    fresh = hit & ~some  # (step 4)
+    out = np.where((some & took)[..., None], blended, np.where((some & ~took)[..., None], hist, cur))
+    moments = np.zeros((H, W, 3))
+    for plane, new, carried, first in ((0, M1, m1, l), (1, M2, m2, l2), (2, total, Sh, kd)):
+        moments[..., plane] = np.where(some & took, new, np.where(some, carried, np.where(fresh & took, first, 0.0)))
+    count = np.where(some & took, np.minimum(nmax + 1, max_history), np.where(some, np.minimum(nmax, max_history), np.where(fresh & took, 1, 0)))
+    return out, moments, count.astype(np.int32)
+
+
 def _wrapped_columns(cols, offset, W, wrap_x):
     """Columns ``cols + offset`` of a frame ``W`` wide -> (the columns, clipped or wrapped into the frame; which of them exist)."""
     qx = cols + offset
@@ -1661,6 +1748,30 @@ class WorldQueries:
                                          np.asarray(prev.count).reshape(-1), prev_camera, width, height, **params)
         return TemporalHistory(out, index, normals, points, count)
 
+    def accumulated_weighted(self, values, samples, hits, prev: "WeightedHistory", prev_camera, **params) -> "WeightedHistory":
+        """:meth:`accumulated` with every frame weighted by the samples it took, for ``values`` and their luminance moments at once --
+        on the device (``DeviceScene.weighted``), :func:`weighted_host` in every bit.  ``samples``: ``[H, W]`` int32, what this
+        frame took per record (``None``: one everywhere; 0: nothing, the reprojected history is carried); ``prev``: the
+        :class:`WeightedHistory` of the previous frame (or ``WeightedHistory.empty``).  ``params``: those of
+        ``_weighted_lib.DEFAULTS`` -> the :class:`WeightedHistory` of this frame."""
+        v, index, normals, points, width, height = _one_record_frame(values, hits, "the accumulation")
+        index = np.ascontiguousarray(index, dtype=np.int32).reshape(height, width)
+        normals = np.asarray(normals, dtype=np.float64).reshape(height, width, 3)
+        points = np.asarray(points, dtype=np.float64).reshape(height, width, 3)
+        if np.asarray(prev.count).shape != (height, width):
+            raise ValueError(f"a history of {np.asarray(prev.count).shape} for a frame of {height} x {width}")
+        if samples is not None:
+            samples = np.asarray(samples)
+            if samples.size != height * width:
+                raise ValueError(f"{samples.size} sample counts for a frame of {height} x {width}")
+            samples = samples.reshape(-1)
+        out, moments, count = self.scene.weighted(v.reshape(-1, 3), samples, index.reshape(-1), normals.reshape(-1, 3), points.reshape(-1, 3),
+                                                  np.asarray(prev.colour).reshape(-1, 3), np.asarray(prev.moments).reshape(-1, 3),
+                                                  np.asarray(prev.shape_index).reshape(-1), np.asarray(prev.normal).reshape(-1, 3),
+                                                  np.asarray(prev.point).reshape(-1, 3), np.asarray(prev.count).reshape(-1), prev_camera, width,
+                                                  height, **params)
+        return WeightedHistory(out, index, normals, points, count, moments)
+
     def variance_filtered(self, values, hits, variance=None, count=None, **params):
         """``values`` filtered by the variance-guided a-trous filter of include/ptrace_variance.h, guided by ``hits`` -- on the
         device (``DeviceScene.variance_filter``), :func:`variance_filter_host` in every bit.  ``values`` and ``hits``: as
@@ -1918,3 +2029,111 @@ class VarianceAccumulator:
         scene.variance_estimate(mu, self.count, hits.shape_index, hits.normal, hits.point, width, height, device=True, stream=self.stream,
                                 out=out_variance, **self.estimate_params)
         return colour, out_variance
+
+
+# ---- accumulation weighted by samples (include/ptrace_weighted.h) ----------------------------------------------------------------------
+class WeightedHistory(TemporalHistory):
+    """:class:`TemporalHistory` plus ``moments`` ``[H, W, 3]``: the accumulated luminance moments M1, M2 and the accumulated weight S."""
+
+    def __init__(self, colour, shape_index, normal, point, count, moments):
+        super().__init__(colour, shape_index, normal, point, count)
+        self.moments = moments
+
+    @classmethod
+    def empty(cls, width: int, height: int) -> "WeightedHistory":
+        """The history before the first frame: every length 0, so nothing of it is ever read."""
+        base = TemporalHistory.empty(width, height)
+        return cls(base.colour, base.shape_index, base.normal, base.point, base.count, np.zeros((int(height), int(width), 3)))
+
+
+class WeightedAccumulator:
+    """The counterpart of :class:`VarianceAccumulator` on the weighted accumulate query (include/ptrace_weighted.h): every frame
+    counts by the samples it took.  ``update(values, hits, camera, samples=None)`` returns ``(accumulated E, variance)`` from TWO
+    launches -- ``DeviceScene.weighted``, which finds the taps once and blends colour, luminance moments and weight, and
+    ``DeviceScene.variance_estimate`` on its moments and lengths -- where :class:`VarianceAccumulator` makes four.  ``samples``: what
+    this frame took per record (int32; ``None``: one everywhere; 0: nothing was sampled there, the reprojected history is carried
+    and the record's colour is never read into it).  ``params``: ``max_history``, ``max_weight``, ``blend_weight`` (the
+    accumulation's), ``min_history`` (the estimate's), and ``same_shape``, ``normal_min``, ``point_tolerance``, which both read.
+    ``count`` holds the history lengths, ``weight`` the accumulated weights S, ``frames`` the number of updates since ``reset()``.
+
+    ``device=False``: ``values`` and ``hits`` as ``WorldQueries.accumulated`` takes them, ``samples`` ``[H, W]``; ``update`` returns
+    ``E`` ``[H, W, 3]`` and the variance ``[H, W]``; ``count`` and ``weight`` are ``[H, W]``.
+
+    ``device=True``: everything stays in HBM, with the buffer lifetimes of :class:`TemporalAccumulator`: ``values`` are ``[3, m]``
+    fp64 planes, ``samples`` ``m`` int32 (a ``DeviceBuffer`` or a raw address, such as the ``TAKEN`` plane of a ragged gather),
+    ``hits`` a :class:`DeviceGuides` (alternate two hit buffers), with ``width=`` and ``height=``; the two launches are enqueued on
+    ``stream``; ``update`` returns the colour ``DeviceBuffer`` (``[3, m]``) and the variance ``DeviceBuffer`` (``[m]``), both valid
+    until the next but one ``update``; ``count`` is the count buffer, ``weight`` the address of the S plane of the moments buffer
+    (``moments``, ``[3, m]``)."""
+
+    HISTORY_KEYS = ("max_history", "max_weight", "blend_weight", "same_shape", "normal_min", "point_tolerance")
+    ESTIMATE_KEYS = ("min_history", "same_shape", "normal_min", "point_tolerance")
+
+    def __init__(self, queries, device: bool = False, stream=None, **params):
+        unknown = set(params) - set(self.HISTORY_KEYS) - set(self.ESTIMATE_KEYS)
+        if unknown:
+            raise TypeError(f"WeightedAccumulator: unknown accumulation or estimate parameter(s) {sorted(unknown)}")
+        if stream is not None and not device:
+            raise ValueError("stream= goes with device=True (host frames are staged and synchronous)")
+        self.history_params = {k: v for k, v in params.items() if k in self.HISTORY_KEYS}
+        self.estimate_params = {k: v for k, v in params.items() if k in self.ESTIMATE_KEYS}
+        self.queries, self.device, self.stream = queries, bool(device), stream
+        self._buffers, self._m = None, -1
+        self.reset()
+
+    def reset(self) -> None:
+        """Forget the history: the next ``update`` starts a sequence."""
+        self._prev, self._camera, self.count, self.weight, self.moments, self.frames = None, None, None, None, None, 0
+
+    def update(self, values, hits, camera, samples=None, width=None, height=None):
+        from . import _weighted_lib
+
+        scene = self.queries.scene
+        cam = _weighted_lib.camera(camera)
+        cam = _weighted_lib.WeightedCamera.from_buffer_copy(cam)  # (the caller's camera may move on)
+        if not self.device:
+            if width is not None or height is not None:
+                raise ValueError("width= and height= go with device=True (a host frame brings its own)")
+            prev, prev_camera = self._prev, self._camera
+            if prev is None:
+                _, _, _, _, w, h = _one_record_frame(values, hits, "the accumulation")
+                prev, prev_camera = WeightedHistory.empty(w, h), cam
+            new = self.queries.accumulated_weighted(values, samples, hits, prev, prev_camera, **self.history_params)
+            h, w = np.asarray(new.count).shape
+            variance = scene.variance_estimate(np.asarray(new.moments).reshape(-1, 3), np.asarray(new.count).reshape(-1),
+                                               new.shape_index.reshape(-1), new.normal.reshape(-1, 3), new.point.reshape(-1, 3), w, h,
+                                               **self.estimate_params)
+            self._prev, self._camera, self.count, self.moments = new, cam, new.count, new.moments
+            self.weight = np.asarray(new.moments)[..., 2]
+            self.frames += 1
+            return new.colour, variance
+        from .devmem import DeviceBuffer
+
+        if width is None or height is None:
+            raise ValueError("device=True needs width= and height=: planes in HBM do not say what frame they are")
+        if not isinstance(hits, DeviceGuides):
+            raise TypeError(f"device=True takes hits as a DeviceGuides, not {type(hits).__name__}")
+        m = int(width) * int(height)
+        if self._buffers is None or self._m != m:
+            n = max(m, 1)
+            self._buffers = [(DeviceBuffer((3, n), np.float64, scene.device), DeviceBuffer((3, n), np.float64, scene.device),
+                              DeviceBuffer((n,), np.int32, scene.device), DeviceBuffer((n,), np.float64, scene.device)) for _ in range(2)]
+            self._m = m
+            self.reset()
+        out, out_moments, out_count, out_variance = self._buffers[self.frames & 1]
+        prev_colour, prev_moments, prev_count, _ = self._buffers[(self.frames & 1) ^ 1]
+        prev, prev_camera = self._prev, self._camera
+        if prev is None:  # (lengths of 0: neither the other buffers nor the guides handed in as the previous ones are read)
+            scene.weighted_clear(prev_count, m, self.stream)
+            prev, prev_camera = hits, cam
+        elif set(prev.addresses()) & set(hits.addresses()):
+            raise ValueError("this frame's guides lie where the previous frame's did: alternate two hit buffers")
+        scene.weighted(values, samples, hits.shape_index, hits.normal, hits.point, prev_colour, prev_moments, prev.shape_index, prev.normal,
+                       prev.point, prev_count, prev_camera, width, height, device=True, stream=self.stream, out=out, out_moments=out_moments,
+                       out_count=out_count, **self.history_params)
+        scene.variance_estimate(out_moments, out_count, hits.shape_index, hits.normal, hits.point, width, height, device=True, stream=self.stream,
+                                out=out_variance, **self.estimate_params)
+        self._prev, self._camera, self.count, self.moments = hits, cam, out_count, out_moments
+        self.weight = int(out_moments.data_ptr()) + 16 * m  # (plane 2 of [3, m] fp64)
+        self.frames += 1
+        return out, out_variance

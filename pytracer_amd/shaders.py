@@ -679,8 +679,8 @@ class AdaptiveGatherShader(VarianceGuidedGatherShader):
     ``gain``; ``budget`` (samples per frame, or ``None``) caps every ragged gather -- a total beyond it is truncated in record order.
     ``last_counts`` holds the counts of the last frame (``None`` for a uniform one), ``last_total`` the samples it took.
 
-    OUT OF SCOPE: ``rays.TemporalAccumulator`` weights every frame equally whatever it cost, so a pixel's 32-sample frame counts
-    as much as its 1-sample frame.  Weighting frames by their samples would be a change to the accumulate query."""
+    OUT OF SCOPE here: ``rays.TemporalAccumulator`` weights every frame equally whatever it cost, so a pixel's 32-sample frame counts as much
+    as its 1-sample frame.  :class:`WeightedAdaptiveGatherShader` weights frames by their samples (include/ptrace_weighted.h)."""
 
     COUNT_KEYS = ("min_samples", "max_samples", "tolerance", "luminance_floor", "gain")
 
@@ -732,6 +732,78 @@ class AdaptiveGatherShader(VarianceGuidedGatherShader):
             if self.accumulator is None or self.accumulator.queries.scene is not q.scene:
                 self.accumulator = VarianceAccumulator(q, **self.history_params)
             e, variance = self.accumulator.update(e, frame, self.tracer.camera)
+            self.last_variance, self._previous = variance, (e, variance)
+            self.frame_no += 1
+            self._next_seq += total  # (the streams this frame's records were given, taken or not)
+        if self.filtered:
+            estimate = {} if self.accumulate else {k: v for k, v in self.history_params.items() if k in ("min_history", "normal_min", "point_tolerance")}
+            e, _ = q.variance_filtered(e, frame, variance=variance, **self.params, **estimate)
+        mat = q.materials(frame)
+        lit = np.asarray(mat.emitted) + np.asarray(mat.brdf_color) * e[None]
+        return np.where(np.asarray(mat.hit)[..., None], lit, self._background(frame))
+
+
+class WeightedAdaptiveGatherShader(AdaptiveGatherShader):
+    """:class:`AdaptiveGatherShader` whose accumulation weights every frame by the samples it took
+    (``rays.WeightedAccumulator``, include/ptrace_weighted.h): a pixel's 31-sample frame counts 31 times its 1-sample frame, and the
+    accumulation and the variance estimate are two launches where :class:`AdaptiveGatherShader` makes four.  Frame 0 hands the
+    accumulator a plane that is ``samples`` at the hit records; every later frame hands it the ragged gather's ``taken`` plane.
+
+    ``min_samples = 0`` is legal here: a record that took no sample has weight 0, so its (black) radiance is never read into the
+    history, which is reprojected and carried as it was.  For the same reason a ``budget`` that runs out leaves the history of the
+    records it cut off untouched, where :class:`AdaptiveGatherShader` blends them in as black.
+
+    ``params``: :class:`AdaptiveGatherShader` 's, and the accumulation's ``max_weight`` (the cap of a history's weight; default
+    128) and ``blend_weight`` (the history's weight is the blend of the taps' weights, not their largest)."""
+
+    HISTORY_KEYS = AdaptiveGatherShader.HISTORY_KEYS + ("max_weight", "blend_weight")
+
+    def __init__(self, world, tracer=None, samples: int = 4, background_color: Color = BLACK, init_state: int = 42, init_seq: int = 54,
+                 max_depth: int = 10, russian_roulette_limit: int = 3, filtered: bool = True, pcg=None, accumulate: bool = True, budget=None,
+                 **params):
+        least = params.pop("min_samples", None)
+        if least is not None and int(least) < 0:
+            raise ValueError(f"WeightedAdaptiveGatherShader needs min_samples >= 0, not {least}")
+        try:
+            super().__init__(world, tracer, samples, background_color, init_state, init_seq, max_depth, russian_roulette_limit, filtered, pcg,
+                             accumulate, budget, **params)
+        except TypeError as e:
+            raise TypeError(str(e).replace("AdaptiveGatherShader", "WeightedAdaptiveGatherShader")) from None
+        if least is not None:
+            self.count_params["min_samples"] = int(least)
+
+    def shade_hits(self, frame) -> np.ndarray:
+        from .rays import WeightedAccumulator
+
+        if self.tracer is None:
+            raise TypeError("WeightedAdaptiveGatherShader.shade_hits needs the tracer whose device scene holds the world: "
+                            "WeightedAdaptiveGatherShader(world, tracer, ...)")
+        index = np.asarray(frame.shape_index)
+        if index.ndim != 3 or index.shape[0] != 1:
+            raise ValueError(f"WeightedAdaptiveGatherShader keeps one record per pixel, not a frame of {index.shape}: build the tracer with "
+                             "samples_per_side=0 or 1")
+        q = self.tracer.world_queries(self.world)
+        m = index.shape[1] * index.shape[2]
+        if self._previous is not None and self._previous[1].size == m:
+            e_prev, var_prev = self._previous
+            counts = q.sample_counts(e_prev, frame, var_prev, **self.count_params)
+            gathered = q.hemisphere_radiance_ragged(frame, counts[None], self.budget, self.init_state, None, 1, self.max_depth,
+                                                    self.russian_roulette_limit, self.background_color, 1, "taken", init_seq=self._next_seq)
+            total = int(np.maximum(counts, 0).sum(dtype=np.int64))
+            taken = np.asarray(gathered.taken, dtype=np.int32).reshape(index.shape[1:])
+            self.last_counts, self.last_total = counts, int(taken.sum(dtype=np.int64))
+        else:
+            gathered = q.hemisphere_radiance(frame, self.samples, self.init_state, None, 1, self.max_depth, self.russian_roulette_limit,
+                                             self.background_color, 1, "none", init_seq=self._next_seq)
+            total = m * self.samples
+            taken = np.where(index[0] >= 0, self.samples, 0).astype(np.int32)
+            self.last_counts, self.last_total = None, int((index >= 0).sum()) * self.samples
+        self.last_gather = gathered
+        e, variance = np.asarray(gathered.radiance)[0], None
+        if self.accumulate:
+            if self.accumulator is None or self.accumulator.queries.scene is not q.scene:
+                self.accumulator = WeightedAccumulator(q, **self.history_params)
+            e, variance = self.accumulator.update(e, frame, self.tracer.camera, samples=taken)
             self.last_variance, self._previous = variance, (e, variance)
             self.frame_no += 1
             self._next_seq += total  # (the streams this frame's records were given, taken or not)
