@@ -1126,6 +1126,110 @@ def weighted(width, height, frames, step_deg, samples, min_samples, max_samples,
     tracer.close()
 
 
+def parse_moves(switches: Iterable[str], n_shapes: int) -> Dict[int, tuple]:
+    """``SHAPE:DX:DY:DZ`` switches -> {shape index: (dx, dy, dz)}; a shape named twice moves by the sum."""
+    import math
+
+    moves: Dict[int, tuple] = {}
+    for text in switches:
+        parts = text.split(":")
+        try:
+            if len(parts) != 4:
+                raise ValueError
+            shape, step = int(parts[0]), tuple(float(x) for x in parts[1:])
+        except ValueError:
+            raise UsageError(f"--move={text!r}: expected SHAPE:DX:DY:DZ") from None
+        if not 0 <= shape < n_shapes:
+            raise UsageError(f"--move={text!r}: the world has shapes 0 to {n_shapes - 1}")
+        if not all(math.isfinite(x) for x in step):
+            raise UsageError(f"--move={text!r}: the step must be finite")
+        old = moves.get(shape, (0.0, 0.0, 0.0))
+        moves[shape] = tuple(a + b for a, b in zip(old, step))
+    return moves
+
+
+def moved_world(world, moves: Dict[int, tuple], times: int):
+    """A ``World`` with the shapes and lights of ``world``, those in ``moves`` translated by ``times`` of their step."""
+    import copy
+
+    out = copy.copy(world)
+    out.shapes = list(world.shapes)
+    for shape, (dx, dy, dz) in moves.items():
+        s = copy.copy(world.shapes[shape])
+        s.transformation = hm.translation(hm.Vec(dx * times, dy * times, dz * times)) * s.transformation
+        out.shapes[shape] = s
+    return out
+
+
+@click.command("motion")
+@click.option("--width", type=int, default=640, help="Width of the frame")
+@click.option("--height", type=int, default=480, help="Height of the frame")
+@click.option("--frames", type=int, default=8, help="Frames to render; the last one is written")
+@click.option("--step-deg", type=float, default=1.0, help="The camera turns by this many degrees about z from one frame to the next")
+@click.option("--samples", type=int, default=4, help="Hemisphere rays per pixel and frame")
+@click.option("--move", type=str, multiple=True, help="SHAPE:DX:DY:DZ: that shape is translated by that much per frame (repeatable)")
+@click.option("--no-follow", is_flag=True, help="Reproject through the camera only (the weighted accumulate query), for comparison")
+@click.option("--max-history", type=int, default=32, help="Frames after which the running mean becomes an exponential average, 1 to 2^20")
+@click.option("--passes", type=int, default=4, help="Filter passes behind the accumulation, 1 to 10; 0: no filter")
+@click.option("--max-depth", type=int, default=3, help="Maximum allowed ray depth of the gather's walks")
+@click.option("--init-state", type=int, default=45, help="Initial seed for the random number generator.")
+@click.option("--init-seq", type=int, default=54, help="Identifier of the first random sequence.")
+@click.option("--pfm-output", type=str, default="frame.pfm", help="Name of the PFM file to create")
+@click.option("--declare-float", "-d", type=str, multiple=True, help="Declare a variable: --declare-float=VAR:VALUE")
+@click.option("--device", type=int, default=0, help="GPU to render on")
+@click.argument("input_scene_name", type=str, default="builtin:demo")
+def motion(width, height, frames, step_deg, samples, move, no_follow, max_history, passes, max_depth, init_state, init_seq, pfm_output,
+           declare_float, device, input_scene_name):
+    """The last of --frames frames of a camera that turns about z over a world whose --move shapes are translated from frame to
+    frame, each lit by one bounce of few rays whose mean is accumulated over the frames by the motion accumulate query: the history
+    of a shape that moved is fetched where that surface point was on the previous screen.  Then the variance-guided filter, then
+    emitted + brdf_color * E.  Writes a PFM."""
+    import math
+
+    try:
+        if width < 1 or height < 1:
+            raise UsageError("--width and --height must be at least 1")
+        if frames < 1:
+            raise UsageError("--frames must be at least 1")
+        if not math.isfinite(step_deg):
+            raise UsageError("--step-deg must be finite")
+        if samples < 1:
+            raise UsageError("--samples must be at least 1")
+        if not 1 <= max_history <= 2 ** 20:
+            raise UsageError("--max-history must be 1 to 2^20")
+        if not 0 <= passes <= 10:
+            raise UsageError("--passes must be 0 to 10")
+        if max_depth < 0:
+            raise UsageError("--max-depth must not be negative")
+        world, camera, _ = _load_scene(input_scene_name, parse_float_overrides(declare_float), width, height)
+        moves = parse_moves(move, len(world.shapes))
+    except UsageError as e:
+        click.echo(f"pytracer_amd motion: {e}", err=True)
+        sys.exit(2)
+    from . import _lib, prefer_device_kernargs
+    from .shaders import MovingWorldGatherShader
+
+    prefer_device_kernargs()
+    _lib.standalone()  # (torch-free, like `temporal`)
+    image = hm.HdrImage(width, height)
+    tracer = GpuImageTracer(image=image, camera=camera, samples_per_side=0, device=device)
+    shader = MovingWorldGatherShader(world, tracer, samples, init_state=init_state, init_seq=init_seq, max_depth=max_depth, filtered=passes > 0,
+                                     passes=max(passes, 1), max_history=max_history)
+    shader.follow = not no_follow
+    started = perf_counter()
+    for f in range(frames):
+        tracer.camera = scenes.turned_camera(camera, step_deg * f)
+        shader.world = moved_world(world, moves, f)
+        tracer.fire_all_rays(shader)
+    wall = perf_counter() - started
+    with open(pfm_output, "wb") as out:
+        image.write_pfm(out)
+    count = shader.accumulator.count
+    click.echo(f"{width}x{height} px, {len(world.shapes)} shape(s), {len(moves)} moving{'' if shader.follow else ' (not followed)'}, {frames} frame(s) of "
+               f"{samples} ray(s) per pixel, {step_deg:g} degree(s) per frame, longest history {int(count.max())}, {wall:.3f} s: wrote {pfm_output}")
+    tracer.close()
+
+
 cli.add_command(render)
 cli.add_command(lit)
 cli.add_command(denoise)
@@ -1133,6 +1237,7 @@ cli.add_command(temporal)
 cli.add_command(variance)
 cli.add_command(adaptive)
 cli.add_command(weighted)
+cli.add_command(motion)
 cli.add_command(hits)
 cli.add_command(rays)
 cli.add_command(radiance)

@@ -1099,6 +1099,108 @@ class DeviceScene:
             count.rendered_on(stream)
         return count
 
+    # -- motion accumulate queries (include/ptrace_motion.h, libptrace_motion.so): histories follow the shapes that moved ----------------
+    def motion(self, colour, samples, shape_index, normal, point, prev_colour, prev_moments, prev_shape, prev_normal, prev_point, prev_count,
+               prev_camera, moved, motion, width: int, height: int, device: bool = False, stream=None, out=None, out_moments=None, out_count=None,
+               n_shapes=None, **params):
+        """:meth:`weighted` with a motion per shape (include/ptrace_motion.h): a record whose shape index ``s`` has ``moved[s] != 0``
+        is carried into the PREVIOUS frame's world -- its point by the affine map ``motion[s][0:12]``, its normal by the 3 x 3
+        ``motion[s][12:21]`` -- before it is projected onto the previous screen and tested against the taps, so the history of a shape
+        that moved is fetched where that surface point was.  ``moved``: int32 per shape, ``motion``: ``[S, 24]`` fp64, as
+        ``rays.shape_motion`` returns them; ``None`` for both: nothing moved, and every bit is :meth:`weighted`'s.  A shape index at
+        or beyond ``S`` is a static shape.  Everything else as :meth:`weighted` takes and returns it;
+        :func:`pytracer_amd.rays.motion_host` in every bit.  No scene is read.  ``device=True``: the planes and both tables are in
+        HBM (:meth:`motion_table` uploads the tables; raw addresses need ``n_shapes=``), the one launch is enqueued on ``stream``;
+        no output may overlap an input or a table."""
+        from . import _motion_lib, rays as rb
+
+        L, par, cam = _motion_lib.lib(), _motion_lib.params(**params), _motion_lib.camera(prev_camera)
+        width, height = _motion_lib._addon.c_int(width, "width"), _motion_lib._addon.c_int(height, "height")
+        m = width * height
+        if device:
+            from .devmem import DeviceBuffer
+
+            if (moved is None) != (motion is None):
+                raise ValueError("moved and motion come together (or neither: nothing moved)")
+            if n_shapes is None:
+                if moved is None:
+                    n_shapes = 0
+                elif hasattr(moved, "nbytes"):
+                    n_shapes = int(moved.nbytes) // 4
+                elif callable(getattr(moved, "numel", None)):
+                    n_shapes = int(moved.numel())
+                else:
+                    raise ValueError("n_shapes= is needed when the tables are raw device addresses")
+            n_shapes = _motion_lib._addon.c_int(n_shapes, "n_shapes")
+            handle = getattr(stream, "handle", stream)
+            if out is None:
+                out = DeviceBuffer((3, max(m, 1)), np.float64, self.device)
+            if out_moments is None:
+                out_moments = DeviceBuffer((3, max(m, 1)), np.float64, self.device)
+            if out_count is None:
+                out_count = DeviceBuffer((max(m, 1),), np.int32, self.device)
+            ptr = self._plane_ptr
+            _motion_lib.check(L.pt_rays_motion_accumulate_device(
+                self.device, width, height, C.byref(par), C.byref(cam), ptr(colour, "colour"), ptr(samples, "samples"),
+                ptr(shape_index, "shape_index"), ptr(normal, "normal"), ptr(point, "point"), ptr(prev_colour, "prev_colour"),
+                ptr(prev_moments, "prev_moments"), ptr(prev_shape, "prev_shape"), ptr(prev_normal, "prev_normal"), ptr(prev_point, "prev_point"),
+                ptr(prev_count, "prev_count"), n_shapes, ptr(moved, "moved"), ptr(motion, "motion"), ptr(out, "out"), int(out.nbytes),
+                ptr(out_moments, "out_moments"), int(out_moments.nbytes), ptr(out_count, "out_count"), int(out_count.nbytes),
+                C.c_void_p(handle) if handle else None))
+            for buf in (out, out_moments, out_count):
+                if hasattr(buf, "rendered_on"):
+                    buf.rendered_on(stream)
+            return out, out_moments, out_count
+        if stream is not None or out is not None or out_moments is not None or out_count is not None or n_shapes is not None:
+            raise ValueError("stream=, out=, out_moments=, out_count= and n_shapes= go with device=True (host frames are staged and synchronous)")
+        n_shapes, moved, motion = _motion_lib.tables(moved, motion)
+        ints = [np.ascontiguousarray(a, dtype=np.int32).reshape(-1) for a in (shape_index, prev_shape, prev_count)]
+        taken = None if samples is None else np.ascontiguousarray(samples, dtype=np.int32).reshape(-1)
+        planes = [rb.planar(a, 3) for a in (colour, normal, point, prev_colour, prev_moments, prev_normal, prev_point)]
+        if any(a.shape[0] != m for a in ints) or any(p.shape[1] != m for p in planes) or (taken is not None and taken.shape[0] != m):
+            raise ValueError(f"a {width} x {height} frame has {m} records, not {[a.shape[0] for a in ints]} shape indices and counts, "
+                             f"{None if taken is None else taken.shape[0]} sample counts and {[p.shape[1] for p in planes]} colours, normals, "
+                             "points and moments")
+        buf, mom, cnt = np.empty((3, m), dtype=np.float64), np.empty((3, m), dtype=np.float64), np.empty((m,), dtype=np.int32)
+        p = lambda a: a.ctypes.data_as(C.c_void_p) if a is not None else None  # noqa: E731
+        _motion_lib.check(L.pt_rays_motion_accumulate(self.device, width, height, C.byref(par), C.byref(cam), p(planes[0]), p(taken), p(ints[0]),
+                                                      p(planes[1]), p(planes[2]), p(planes[3]), p(planes[4]), p(ints[1]), p(planes[5]),
+                                                      p(planes[6]), p(ints[2]), n_shapes, p(moved), p(motion), p(buf), buf.nbytes, p(mom),
+                                                      mom.nbytes, p(cnt), cnt.nbytes))
+        return (np.ascontiguousarray(buf.T).reshape(height, width, 3), np.ascontiguousarray(mom.T).reshape(height, width, 3),
+                cnt.reshape(height, width))
+
+    def motion_table(self, moved, motion):
+        """The two tables of :meth:`motion` uploaded to this scene's device -> ``(moved, motion)`` as device tensors (int32 ``[S]``
+        and fp64 ``[S, 24]``; the allocator aligns them beyond the 64 bytes a record wants), complete when this returns, for
+        ``device=True`` calls on any stream.  The upload goes through PyTorch-ROCm, which the project uses for such plumbing: the
+        C-ABI has no host-to-device copy of its own.  ``S = 0`` -> ``(None, None)``: nothing moved."""
+        from . import _motion_lib
+
+        n_shapes, moved, motion = _motion_lib.tables(moved, motion)
+        if n_shapes == 0:
+            return None, None
+        if n_shapes > _motion_lib.MAX_SHAPES:
+            raise ValueError(f"n_shapes={n_shapes}: 0 to 2^20")
+        import torch
+
+        where = torch.device("cuda", self.device)
+        return torch.from_numpy(moved.copy()).to(where), torch.from_numpy(motion.copy()).to(where)
+
+    def motion_clear(self, count, m=None, stream=None):
+        """An empty history: the ``m`` int32 lengths of the device buffer ``count`` (default: all it holds) become 0 on ``stream``
+        (``pt_rays_motion_clear_device``) -> ``count``.  With lengths of 0 no colour, moment or weight of the history is read."""
+        from . import _motion_lib
+
+        handle = getattr(stream, "handle", stream)
+        m = self._device_count(count, m)
+        nbytes = int(count.nbytes) if hasattr(count, "nbytes") else 4 * m
+        _motion_lib.check(_motion_lib.lib().pt_rays_motion_clear_device(self.device, m, self._plane_ptr(count, "count"), nbytes,
+                                                                        C.c_void_p(handle) if handle else None))
+        if hasattr(count, "rendered_on"):
+            count.rendered_on(stream)
+        return count
+
     # -- variance queries (include/ptrace_variance.h, libptrace_variance.so): moments, a per-pixel variance and a filter guided by it --
     @staticmethod
     def _variance_frame(width, height):

@@ -1205,6 +1205,89 @@ def weighted_host(colour, samples, shape, normal, point, prev_colour, prev_momen
     return out, moments, count.astype(np.int32)
 
 
+# ---- the mirror of the motion accumulate query (include/ptrace_motion.h) ---------------------------------------------------------------
+def shape_motion(prev_world, world, static=()):
+    """The tables of the motion accumulate query for two worlds that hold the same shapes, in the same order, under transformations
+    that may differ -> ``(moved int32[S], motion float64[S, 24])``.  Per shape: ``motion[s][0:12]`` are rows 0..2 of
+    ``A = prev.transformation * cur.transformation.inverse()``, which takes a point of the shape in THIS frame's world to where that
+    surface point was in the PREVIOUS frame's; ``motion[s][12:21]`` is the transpose of the linear part of
+    ``cur.transformation * prev.transformation.inverse()`` (the host model's own ``Transformation`` product: its bits are the
+    definition), which carries a normal the same way; ``moved[s]`` is 0 where both matrices of the two transformations are equal
+    element for element, and for every index in ``static``.
+
+    WHAT BELONGS IN ``static``.  ``E`` is light arriving at a place.  A shape that moves ONTO ITSELF -- a sphere spinning about an
+    axis through its centre, a plane sliding in its own plane -- carries no light with it: list it in ``static`` and the history
+    stays where the light is.  Left in the table, its history would be fetched from the surface point that turned into this place,
+    which the light of another place fell on.
+
+    Raises ``ValueError`` when the worlds differ in the number or the kinds of their shapes."""
+    before, now = list(prev_world.shapes), list(world.shapes)
+    if len(before) != len(now):
+        raise ValueError(f"the previous world has {len(before)} shapes, this one {len(now)}: a motion needs the same shapes in both")
+    static = {int(s) for s in static}
+    moved, motion = np.zeros(len(now), dtype=np.int32), np.zeros((len(now), 24))
+    for s, (a, b) in enumerate(zip(before, now)):
+        if type(a) is not type(b):
+            raise ValueError(f"shape {s} was a {type(a).__name__} and is a {type(b).__name__}: a motion needs the same shapes in both")
+        ta, tb = a.transformation, b.transformation
+        forward = (ta * tb.inverse()).m
+        back = (tb * ta.inverse()).m
+        motion[s, :12] = [forward[i][j] for i in range(3) for j in range(4)]
+        motion[s, 12:21] = [back[j][i] for i in range(3) for j in range(3)]
+        same = all(ta.m[i][j] == tb.m[i][j] and ta.invm[i][j] == tb.invm[i][j] for i in range(4) for j in range(4))
+        moved[s] = 0 if same or s in static else 1
+    return moved, motion
+
+
+def _motion_tables(moved, motion):
+    """``(n_shapes, moved, motion [S, 24])`` of two tables, checked as the library checks them (``ValueError``)."""
+    from . import _motion_lib
+
+    n, moved, motion = _motion_lib.tables(moved, motion)
+    if n > _motion_lib.MAX_SHAPES:
+        raise ValueError(f"n_shapes={n}: 0 to 2^20")
+    return n, moved, motion
+
+
+def move_records_host(shape, normal, point, moved, motion):
+    """Step 1 of include/ptrace_motion.h on the host, operation for operation: a record whose shape index ``s`` lies in
+    ``0 <= s < len(moved)`` with ``moved[s] != 0`` gets ``pm = A_s * point`` and ``nm = N_s * normal`` (each row summed in the header's
+    order); every other record keeps its point and normal bit for bit, and no table entry is read for it -> ``(normal, point)`` in
+    the shapes they came in."""
+    n, moved, motion = _motion_tables(moved, motion)
+    nrm = np.array(normal, dtype=np.float64)
+    pnt = np.array(point, dtype=np.float64)
+    sh = np.asarray(shape, dtype=np.int32).reshape(-1)
+    nf, pf = nrm.reshape(-1, 3), pnt.reshape(-1, 3)
+    if n == 0 or sh.shape[0] == 0:
+        return nrm, pnt
+    listed = (sh >= 0) & (sh < n)
+    s = np.where(listed, sh, 0)
+    mv = listed & (moved[s] != 0)
+    t = motion[s]  # [m, 24]
+    px, py, pz = pf[:, 0], pf[:, 1], pf[:, 2]
+    nx, ny, nz = nf[:, 0], nf[:, 1], nf[:, 2]
+    with np.errstate(all="ignore"):
+        pm = [((t[:, 4 * i] * px + t[:, 4 * i + 1] * py) + t[:, 4 * i + 2] * pz) + t[:, 4 * i + 3] for i in range(3)]
+        nm = [(t[:, 12 + 3 * i] * nx + t[:, 13 + 3 * i] * ny) + t[:, 14 + 3 * i] * nz for i in range(3)]
+    new_p, new_n = np.stack(pm, axis=-1), np.stack(nm, axis=-1)
+    pf[mv], nf[mv] = new_p[mv], new_n[mv]
+    return nrm, pnt
+
+
+def motion_host(colour, samples, shape, normal, point, prev_colour, prev_moments, prev_shape, prev_normal, prev_point, prev_count, prev_camera,
+                moved, motion, width: int, height: int, **params):
+    """The numpy mirror of the motion accumulate query (include/ptrace_motion.h), operation for operation: step 1 is
+    :func:`move_records_host`, everything after it is :func:`weighted_host` on the moved records (contract D of the header is how
+    this mirror is made; contract C -- nothing moved, nothing changes -- follows).  The planes and ``params`` as
+    :func:`weighted_host` takes them, plus ``moved`` (int32 per shape) and ``motion`` (``[S, 24]``), or ``None`` for both -> ``(out
+    [height, width, 3] float64, moments [height, width, 3] float64, count [height, width] int32)``.  Refuses what the library refuses,
+    with a ``ValueError``."""
+    nm, pm = move_records_host(shape, normal, point, moved, motion)
+    return weighted_host(colour, samples, shape, nm, pm, prev_colour, prev_moments, prev_shape, prev_normal, prev_point, prev_count, prev_camera,
+                         width, height, **params)
+
+
 def _wrapped_columns(cols, offset, W, wrap_x):
     """Columns ``cols + offset`` of a frame ``W`` wide -> (the columns, clipped or wrapped into the frame; which of them exist)."""
     qx = cols + offset
@@ -1772,6 +1855,31 @@ class WorldQueries:
                                                   height, **params)
         return WeightedHistory(out, index, normals, points, count, moments)
 
+    def accumulated_moving(self, values, samples, hits, prev: "WeightedHistory", prev_camera, motion, **params) -> "WeightedHistory":
+        """:meth:`accumulated_weighted` for a world whose shapes moved since the previous frame -- on the device
+        (``DeviceScene.motion``), :func:`motion_host` in every bit.  ``motion``: ``(moved, motion)`` as :func:`shape_motion` returns
+        them, or ``None``: nothing moved.  A record whose shape moved is carried into the previous frame's world before it is
+        projected onto the previous screen and tested against the taps; the :class:`WeightedHistory` returned holds this frame's
+        own records, unmoved, as the next frame's guides."""
+        v, index, normals, points, width, height = _one_record_frame(values, hits, "the accumulation")
+        index = np.ascontiguousarray(index, dtype=np.int32).reshape(height, width)
+        normals = np.asarray(normals, dtype=np.float64).reshape(height, width, 3)
+        points = np.asarray(points, dtype=np.float64).reshape(height, width, 3)
+        if np.asarray(prev.count).shape != (height, width):
+            raise ValueError(f"a history of {np.asarray(prev.count).shape} for a frame of {height} x {width}")
+        if samples is not None:
+            samples = np.asarray(samples)
+            if samples.size != height * width:
+                raise ValueError(f"{samples.size} sample counts for a frame of {height} x {width}")
+            samples = samples.reshape(-1)
+        moved, table = (None, None) if motion is None else motion
+        out, moments, count = self.scene.motion(v.reshape(-1, 3), samples, index.reshape(-1), normals.reshape(-1, 3), points.reshape(-1, 3),
+                                                np.asarray(prev.colour).reshape(-1, 3), np.asarray(prev.moments).reshape(-1, 3),
+                                                np.asarray(prev.shape_index).reshape(-1), np.asarray(prev.normal).reshape(-1, 3),
+                                                np.asarray(prev.point).reshape(-1, 3), np.asarray(prev.count).reshape(-1), prev_camera, moved,
+                                                table, width, height, **params)
+        return WeightedHistory(out, index, normals, points, count, moments)
+
     def variance_filtered(self, values, hits, variance=None, count=None, **params):
         """``values`` filtered by the variance-guided a-trous filter of include/ptrace_variance.h, guided by ``hits`` -- on the
         device (``DeviceScene.variance_filter``), :func:`variance_filter_host` in every bit.  ``values`` and ``hits``: as
@@ -2135,5 +2243,106 @@ class WeightedAccumulator:
                                 out=out_variance, **self.estimate_params)
         self._prev, self._camera, self.count, self.moments = hits, cam, out_count, out_moments
         self.weight = int(out_moments.data_ptr()) + 16 * m  # (plane 2 of [3, m] fp64)
+        self.frames += 1
+        return out, out_variance
+
+
+# ---- accumulation that follows the shapes that moved (include/ptrace_motion.h) -----------------------------------------------------
+def _snapshot(world):
+    """The shapes of ``world`` as they are now (shallow copies: each keeps its kind and the transformation it has), so that a caller
+    who gives a shape of the same ``World`` a new transformation for the next frame is seen to have moved it."""
+    import copy
+    from types import SimpleNamespace
+
+    return SimpleNamespace(shapes=[copy.copy(s) for s in world.shapes])
+
+
+class MotionAccumulator(WeightedAccumulator):
+    """:class:`WeightedAccumulator` on the motion accumulate query (include/ptrace_motion.h): the history of a shape that moved
+    between two frames is fetched where that surface point was.  ``update(values, hits, camera, samples=None, world=None,
+    motion=None, queries=None)`` returns ``(accumulated E, variance)`` from TWO launches, ``DeviceScene.motion`` and
+    ``DeviceScene.variance_estimate``.
+
+    ``world=``: this frame's ``World``; the accumulator keeps the previous one and calls :func:`shape_motion` (with ``static``, the
+    shapes that move onto themselves -- see there).  ``motion=``: ``(moved, motion)``, a table of the caller's, instead.  Neither:
+    nothing moved, and every bit is :class:`WeightedAccumulator`'s.  ``queries=`` replaces the queries object: every frame of a
+    moving world has a device scene of its own, and the accumulation reads none.  Everything else, ``device=True`` and its buffer
+    lifetimes included, is :class:`WeightedAccumulator`'s; on the device the tables are uploaded by ``DeviceScene.motion_table`` and
+    kept until the next but one ``update``."""
+
+    def __init__(self, queries, device: bool = False, stream=None, static=(), **params):
+        self.static = tuple(static)
+        self._world, self._tables = None, [None, None]
+        try:
+            super().__init__(queries, device, stream, **params)
+        except TypeError as e:
+            raise TypeError(str(e).replace("WeightedAccumulator", "MotionAccumulator")) from None
+
+    def reset(self) -> None:
+        """Forget the history and the previous world: the next ``update`` starts a sequence."""
+        super().reset()
+        self._world = None
+
+    def update(self, values, hits, camera, samples=None, world=None, motion=None, queries=None, width=None, height=None):
+        from . import _motion_lib
+
+        if queries is not None:
+            self.queries = queries
+        if world is not None and motion is not None:
+            raise ValueError("world= (the accumulator derives the motion) or motion= (a table of the caller's), not both")
+        if world is not None and self._world is not None and self._prev is not None:
+            motion = shape_motion(self._world, world, self.static)
+        scene = self.queries.scene
+        cam = _motion_lib.camera(camera)
+        cam = _motion_lib.MotionCamera.from_buffer_copy(cam)  # (the caller's camera may move on)
+        if not self.device:
+            if width is not None or height is not None:
+                raise ValueError("width= and height= go with device=True (a host frame brings its own)")
+            prev, prev_camera = self._prev, self._camera
+            if prev is None:
+                _, _, _, _, w, h = _one_record_frame(values, hits, "the accumulation")
+                prev, prev_camera = WeightedHistory.empty(w, h), cam
+            new = self.queries.accumulated_moving(values, samples, hits, prev, prev_camera, motion, **self.history_params)
+            h, w = np.asarray(new.count).shape
+            variance = scene.variance_estimate(np.asarray(new.moments).reshape(-1, 3), np.asarray(new.count).reshape(-1),
+                                               new.shape_index.reshape(-1), new.normal.reshape(-1, 3), new.point.reshape(-1, 3), w, h,
+                                               **self.estimate_params)
+            self._prev, self._camera, self.count, self.moments = new, cam, new.count, new.moments
+            self.weight = np.asarray(new.moments)[..., 2]
+            self._world = None if world is None else _snapshot(world)
+            self.frames += 1
+            return new.colour, variance
+        from .devmem import DeviceBuffer
+
+        if width is None or height is None:
+            raise ValueError("device=True needs width= and height=: planes in HBM do not say what frame they are")
+        if not isinstance(hits, DeviceGuides):
+            raise TypeError(f"device=True takes hits as a DeviceGuides, not {type(hits).__name__}")
+        m = int(width) * int(height)
+        if self._buffers is None or self._m != m:
+            n = max(m, 1)
+            self._buffers = [(DeviceBuffer((3, n), np.float64, scene.device), DeviceBuffer((3, n), np.float64, scene.device),
+                              DeviceBuffer((n,), np.int32, scene.device), DeviceBuffer((n,), np.float64, scene.device)) for _ in range(2)]
+            self._m = m
+            self.reset()
+            motion = None  # (a new frame size starts a sequence: nothing to follow)
+        out, out_moments, out_count, out_variance = self._buffers[self.frames & 1]
+        prev_colour, prev_moments, prev_count, _ = self._buffers[(self.frames & 1) ^ 1]
+        prev, prev_camera = self._prev, self._camera
+        if prev is None:  # (lengths of 0: neither the other buffers nor the guides handed in as the previous ones are read)
+            scene.motion_clear(prev_count, m, self.stream)
+            prev, prev_camera = hits, cam
+        elif set(prev.addresses()) & set(hits.addresses()):
+            raise ValueError("this frame's guides lie where the previous frame's did: alternate two hit buffers")
+        moved_dev, motion_dev = (None, None) if motion is None else scene.motion_table(*motion)
+        self._tables[self.frames & 1] = (moved_dev, motion_dev)  # (held while the launch that reads them may be in flight)
+        scene.motion(values, samples, hits.shape_index, hits.normal, hits.point, prev_colour, prev_moments, prev.shape_index, prev.normal,
+                     prev.point, prev_count, prev_camera, moved_dev, motion_dev, width, height, device=True, stream=self.stream, out=out,
+                     out_moments=out_moments, out_count=out_count, **self.history_params)
+        scene.variance_estimate(out_moments, out_count, hits.shape_index, hits.normal, hits.point, width, height, device=True, stream=self.stream,
+                                out=out_variance, **self.estimate_params)
+        self._prev, self._camera, self.count, self.moments = hits, cam, out_count, out_moments
+        self.weight = int(out_moments.data_ptr()) + 16 * m  # (plane 2 of [3, m] fp64)
+        self._world = None if world is None else _snapshot(world)
         self.frames += 1
         return out, out_variance

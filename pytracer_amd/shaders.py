@@ -815,6 +815,71 @@ class WeightedAdaptiveGatherShader(AdaptiveGatherShader):
         return np.where(np.asarray(mat.hit)[..., None], lit, self._background(frame))
 
 
+class MovingWorldGatherShader(VarianceGuidedGatherShader):
+    """:class:`VarianceGuidedGatherShader` for a world whose shapes move between frames, on a ``rays.MotionAccumulator``
+    (include/ptrace_motion.h): the hit frame, a uniform gather of ``samples`` rays per pixel, the motion accumulate query -- which
+    fetches the history of a shape that moved where that surface point WAS -- the variance estimate, the variance-guided filter
+    (when ``filtered``) and the material.  ``world`` is the caller's to replace between frames (or to give its shapes new
+    transformations): the accumulator keeps the shapes of the frame before and derives the motion (``rays.shape_motion``), and the
+    history survives the new device scene every such frame brings.  ``static=``: the indices of shapes that move ONTO THEMSELVES (a
+    sphere spinning about its centre, a plane sliding in its own plane): ``E`` is light arriving at a place, and their history
+    stays where the light is.
+
+    ``params``: :class:`VarianceGuidedGatherShader` 's, and the accumulation's ``max_weight`` and ``blend_weight``.  ``follow = False``
+    (an attribute, set before the first frame) runs the same sequence on a ``rays.WeightedAccumulator``, for comparison.
+
+    ADAPTIVE COUNTS STAY OUT: ``WorldQueries.sample_counts`` reads last frame's planes at this frame's pixels, which for a moving
+    shape is a reprojection question of its own; every frame here is a uniform gather."""
+
+    HISTORY_KEYS = VarianceGuidedGatherShader.HISTORY_KEYS + ("max_weight", "blend_weight")
+
+    def __init__(self, world, tracer=None, samples: int = 4, background_color: Color = BLACK, init_state: int = 42, init_seq: int = 54,
+                 max_depth: int = 10, russian_roulette_limit: int = 3, filtered: bool = True, pcg=None, accumulate: bool = True, static=(),
+                 **params):
+        try:
+            super().__init__(world, tracer, samples, background_color, init_state, init_seq, max_depth, russian_roulette_limit, filtered, pcg,
+                             accumulate, **params)
+        except TypeError as e:
+            raise TypeError(str(e).replace("VarianceGuidedGatherShader", "MovingWorldGatherShader")) from None
+        self.static, self.follow = tuple(static), True
+
+    def shade_hits(self, frame) -> np.ndarray:
+        from .rays import MotionAccumulator, WeightedAccumulator
+
+        if self.tracer is None:
+            raise TypeError("MovingWorldGatherShader.shade_hits needs the tracer whose device scene holds the world: "
+                            "MovingWorldGatherShader(world, tracer, ...)")
+        index = np.asarray(frame.shape_index)
+        if index.ndim != 3 or index.shape[0] != 1:
+            raise ValueError(f"MovingWorldGatherShader keeps one record per pixel, not a frame of {index.shape}: build the tracer with "
+                             "samples_per_side=0 or 1")
+        q = self.tracer.world_queries(self.world)
+        seq = self.init_seq + self.frame_no * (index.shape[1] * index.shape[2]) * self.samples
+        gathered = q.hemisphere_radiance(frame, self.samples, self.init_state, None, 1, self.max_depth, self.russian_roulette_limit,
+                                         self.background_color, 1, "none", init_seq=seq)
+        self.last_gather = gathered
+        e, variance = np.asarray(gathered.radiance)[0], None
+        if self.accumulate:
+            taken = np.where(index[0] >= 0, self.samples, 0).astype(np.int32)
+            if self.follow:
+                if self.accumulator is None:
+                    self.accumulator = MotionAccumulator(q, static=self.static, **self.history_params)
+                e, variance = self.accumulator.update(e, frame, self.tracer.camera, samples=taken, world=self.world, queries=q)
+            else:  # (for comparison: the same sequence reprojected through the camera only)
+                if self.accumulator is None:
+                    self.accumulator = WeightedAccumulator(q, **self.history_params)
+                self.accumulator.queries = q
+                e, variance = self.accumulator.update(e, frame, self.tracer.camera, samples=taken)
+            self.last_variance = variance
+            self.frame_no += 1
+        if self.filtered:
+            estimate = {} if self.accumulate else {k: v for k, v in self.history_params.items() if k in ("min_history", "normal_min", "point_tolerance")}
+            e, _ = q.variance_filtered(e, frame, variance=variance, **self.params, **estimate)
+        mat = q.materials(frame)
+        lit = np.asarray(mat.emitted) + np.asarray(mat.brdf_color) * e[None]
+        return np.where(np.asarray(mat.hit)[..., None], lit, self._background(frame))
+
+
 def scatter_ray(brdf, pcg, in_dir, point, normal):
     """``brdf.scatter_ray`` (materials.py:132-152, 175-196; the orthonormal basis of geometry.py:247-262) in Python floats with
     ``x * x`` for ``x**2``, for a BRDF that may be a parameter holder (by class name) -> (origin, direction, tmin)."""
