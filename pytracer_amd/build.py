@@ -23,6 +23,7 @@ after libptrace.so, in the order of ``ADDONS`` (csrc/ptrace_NAME.hip, include/pt
 * adaptive: sample counts from that variance, their prefix sum, and a gather whose sample count is a per-record plane
 * weighted: that accumulation with every frame weighted by the samples it took, colour and luminance moments in one launch
 * motion: the weighted accumulation with a motion per shape, so that the history of a shape that moved is fetched where it was
+* gradient: probes re-gathered in the previous world, the share of its history each pixel keeps, and the motion accumulation with it
 """
 from __future__ import annotations
 
@@ -102,9 +103,15 @@ MOTION_ADDONS = {name: ([f"ptrace_{name}.hip"], os.path.join(HERE, f"libptrace_{
 MOTION_TARGETS = tuple((FLAGS[:-1] + [f"-cuid={cuid}"], lib, sources) for sources, lib, cuid in MOTION_ADDONS.values())
 ((MOTION_FLAGS, MOTION_LIB, MOTION_SOURCES),) = MOTION_TARGETS
 MOVING_TARGETS = HISTORY_TARGETS + MOTION_TARGETS
+# The add-ons since interface 1.14.  MOVING_TARGETS keeps the value it had at interface 1.13 (tests/test_motion_host.py pins it:
+# fifteen rows, the motion library's last), so what came later is listed here and LIGHT_TARGETS is what build() and needs_build() walk.
+GRADIENT_ADDONS = {name: ([f"ptrace_{name}.hip"], os.path.join(HERE, f"libptrace_{name}.so"), f"libptrace_{name}") for name in ("gradient",)}
+GRADIENT_TARGETS = tuple((FLAGS[:-1] + [f"-cuid={cuid}"], lib, sources) for sources, lib, cuid in GRADIENT_ADDONS.values())
+((GRADIENT_FLAGS, GRADIENT_LIB, GRADIENT_SOURCES),) = GRADIENT_TARGETS
+LIGHT_TARGETS = MOVING_TARGETS + GRADIENT_TARGETS
 # every file the translation units include: all of csrc/ (tests/test_host.py checks this list against the #include lines)
 DEPS = sorted(f for f in os.listdir(CSRC) if f.endswith((".hip", ".h"))) + [
-    os.path.join("..", "..", "include", h) for h in ["ptrace.h", "ptrace_debug.h"] + [f"ptrace_{name}.h" for name in list(ADDONS) + list(LATER_ADDONS) + list(NEWER_ADDONS) + list(NEWEST_ADDONS) + list(DENOISE_ADDONS) + list(TEMPORAL_ADDONS) + list(VARIANCE_ADDONS) + list(ADAPTIVE_ADDONS) + list(WEIGHTED_ADDONS) + list(MOTION_ADDONS)]]
+    os.path.join("..", "..", "include", h) for h in ["ptrace.h", "ptrace_debug.h"] + [f"ptrace_{name}.h" for name in list(ADDONS) + list(LATER_ADDONS) + list(NEWER_ADDONS) + list(NEWEST_ADDONS) + list(DENOISE_ADDONS) + list(TEMPORAL_ADDONS) + list(VARIANCE_ADDONS) + list(ADAPTIVE_ADDONS) + list(WEIGHTED_ADDONS) + list(MOTION_ADDONS) + list(GRADIENT_ADDONS)]]
 
 
 def code_hash(lib: str = LIB) -> str:
@@ -143,17 +150,17 @@ def _hipcc() -> str:
 
 
 def needs_build() -> bool:
-    libs = [lib for _, lib, _ in MOVING_TARGETS]
+    libs = [lib for _, lib, _ in LIGHT_TARGETS]
     if not all(os.path.exists(lib) for lib in libs):
         return True
-    t = min(os.path.getmtime(lib) for lib in libs)  # (one list of files for all fifteen: they share the headers)
+    t = min(os.path.getmtime(lib) for lib in libs)  # (one list of files for all sixteen: they share the headers)
     return any(os.path.getmtime(os.path.join(CSRC, d)) > t for d in DEPS)
 
 
 def build(force: bool = False, verbose: bool = False) -> str:
     if not force and not needs_build():
         return LIB
-    for flags, lib, sources in MOVING_TARGETS:
+    for flags, lib, sources in LIGHT_TARGETS:
         cmd = [_hipcc()] + flags + ["-o", lib] + [os.path.join(CSRC, s) for s in sources]
         if verbose:
             print(" ".join(cmd), file=sys.stderr)

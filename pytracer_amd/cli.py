@@ -1230,6 +1230,88 @@ def motion(width, height, frames, step_deg, samples, move, no_follow, max_histor
     tracer.close()
 
 
+@click.command("gradient")
+@click.option("--width", type=int, default=640, help="Width of the frame")
+@click.option("--height", type=int, default=480, help="Height of the frame")
+@click.option("--frames", type=int, default=8, help="Frames to render; the last one is written")
+@click.option("--step-deg", type=float, default=1.0, help="The camera turns by this many degrees about z from one frame to the next")
+@click.option("--samples", type=int, default=4, help="Hemisphere rays per pixel and frame")
+@click.option("--move", type=str, multiple=True, help="SHAPE:DX:DY:DZ: that shape is translated by that much per frame (repeatable)")
+@click.option("--no-follow-light", is_flag=True, help="Follow the shapes only (the motion accumulate query), for comparison")
+@click.option("--stratum", type=int, default=3, help="One probe per block of this many pixels squared, 1 to 16")
+@click.option("--radius", type=int, default=1, help="A pixel listens to the probes of (2 radius + 1)^2 blocks, 0 to 4")
+@click.option("--gain", type=float, default=8.0, help="How much of the history a relative change of 1 takes away; 0: nothing")
+@click.option("--max-history", type=int, default=32, help="Frames after which the running mean becomes an exponential average, 1 to 2^20")
+@click.option("--passes", type=int, default=4, help="Filter passes behind the accumulation, 1 to 10; 0: no filter")
+@click.option("--max-depth", type=int, default=3, help="Maximum allowed ray depth of the gather's walks")
+@click.option("--init-state", type=int, default=45, help="Initial seed for the random number generator.")
+@click.option("--init-seq", type=int, default=54, help="Identifier of the first random sequence.")
+@click.option("--pfm-output", type=str, default="frame.pfm", help="Name of the PFM file to create")
+@click.option("--declare-float", "-d", type=str, multiple=True, help="Declare a variable: --declare-float=VAR:VALUE")
+@click.option("--device", type=int, default=0, help="GPU to render on")
+@click.argument("input_scene_name", type=str, default="builtin:demo")
+def gradient(width, height, frames, step_deg, samples, move, no_follow_light, stratum, radius, gain, max_history, passes, max_depth, init_state,
+             init_seq, pfm_output, declare_float, device, input_scene_name):
+    """The last of --frames frames of a camera that turns about z over a world whose --move shapes are translated from frame to
+    frame, as `motion` renders them, with the gradient accumulate query: one probe per block of the frame is gathered again in the
+    PREVIOUS frame's world with this frame's random streams, and where the light changed -- under a shadow that moved -- the history
+    counts for less.  Then the variance-guided filter, then emitted + brdf_color * E.  Writes a PFM."""
+    import math
+
+    import numpy as np
+
+    try:
+        if width < 1 or height < 1:
+            raise UsageError("--width and --height must be at least 1")
+        if frames < 1:
+            raise UsageError("--frames must be at least 1")
+        if not math.isfinite(step_deg):
+            raise UsageError("--step-deg must be finite")
+        if samples < 1:
+            raise UsageError("--samples must be at least 1")
+        if not 1 <= stratum <= 16:
+            raise UsageError("--stratum must be 1 to 16")
+        if not 0 <= radius <= 4:
+            raise UsageError("--radius must be 0 to 4")
+        if not gain >= 0.0:
+            raise UsageError("--gain must not be negative")
+        if not 1 <= max_history <= 2 ** 20:
+            raise UsageError("--max-history must be 1 to 2^20")
+        if not 0 <= passes <= 10:
+            raise UsageError("--passes must be 0 to 10")
+        if max_depth < 0:
+            raise UsageError("--max-depth must not be negative")
+        world, camera, _ = _load_scene(input_scene_name, parse_float_overrides(declare_float), width, height)
+        moves = parse_moves(move, len(world.shapes))
+    except UsageError as e:
+        click.echo(f"pytracer_amd gradient: {e}", err=True)
+        sys.exit(2)
+    from . import _lib, prefer_device_kernargs
+    from .shaders import GradientGatherShader
+
+    prefer_device_kernargs()
+    _lib.standalone()  # (torch-free, like `motion`)
+    image = hm.HdrImage(width, height)
+    tracer = GpuImageTracer(image=image, camera=camera, samples_per_side=0, device=device)
+    shader = GradientGatherShader(world, tracer, samples, init_state=init_state, init_seq=init_seq, max_depth=max_depth, filtered=passes > 0,
+                                  passes=max(passes, 1), max_history=max_history, stratum=stratum, radius=radius, gain=gain)
+    shader.follow_light = not no_follow_light
+    started = perf_counter()
+    for f in range(frames):
+        tracer.camera = scenes.turned_camera(camera, step_deg * f)
+        shader.world = moved_world(world, moves, f)
+        tracer.fire_all_rays(shader)
+    wall = perf_counter() - started
+    with open(pfm_output, "wb") as out:
+        image.write_pfm(out)
+    count, keep = np.asarray(shader.accumulator.count), getattr(shader.accumulator, "keep", None)
+    cut = 0 if keep is None else int((np.asarray(keep) < 1.0).sum())
+    click.echo(f"{width}x{height} px, {len(world.shapes)} shape(s), {len(moves)} moving{'' if shader.follow_light else ' (light not followed)'}, "
+               f"{frames} frame(s) of {samples} ray(s) per pixel, {step_deg:g} degree(s) per frame, longest history {int(count.max())}, "
+               f"mean history {float(count.mean()):.2f}, {cut} pixel(s) kept less than all of theirs, {wall:.3f} s: wrote {pfm_output}")
+    tracer.close()
+
+
 cli.add_command(render)
 cli.add_command(lit)
 cli.add_command(denoise)
@@ -1238,6 +1320,7 @@ cli.add_command(variance)
 cli.add_command(adaptive)
 cli.add_command(weighted)
 cli.add_command(motion)
+cli.add_command(gradient)
 cli.add_command(hits)
 cli.add_command(rays)
 cli.add_command(radiance)

@@ -1201,6 +1201,189 @@ class DeviceScene:
             count.rendered_on(stream)
         return count
 
+    # -- gradient accumulate queries (include/ptrace_gradient.h, libptrace_gradient.so): histories shorten where the light changed ------
+    def gradient_probes(self, shape_index, normal, point, moved, motion, width: int, height: int, stratum: int = 3, phase: int = 0,
+                        samples: int = 1, init_seq: int = 54, device: bool = False, stream=None, out=None, n_shapes=None):
+        """The probes of a ``width x height`` frame (include/ptrace_gradient.h): one per ``stratum x stratum`` block, at the pixel the
+        hash of ``(phase, block)`` picks, carried into the PREVIOUS world by the tables of :meth:`motion` -> ``(probe_index int32[ns],
+        probe_point [ns, 3], probe_normal [ns, 3], probe_seq uint64[ns])``, :func:`pytracer_amd.rays.gradient_probes_host` in every
+        bit.  They are what :meth:`gather` takes as ``active``, ``points``, ``normals`` and ``seqs`` -- on the previous frame's scene,
+        with this frame's ``samples`` and ``init_seq``.  No scene is read.  ``device=True``: the planes and tables are in HBM, the one
+        launch is enqueued on ``stream`` -> four ``DeviceBuffer`` s (``out``: a tuple of four, or new ones), index ``[ns]``, point
+        and normal planar ``[3, ns]``, seq ``[ns]``."""
+        from . import _gradient_lib, rays as rb
+
+        L = _gradient_lib.lib()
+        width, height = _gradient_lib._addon.c_int(width, "width"), _gradient_lib._addon.c_int(height, "height")
+        stratum, samples = _gradient_lib._addon.c_int(stratum, "stratum"), _gradient_lib._addon.c_int(samples, "samples")
+        phase, init_seq = int(phase) & (2 ** 64 - 1), int(init_seq) & (2 ** 64 - 1)
+        m = width * height
+        ns = int(L.pt_rays_gradient_strata(width, height, stratum))
+        if device:
+            from .devmem import DeviceBuffer
+
+            if (moved is None) != (motion is None):
+                raise ValueError("moved and motion come together (or neither: nothing moved)")
+            if n_shapes is None:
+                if moved is None:
+                    n_shapes = 0
+                elif hasattr(moved, "nbytes"):
+                    n_shapes = int(moved.nbytes) // 4
+                elif callable(getattr(moved, "numel", None)):
+                    n_shapes = int(moved.numel())
+                else:
+                    raise ValueError("n_shapes= is needed when the tables are raw device addresses")
+            n_shapes = _gradient_lib._addon.c_int(n_shapes, "n_shapes")
+            handle = getattr(stream, "handle", stream)
+            if out is None:
+                out = (DeviceBuffer((max(ns, 1),), np.int32, self.device), DeviceBuffer((3, max(ns, 1)), np.float64, self.device),
+                       DeviceBuffer((3, max(ns, 1)), np.float64, self.device), DeviceBuffer((max(ns, 1),), np.uint64, self.device))
+            ptr = self._plane_ptr
+            _gradient_lib.check(L.pt_rays_gradient_probes_device(
+                self.device, width, height, stratum, phase, samples, init_seq, ptr(shape_index, "shape_index"), ptr(normal, "normal"),
+                ptr(point, "point"), n_shapes, ptr(moved, "moved"), ptr(motion, "motion"), ptr(out[0], "probe_index"), int(out[0].nbytes),
+                ptr(out[1], "probe_point"), int(out[1].nbytes), ptr(out[2], "probe_normal"), int(out[2].nbytes), ptr(out[3], "probe_seq"),
+                int(out[3].nbytes), C.c_void_p(handle) if handle else None))
+            for buf in out:
+                if hasattr(buf, "rendered_on"):
+                    buf.rendered_on(stream)
+            return out
+        if stream is not None or out is not None or n_shapes is not None:
+            raise ValueError("stream=, out= and n_shapes= go with device=True (host frames are staged and synchronous)")
+        n_shapes, moved, motion = _gradient_lib.tables(moved, motion)
+        sh = np.ascontiguousarray(shape_index, dtype=np.int32).reshape(-1)
+        planes = [rb.planar(a, 3) for a in (normal, point)]
+        if sh.shape[0] != m or any(p.shape[1] != m for p in planes):
+            raise ValueError(f"a {width} x {height} frame has {m} records, not {sh.shape[0]} shape indices and {[p.shape[1] for p in planes]} "
+                             "normals and points")
+        index, pts, nrm, seq = np.empty(ns, np.int32), np.empty((3, ns)), np.empty((3, ns)), np.empty(ns, np.uint64)
+        p = lambda a: a.ctypes.data_as(C.c_void_p) if a is not None else None  # noqa: E731
+        _gradient_lib.check(L.pt_rays_gradient_probes(self.device, width, height, stratum, phase, samples, init_seq, p(sh), p(planes[0]),
+                                                      p(planes[1]), n_shapes, p(moved), p(motion), p(index), index.nbytes, p(pts), pts.nbytes,
+                                                      p(nrm), nrm.nbytes, p(seq), seq.nbytes))
+        return index, np.ascontiguousarray(pts.T), np.ascontiguousarray(nrm.T), seq
+
+    def gradient_keep(self, colour, shape_index, probe_index, probe_old, width: int, height: int, device: bool = False, stream=None, out=None,
+                      **params):
+        """The share of its history every pixel of a ``width x height`` frame keeps (include/ptrace_gradient.h): from this frame's
+        ``colour`` at the probes' pixels and ``probe_old``, the probes' gather in the previous world, over the ``(2 radius + 1)^2``
+        strata around the pixel.  ``params``: ``stratum``, ``radius``, ``gain``, ``same_shape_probes`` -> ``keep [height, width]``
+        float64 in [0, 1], :func:`pytracer_amd.rays.gradient_keep_host` in every bit.  No scene is read.  ``device=True``: the planes
+        are in HBM (``colour`` and ``probe_old`` planar), the one launch is enqueued on ``stream`` -> the output ``DeviceBuffer``."""
+        from . import _gradient_lib, rays as rb
+
+        L, par = _gradient_lib.lib(), _gradient_lib.params(**params)
+        width, height = _gradient_lib._addon.c_int(width, "width"), _gradient_lib._addon.c_int(height, "height")
+        m = width * height
+        if device:
+            from .devmem import DeviceBuffer
+
+            handle = getattr(stream, "handle", stream)
+            if out is None:
+                out = DeviceBuffer((max(m, 1),), np.float64, self.device)
+            ptr = self._plane_ptr
+            _gradient_lib.check(L.pt_rays_gradient_keep_device(self.device, width, height, C.byref(par), ptr(colour, "colour"),
+                                                               ptr(shape_index, "shape_index"), ptr(probe_index, "probe_index"),
+                                                               ptr(probe_old, "probe_old"), ptr(out, "out"), int(out.nbytes),
+                                                               C.c_void_p(handle) if handle else None))
+            if hasattr(out, "rendered_on"):
+                out.rendered_on(stream)
+            return out
+        if stream is not None or out is not None:
+            raise ValueError("stream= and out= go with device=True (host frames are staged and synchronous)")
+        ns = int(L.pt_rays_gradient_strata(width, height, par.stratum))
+        sh = np.ascontiguousarray(shape_index, dtype=np.int32).reshape(-1)
+        index = np.ascontiguousarray(probe_index, dtype=np.int32).reshape(-1)
+        col, old = rb.planar(colour, 3), rb.planar(probe_old, 3)
+        if sh.shape[0] != m or col.shape[1] != m or (1 <= par.stratum <= _gradient_lib.MAX_STRATUM and (index.shape[0] != ns or old.shape[1] != ns)):
+            raise ValueError(f"a {width} x {height} frame has {m} records and {ns} probes, not {sh.shape[0]} shape indices, {col.shape[1]} colours, "
+                             f"{index.shape[0]} probe indices and {old.shape[1]} old colours")
+        keep = np.empty(m, np.float64)
+        p = lambda a: a.ctypes.data_as(C.c_void_p) if a is not None else None  # noqa: E731
+        _gradient_lib.check(L.pt_rays_gradient_keep(self.device, width, height, C.byref(par), p(col), p(sh), p(index), p(old), p(keep), keep.nbytes))
+        return keep.reshape(height, width)
+
+    def gradient_accumulate(self, colour, samples, shape_index, normal, point, prev_colour, prev_moments, prev_shape, prev_normal, prev_point,
+                            prev_count, prev_camera, moved, motion, keep, width: int, height: int, device: bool = False, stream=None, out=None,
+                            out_moments=None, out_count=None, n_shapes=None, **params):
+        """:meth:`motion` with one more plane (include/ptrace_gradient.h): ``keep`` (float64 per record, :meth:`gradient_keep`'s
+        output; ``None``: everything is kept and every bit is :meth:`motion`'s), clamped to [0, 1], multiplies the weight of the
+        reprojected history and, under a floor, its length, before this frame's samples are blended in.  Everything else as
+        :meth:`motion` takes and returns it; :func:`pytracer_amd.rays.gradient_accumulate_host` in every bit.  No scene is read."""
+        from . import _gradient_lib, rays as rb
+
+        L, par, cam = _gradient_lib.lib(), _gradient_lib.history(**params), _gradient_lib.camera(prev_camera)
+        width, height = _gradient_lib._addon.c_int(width, "width"), _gradient_lib._addon.c_int(height, "height")
+        m = width * height
+        if device:
+            from .devmem import DeviceBuffer
+
+            if (moved is None) != (motion is None):
+                raise ValueError("moved and motion come together (or neither: nothing moved)")
+            if n_shapes is None:
+                if moved is None:
+                    n_shapes = 0
+                elif hasattr(moved, "nbytes"):
+                    n_shapes = int(moved.nbytes) // 4
+                elif callable(getattr(moved, "numel", None)):
+                    n_shapes = int(moved.numel())
+                else:
+                    raise ValueError("n_shapes= is needed when the tables are raw device addresses")
+            n_shapes = _gradient_lib._addon.c_int(n_shapes, "n_shapes")
+            handle = getattr(stream, "handle", stream)
+            if out is None:
+                out = DeviceBuffer((3, max(m, 1)), np.float64, self.device)
+            if out_moments is None:
+                out_moments = DeviceBuffer((3, max(m, 1)), np.float64, self.device)
+            if out_count is None:
+                out_count = DeviceBuffer((max(m, 1),), np.int32, self.device)
+            ptr = self._plane_ptr
+            _gradient_lib.check(L.pt_rays_gradient_accumulate_device(
+                self.device, width, height, C.byref(par), C.byref(cam), ptr(colour, "colour"), ptr(samples, "samples"),
+                ptr(shape_index, "shape_index"), ptr(normal, "normal"), ptr(point, "point"), ptr(prev_colour, "prev_colour"),
+                ptr(prev_moments, "prev_moments"), ptr(prev_shape, "prev_shape"), ptr(prev_normal, "prev_normal"), ptr(prev_point, "prev_point"),
+                ptr(prev_count, "prev_count"), n_shapes, ptr(moved, "moved"), ptr(motion, "motion"), ptr(keep, "keep"), ptr(out, "out"),
+                int(out.nbytes), ptr(out_moments, "out_moments"), int(out_moments.nbytes), ptr(out_count, "out_count"), int(out_count.nbytes),
+                C.c_void_p(handle) if handle else None))
+            for buf in (out, out_moments, out_count):
+                if hasattr(buf, "rendered_on"):
+                    buf.rendered_on(stream)
+            return out, out_moments, out_count
+        if stream is not None or out is not None or out_moments is not None or out_count is not None or n_shapes is not None:
+            raise ValueError("stream=, out=, out_moments=, out_count= and n_shapes= go with device=True (host frames are staged and synchronous)")
+        n_shapes, moved, motion = _gradient_lib.tables(moved, motion)
+        ints = [np.ascontiguousarray(a, dtype=np.int32).reshape(-1) for a in (shape_index, prev_shape, prev_count)]
+        taken = None if samples is None else np.ascontiguousarray(samples, dtype=np.int32).reshape(-1)
+        kept = None if keep is None else np.ascontiguousarray(keep, dtype=np.float64).reshape(-1)
+        planes = [rb.planar(a, 3) for a in (colour, normal, point, prev_colour, prev_moments, prev_normal, prev_point)]
+        if (any(a.shape[0] != m for a in ints) or any(p.shape[1] != m for p in planes) or (taken is not None and taken.shape[0] != m)
+                or (kept is not None and kept.shape[0] != m)):
+            raise ValueError(f"a {width} x {height} frame has {m} records, not {[a.shape[0] for a in ints]} shape indices and counts, "
+                             f"{None if taken is None else taken.shape[0]} sample counts, {None if kept is None else kept.shape[0]} keep values "
+                             f"and {[p.shape[1] for p in planes]} colours, normals, points and moments")
+        buf, mom, cnt = np.empty((3, m), dtype=np.float64), np.empty((3, m), dtype=np.float64), np.empty((m,), dtype=np.int32)
+        p = lambda a: a.ctypes.data_as(C.c_void_p) if a is not None else None  # noqa: E731
+        _gradient_lib.check(L.pt_rays_gradient_accumulate(self.device, width, height, C.byref(par), C.byref(cam), p(planes[0]), p(taken), p(ints[0]),
+                                                          p(planes[1]), p(planes[2]), p(planes[3]), p(planes[4]), p(ints[1]), p(planes[5]),
+                                                          p(planes[6]), p(ints[2]), n_shapes, p(moved), p(motion), p(kept), p(buf), buf.nbytes,
+                                                          p(mom), mom.nbytes, p(cnt), cnt.nbytes))
+        return (np.ascontiguousarray(buf.T).reshape(height, width, 3), np.ascontiguousarray(mom.T).reshape(height, width, 3),
+                cnt.reshape(height, width))
+
+    def gradient_clear(self, count, m=None, stream=None):
+        """An empty history: the ``m`` int32 lengths of the device buffer ``count`` (default: all it holds) become 0 on ``stream``
+        (``pt_rays_gradient_clear_device``) -> ``count``.  With lengths of 0 no colour, moment or weight of the history is read."""
+        from . import _gradient_lib
+
+        handle = getattr(stream, "handle", stream)
+        m = self._device_count(count, m)
+        nbytes = int(count.nbytes) if hasattr(count, "nbytes") else 4 * m
+        _gradient_lib.check(_gradient_lib.lib().pt_rays_gradient_clear_device(self.device, m, self._plane_ptr(count, "count"), nbytes,
+                                                                              C.c_void_p(handle) if handle else None))
+        if hasattr(count, "rendered_on"):
+            count.rendered_on(stream)
+        return count
+
     # -- variance queries (include/ptrace_variance.h, libptrace_variance.so): moments, a per-pixel variance and a filter guided by it --
     @staticmethod
     def _variance_frame(width, height):

@@ -1121,12 +1121,14 @@ def luminance_moments_host(colour, shape, width: int, height: int) -> np.ndarray
 # ---- the mirror of the weighted accumulate query (include/ptrace_weighted.h) ------------------------------------------------------------
 def weighted_host(colour, samples, shape, normal, point, prev_colour, prev_moments, prev_shape, prev_normal, prev_point, prev_count, prev_camera,
                   width: int, height: int, max_history: int = 32, same_shape: bool = True, blend_weight: bool = False, normal_min: float = 0.9,
-                  point_tolerance: float = 0.05, max_weight: float = 128.0):
+                  point_tolerance: float = 0.05, max_weight: float = 128.0, keep=None):
     """The numpy mirror of the weighted accumulate query (include/ptrace_weighted.h), operation for operation: the projection and
     the four taps of :func:`temporal_host`, in its order, for the colour, the luminance moments and the weight at once.  The planes
     as :func:`temporal_host` takes them, plus ``samples`` (int32 per record, or ``None``: one everywhere) and ``prev_moments``
     (``[..., 3]``: M1, M2 and the accumulated weight S) -> ``(out [height, width, 3] float64, moments [height, width, 3] float64,
-    count [height, width] int32)``.  Refuses what the library refuses, with a ``ValueError``."""
+    count [height, width] int32)``.  Refuses what the library refuses, with a ``ValueError``.  ``keep`` (float64 per record, or
+    ``None``) is not part of that query: it is the one insertion of include/ptrace_gradient.h into step 5, which
+    :func:`gradient_accumulate_host` passes; with ``None`` nothing here differs from what it was."""
     W, H, max_history = int(width), int(height), int(max_history)
     normal_min, point_tolerance, max_weight = float(normal_min), float(point_tolerance), float(max_weight)
     if W < 0 or H < 0 or W * H > MAX_RAYS:
@@ -1190,6 +1192,12 @@ def weighted_host(colour, samples, shape, normal, point, prev_colour, prev_momen
         Sh = hm[..., 2] / ws if blend_weight else smax
         Sh = np.where(Sh > 0.0, Sh, 0.0)
         Sh = np.where(Sh > max_weight, max_weight, Sh)
+        if keep is not None:  # (include/ptrace_gradient.h: the history's weight and length shrink where the light changed)
+            kp = np.asarray(keep, dtype=np.float64).reshape(H, W)
+            kp = np.where(kp >= 0.0, kp, 0.0)
+            kp = np.where(kp > 1.0, 1.0, kp)
+            Sh = kp * Sh
+            nmax = np.floor(kp * nmax.astype(np.float64)).astype(np.int64)
         total = Sh + kd
         alpha = kd / total
         blended = hist + (cur - hist) * alpha[..., None]
@@ -1286,6 +1294,119 @@ def motion_host(colour, samples, shape, normal, point, prev_colour, prev_moments
     nm, pm = move_records_host(shape, normal, point, moved, motion)
     return weighted_host(colour, samples, shape, nm, pm, prev_colour, prev_moments, prev_shape, prev_normal, prev_point, prev_count, prev_camera,
                          width, height, **params)
+
+
+# ---- the mirrors of the gradient accumulate query (include/ptrace_gradient.h) ----------------------------------------------------------
+_U64 = (1 << 64) - 1
+
+
+def gradient_probe_offsets(phase: int, strata: int):
+    """The hash of include/ptrace_gradient.h for the strata ``0 .. strata - 1`` of frame ``phase`` -> the uint64 ``x`` after its last
+    step, of which ``x & 0xffff`` and ``(x >> 16) & 0xffff`` place the probe in its stratum."""
+    with np.errstate(over="ignore"):
+        j = np.arange(int(strata), dtype=np.uint64)
+        x = np.uint64((int(phase) * 0x9E3779B97F4A7C15 + 0x2545F4914F6CDD1D) & _U64) + j * np.uint64(0xD1B54A32D192ED03)
+        for _ in range(2):
+            x = x ^ (x >> np.uint64(32))
+            x = x * np.uint64(0xD6E8FEB86659FD93)
+        return x ^ (x >> np.uint64(32))
+
+
+def gradient_probes_host(shape, normal, point, moved, motion, width: int, height: int, stratum: int = 3, phase: int = 0, samples: int = 1,
+                         init_seq: int = 54):
+    """The numpy mirror of the probes query (include/ptrace_gradient.h), operation for operation: one probe per ``stratum x stratum``
+    block of the frame, at the pixel the hash of ``(phase, stratum index)`` picks, carried into the previous world by
+    :func:`move_records_host` -> ``(probe_index int32[ns], probe_point [ns, 3], probe_normal [ns, 3], probe_seq uint64[ns])``; a probe
+    on a miss has index -1 and zeros.  Refuses what the library refuses, with a ``ValueError``."""
+    from . import _gradient_lib
+
+    W, H, s, K = int(width), int(height), int(stratum), int(samples)
+    ns = _gradient_lib.strata(W, H, s)
+    if K < 1:
+        raise ValueError(f"samples={K}: at least 1")
+    _motion_tables(moved, motion)
+    if W * H == 0:
+        return np.zeros(0, np.int32), np.zeros((0, 3)), np.zeros((0, 3)), np.zeros(0, np.uint64)
+    sh = np.asarray(shape, dtype=np.int32).reshape(-1)
+    gw = (W + s - 1) // s
+    j = np.arange(ns, dtype=np.int64)
+    sy, sx = j // gw, j % gw
+    sw, shh = np.minimum(s, W - sx * s), np.minimum(s, H - sy * s)
+    x = gradient_probe_offsets(phase, ns)
+    ox = ((x & np.uint64(0xffff)) % sw.astype(np.uint64)).astype(np.int64)
+    oy = (((x >> np.uint64(16)) & np.uint64(0xffff)) % shh.astype(np.uint64)).astype(np.int64)
+    r = (sy * s + oy) * W + sx * s + ox
+    nm, pm = move_records_host(sh[r], np.asarray(normal, dtype=np.float64).reshape(-1, 3)[r], np.asarray(point, dtype=np.float64).reshape(-1, 3)[r],
+                               moved, motion)
+    hit = sh[r] >= 0
+    with np.errstate(over="ignore"):
+        seq = np.uint64(int(init_seq) & _U64) + r.astype(np.uint64) * np.uint64(K & _U64)
+    return (np.where(hit, r, -1).astype(np.int32), np.where(hit[:, None], pm, 0.0), np.where(hit[:, None], nm, 0.0),
+            np.where(hit, seq, np.uint64(0)))
+
+
+def gradient_keep_host(colour, shape, probe_index, probe_old, width: int, height: int, stratum: int = 3, radius: int = 1, gain: float = 8.0,
+                       same_shape_probes: bool = True) -> np.ndarray:
+    """The numpy mirror of the keep query (include/ptrace_gradient.h), operation for operation: per pixel the sums of ``|lc - lo|`` and
+    of ``max(lc, lo)`` over the probes of the ``(2 radius + 1)^2`` strata around it, ``dy`` then ``dx``, and ``1 - clamp(gain * num /
+    den)`` -> ``keep [height, width]`` float64.  A probe index outside ``[0, m)`` is skipped and nothing is read there.  Refuses what
+    the library refuses, with a ``ValueError``."""
+    from . import _gradient_lib
+
+    W, H, s, R, gain = int(width), int(height), int(stratum), int(radius), float(gain)
+    ns = _gradient_lib.strata(W, H, s)
+    if not 0 <= R <= _gradient_lib.MAX_RADIUS:
+        raise ValueError(f"radius={R}: 0 to 4")
+    if not gain >= 0.0:
+        raise ValueError(f"gain={gain}: not negative (or inf)")
+    m = W * H
+    if m == 0:
+        return np.ones((H, W))
+    col = np.asarray(colour, dtype=np.float64).reshape(m, 3)
+    sh = np.asarray(shape, dtype=np.int32).reshape(m)
+    idx = np.asarray(probe_index, dtype=np.int32).reshape(-1).astype(np.int64)
+    old = np.asarray(probe_old, dtype=np.float64).reshape(-1, 3)
+    if idx.shape[0] != ns or old.shape[0] != ns:
+        raise ValueError(f"a {W} x {H} frame in strata of {s} has {ns} probes, not {idx.shape[0]} indices and {old.shape[0]} old colours")
+    gw, gh = (W + s - 1) // s, (H + s - 1) // s
+    ys, xs = np.divmod(np.arange(m, dtype=np.int64), W)
+    gx, gy = xs // s, ys // s
+    vouched = (idx >= 0) & (idx < m)
+    q_of = np.where(vouched, idx, 0)
+    with np.errstate(all="ignore"):
+        lc_of, lo_of = _luminance(col[q_of]), _luminance(old)
+        d_of = lc_of - lo_of
+        d_of = np.where(d_of < 0.0, 0.0 - d_of, d_of)
+        mx_of = np.where(lc_of > lo_of, lc_of, lo_of)
+        num, den = np.zeros(m), np.zeros(m)
+        for dy in range(-R, R + 1):
+            for dx in range(-R, R + 1):
+                tx, ty = gx + dx, gy + dy
+                inside = (tx >= 0) & (tx < gw) & (ty >= 0) & (ty < gh)
+                j = np.where(inside, ty * gw + tx, 0)
+                take = inside & vouched[j]
+                if same_shape_probes:
+                    take = take & (sh[q_of[j]] == sh)
+                num = np.where(take, num + d_of[j], num)
+                den = np.where(take, den + mx_of[j], den)
+        lam = gain * (num / den)
+        lam = np.where(lam > 0.0, lam, 0.0)
+        lam = np.where(lam > 1.0, 1.0, lam)
+        keep = 1.0 - lam
+    return np.where(sh >= 0, keep, 1.0).reshape(H, W)
+
+
+def gradient_accumulate_host(colour, samples, shape, normal, point, prev_colour, prev_moments, prev_shape, prev_normal, prev_point, prev_count,
+                             prev_camera, moved, motion, keep, width: int, height: int, **params):
+    """The numpy mirror of the gradient accumulate query (include/ptrace_gradient.h), operation for operation: :func:`motion_host`
+    with the one insertion into step 5 -- ``keep`` (float64 per record) clamped to [0, 1] multiplies the history's weight ``Sh`` and,
+    under a floor, its length ``nmax``; ``None``: :func:`motion_host` in every bit (contract E) -> ``(out [height, width, 3],
+    moments [height, width, 3], count [height, width] int32)``."""
+    if keep is not None and np.asarray(keep).size != int(width) * int(height):
+        raise ValueError(f"a {width} x {height} frame has {int(width) * int(height)} records, not {np.asarray(keep).size} keep values")
+    nm, pm = move_records_host(shape, normal, point, moved, motion)
+    return weighted_host(colour, samples, shape, nm, pm, prev_colour, prev_moments, prev_shape, prev_normal, prev_point, prev_count, prev_camera,
+                         width, height, keep=keep, **params)
 
 
 def _wrapped_columns(cols, offset, W, wrap_x):
@@ -1880,6 +2001,36 @@ class WorldQueries:
                                                 table, width, height, **params)
         return WeightedHistory(out, index, normals, points, count, moments)
 
+    def accumulated_gradient(self, values, samples, hits, prev: "WeightedHistory", prev_camera, motion, keep, **params) -> "WeightedHistory":
+        """:meth:`accumulated_moving` with the share of its history every pixel keeps -- on the device
+        (``DeviceScene.gradient_accumulate``), :func:`gradient_accumulate_host` in every bit.  ``keep``: ``[H, W]`` float64 as
+        ``DeviceScene.gradient_keep`` returns it (1: the light did not change, 0: the history counts for nothing), or ``None``:
+        :meth:`accumulated_moving` in every bit."""
+        v, index, normals, points, width, height = _one_record_frame(values, hits, "the accumulation")
+        index = np.ascontiguousarray(index, dtype=np.int32).reshape(height, width)
+        normals = np.asarray(normals, dtype=np.float64).reshape(height, width, 3)
+        points = np.asarray(points, dtype=np.float64).reshape(height, width, 3)
+        if np.asarray(prev.count).shape != (height, width):
+            raise ValueError(f"a history of {np.asarray(prev.count).shape} for a frame of {height} x {width}")
+        if samples is not None:
+            samples = np.asarray(samples)
+            if samples.size != height * width:
+                raise ValueError(f"{samples.size} sample counts for a frame of {height} x {width}")
+            samples = samples.reshape(-1)
+        if keep is not None:
+            keep = np.asarray(keep, dtype=np.float64)
+            if keep.size != height * width:
+                raise ValueError(f"{keep.size} keep values for a frame of {height} x {width}")
+            keep = keep.reshape(-1)
+        moved, table = (None, None) if motion is None else motion
+        out, moments, count = self.scene.gradient_accumulate(v.reshape(-1, 3), samples, index.reshape(-1), normals.reshape(-1, 3),
+                                                             points.reshape(-1, 3), np.asarray(prev.colour).reshape(-1, 3),
+                                                             np.asarray(prev.moments).reshape(-1, 3), np.asarray(prev.shape_index).reshape(-1),
+                                                             np.asarray(prev.normal).reshape(-1, 3), np.asarray(prev.point).reshape(-1, 3),
+                                                             np.asarray(prev.count).reshape(-1), prev_camera, moved, table, keep, width, height,
+                                                             **params)
+        return WeightedHistory(out, index, normals, points, count, moments)
+
     def variance_filtered(self, values, hits, variance=None, count=None, **params):
         """``values`` filtered by the variance-guided a-trous filter of include/ptrace_variance.h, guided by ``hits`` -- on the
         device (``DeviceScene.variance_filter``), :func:`variance_filter_host` in every bit.  ``values`` and ``hits``: as
@@ -2344,5 +2495,130 @@ class MotionAccumulator(WeightedAccumulator):
         self._prev, self._camera, self.count, self.moments = hits, cam, out_count, out_moments
         self.weight = int(out_moments.data_ptr()) + 16 * m  # (plane 2 of [3, m] fp64)
         self._world = None if world is None else _snapshot(world)
+        self.frames += 1
+        return out, out_variance
+
+
+# ---- accumulation that also follows the light (include/ptrace_gradient.h) ------------------------------------------------------------
+class GradientAccumulator(MotionAccumulator):
+    """:class:`MotionAccumulator` on the gradient accumulate query (include/ptrace_gradient.h): the history of a pixel shortens where
+    the LIGHT changed -- under a shadow that moved, in the reflection of a shape that did.  ``update(values, hits, camera,
+    samples=None, world=None, motion=None, queries=None, probe=None)`` returns ``(accumulated E, variance)``.  From the second frame
+    on, with ``probe=``, it makes FIVE launches: ``DeviceScene.gradient_probes`` picks one pixel per stratum of this frame and carries
+    it into the previous world; ``DeviceScene.gather`` ON THE PREVIOUS FRAME'S SCENE gathers there with this frame's streams, so that
+    what differs from this frame's ``values`` at those pixels is what the world's change did, free of sampling noise;
+    ``DeviceScene.gradient_keep`` spreads that over the frame; ``DeviceScene.gradient_accumulate`` is the motion accumulate query with
+    the history's weight and length multiplied by it; ``DeviceScene.variance_estimate`` as before.
+
+    ``probe=``: how ``values`` was gathered -- ``dict(samples=K, init_state=42, init_seq=54, num_of_rays=1, max_depth=10,
+    russian_roulette_limit=3, background=(0, 0, 0), depth=0)``, the arguments of ``DeviceScene.gather`` for THIS frame (a uniform
+    gather: record ``i`` has the streams ``init_seq + i * K ..``; adaptive and ragged counts stay out) -- and optionally ``queries=``,
+    a ``WorldQueries`` on the previous world's scene when the one the accumulator kept from the previous ``update`` has been closed.
+    With no ``probe=``, or on a first frame, every bit is :class:`MotionAccumulator`'s.  The PREVIOUS frame's device scene must stay
+    open until this frame's ``update`` has enqueued its gather (``device=True``: until that gather has run).
+
+    ``params``: :class:`MotionAccumulator`'s, and ``stratum`` (1..16), ``radius`` (0..4), ``gain`` and ``same_shape_probes``.  ``keep``
+    holds the last keep plane (``[H, W]``, or the ``DeviceBuffer``; ``None`` when the last update made none).  ``device=True`` keeps
+    every plane in HBM on the one stream, with the buffer lifetimes of :class:`WeightedAccumulator`; the probe planes and the keep
+    plane alternate between two sets like the outputs.  Shapes that ROTATE give their probes a turned normal, hence other sample
+    directions: their gradient contains sampling noise."""
+
+    KEEP_KEYS = ("stratum", "radius", "gain", "same_shape_probes")
+    PROBE_KEYS = ("samples", "init_state", "init_seq", "num_of_rays", "max_depth", "russian_roulette_limit", "background", "depth", "queries")
+
+    def __init__(self, queries, device: bool = False, stream=None, static=(), **params):
+        from . import _gradient_lib
+
+        self.keep_params = dict(_gradient_lib.KEEP_DEFAULTS)
+        self.keep_params.update({k: params.pop(k) for k in self.KEEP_KEYS if k in params})
+        self._prev_queries, self._probe_buffers, self.keep = None, [None, None], None
+        try:
+            super().__init__(queries, device, stream, static, **params)
+        except TypeError as e:
+            raise TypeError(str(e).replace("MotionAccumulator", "GradientAccumulator")) from None
+
+    def reset(self) -> None:
+        """Forget the history, the previous world and its scene: the next ``update`` starts a sequence."""
+        super().reset()
+        self._prev_queries, self.keep = None, None
+
+    def update(self, values, hits, camera, samples=None, world=None, motion=None, queries=None, probe=None, width=None, height=None):
+        from . import _gradient_lib
+
+        if probe is not None:
+            unknown = set(probe) - set(self.PROBE_KEYS)
+            if unknown or "samples" not in probe:
+                raise TypeError(f"GradientAccumulator: probe= takes samples= and any of {self.PROBE_KEYS[1:]}, not {sorted(unknown)}")
+        before = self._prev_queries if probe is None or probe.get("queries") is None else probe["queries"]
+        first = self._prev is None or (self.device and (self._buffers is None or self._m != int(width or 0) * int(height or 0)))
+        if probe is None or first or before is None:  # (nothing to compare with: the motion query, bit for bit)
+            result = super().update(values, hits, camera, samples=samples, world=world, motion=motion, queries=queries, width=width, height=height)
+            self._prev_queries, self.keep = self.queries, None
+            return result
+        if queries is not None:
+            self.queries = queries
+        if world is not None and motion is not None:
+            raise ValueError("world= (the accumulator derives the motion) or motion= (a table of the caller's), not both")
+        if world is not None and self._world is not None:
+            motion = shape_motion(self._world, world, self.static)
+        scene = self.queries.scene
+        cam = _gradient_lib.GradientCamera.from_buffer_copy(_gradient_lib.camera(camera))  # (the caller's camera may move on)
+        K = int(probe["samples"])
+        init_seq = int(probe.get("init_seq", 54))
+        gather = dict(init_state=probe.get("init_state", 42), num_of_rays=probe.get("num_of_rays", 1), max_depth=probe.get("max_depth", 10),
+                      russian_roulette_limit=probe.get("russian_roulette_limit", 3), background=probe.get("background", (0.0, 0.0, 0.0)),
+                      depth=probe.get("depth", 0), channels="none")
+        spread = {k: v for k, v in self.keep_params.items() if k != "stratum"}
+        stratum = self.keep_params["stratum"]
+        moved, table = (None, None) if motion is None else motion
+        if not self.device:
+            if width is not None or height is not None:
+                raise ValueError("width= and height= go with device=True (a host frame brings its own)")
+            v, index, normals, points, w, h = _one_record_frame(values, hits, "the accumulation")
+            index = np.ascontiguousarray(index, dtype=np.int32).reshape(-1)
+            normals, points = np.asarray(normals, dtype=np.float64).reshape(-1, 3), np.asarray(points, dtype=np.float64).reshape(-1, 3)
+            at, where, facing, seqs = scene.gradient_probes(index, normals, points, moved, table, w, h, stratum=stratum, phase=self.frames,
+                                                            samples=K, init_seq=init_seq)
+            old = before.scene.gather(planar(where, 3), planar(facing, 3), K, seqs=seqs, active=at, **gather).radiance
+            keep = scene.gradient_keep(v.reshape(-1, 3), index, at, old, w, h, stratum=stratum, **spread)
+            new = self.queries.accumulated_gradient(values, samples, hits, self._prev, self._camera, motion, keep, **self.history_params)
+            variance = scene.variance_estimate(np.asarray(new.moments).reshape(-1, 3), np.asarray(new.count).reshape(-1),
+                                               new.shape_index.reshape(-1), new.normal.reshape(-1, 3), new.point.reshape(-1, 3), w, h,
+                                               **self.estimate_params)
+            self._prev, self._camera, self.count, self.moments = new, cam, new.count, new.moments
+            self.weight = np.asarray(new.moments)[..., 2]
+            self._world = None if world is None else _snapshot(world)
+            self._prev_queries, self.keep = self.queries, keep
+            self.frames += 1
+            return new.colour, variance
+        if not isinstance(hits, DeviceGuides):
+            raise TypeError(f"device=True takes hits as a DeviceGuides, not {type(hits).__name__}")
+        m = int(width) * int(height)
+        out, out_moments, out_count, out_variance = self._buffers[self.frames & 1]
+        prev_colour, prev_moments, prev_count, _ = self._buffers[(self.frames & 1) ^ 1]
+        prev, prev_camera = self._prev, self._camera
+        if set(prev.addresses()) & set(hits.addresses()):
+            raise ValueError("this frame's guides lie where the previous frame's did: alternate two hit buffers")
+        moved_dev, motion_dev = (None, None) if motion is None else scene.motion_table(*motion)
+        self._tables[self.frames & 1] = (moved_dev, motion_dev)  # (held while the launches that read them may be in flight)
+        ns = _gradient_lib.strata(width, height, stratum)
+        held = self._probe_buffers[self.frames & 1]
+        probes = scene.gradient_probes(hits.shape_index, hits.normal, hits.point, moved_dev, motion_dev, width, height, stratum=stratum,
+                                       phase=self.frames, samples=K, init_seq=init_seq, device=True, stream=self.stream,
+                                       out=None if held is None or held["ns"] != ns else held["probes"])
+        old = before.scene.gather(probes[1], probes[2], K, seqs=probes[3], active=probes[0], device=True, stream=self.stream, n=ns,
+                                  out=None if held is None or held["ns"] != ns else held["old"], **gather)
+        keep = scene.gradient_keep(values, hits.shape_index, probes[0], old, width, height, stratum=stratum, device=True, stream=self.stream,
+                                   out=None if held is None or held["m"] != m else held["keep"], **spread)
+        self._probe_buffers[self.frames & 1] = dict(ns=ns, m=m, probes=probes, old=old, keep=keep)
+        scene.gradient_accumulate(values, samples, hits.shape_index, hits.normal, hits.point, prev_colour, prev_moments, prev.shape_index,
+                                  prev.normal, prev.point, prev_count, prev_camera, moved_dev, motion_dev, keep, width, height, device=True,
+                                  stream=self.stream, out=out, out_moments=out_moments, out_count=out_count, **self.history_params)
+        scene.variance_estimate(out_moments, out_count, hits.shape_index, hits.normal, hits.point, width, height, device=True, stream=self.stream,
+                                out=out_variance, **self.estimate_params)
+        self._prev, self._camera, self.count, self.moments = hits, cam, out_count, out_moments
+        self.weight = int(out_moments.data_ptr()) + 16 * m  # (plane 2 of [3, m] fp64)
+        self._world = None if world is None else _snapshot(world)
+        self._prev_queries, self.keep = self.queries, keep
         self.frames += 1
         return out, out_variance

@@ -880,6 +880,90 @@ class MovingWorldGatherShader(VarianceGuidedGatherShader):
         return np.where(np.asarray(mat.hit)[..., None], lit, self._background(frame))
 
 
+class GradientGatherShader(MovingWorldGatherShader):
+    """:class:`MovingWorldGatherShader` on a ``rays.GradientAccumulator`` (include/ptrace_gradient.h): besides following the shapes
+    that moved, the history of a pixel shortens where the LIGHT changed -- under the shadow of a shape that moved, in its reflection.
+    Per frame after the first: one probe per stratum of this frame, gathered in the PREVIOUS world with this frame's streams, says
+    how much of ``E`` changed because the world did, free of sampling noise; the accumulation keeps that much less of the history.
+    On a static world every bit is :class:`MovingWorldGatherShader`'s.
+
+    The tracer drops the previous world's device scene when it opens this frame's, so the shader keeps a copy of the previous world's
+    shapes, opens a device scene of its own for the probes' gather and closes it before the frame is done.
+
+    ``params``: :class:`MovingWorldGatherShader`'s, and ``stratum``, ``radius``, ``gain`` and ``same_shape_probes``.  ``follow_light =
+    False`` (an attribute, set before the first frame) is the parent, for comparison; ``follow = False`` the grandparent.  Shapes that
+    ROTATE give their probes a turned normal and hence other sample directions: their gradient contains sampling noise."""
+
+    HISTORY_KEYS = MovingWorldGatherShader.HISTORY_KEYS + ("stratum", "radius", "gain", "same_shape_probes")
+
+    def __init__(self, world, tracer=None, samples: int = 4, background_color: Color = BLACK, init_state: int = 42, init_seq: int = 54,
+                 max_depth: int = 10, russian_roulette_limit: int = 3, filtered: bool = True, pcg=None, accumulate: bool = True, static=(),
+                 **params):
+        try:
+            super().__init__(world, tracer, samples, background_color, init_state, init_seq, max_depth, russian_roulette_limit, filtered, pcg,
+                             accumulate, static, **params)
+        except TypeError as e:
+            raise TypeError(str(e).replace("MovingWorldGatherShader", "GradientGatherShader")) from None
+        self.follow_light, self._before = True, None
+
+    def reset(self) -> None:
+        super().reset()
+        self._before = None
+
+    def shade_hits(self, frame) -> np.ndarray:
+        import copy
+
+        from . import flatten
+        from .device import DeviceScene
+        from .rays import GradientAccumulator, WorldQueries
+
+        keep_keys = GradientAccumulator.KEEP_KEYS
+        if not (self.follow_light and self.follow and self.accumulate):
+            held = self.history_params
+            self.history_params = {k: v for k, v in held.items() if k not in keep_keys}
+            try:
+                return super().shade_hits(frame)
+            finally:
+                self.history_params = held
+        if self.tracer is None:
+            raise TypeError("GradientGatherShader.shade_hits needs the tracer whose device scene holds the world: "
+                            "GradientGatherShader(world, tracer, ...)")
+        index = np.asarray(frame.shape_index)
+        if index.ndim != 3 or index.shape[0] != 1:
+            raise ValueError(f"GradientGatherShader keeps one record per pixel, not a frame of {index.shape}: build the tracer with "
+                             "samples_per_side=0 or 1")
+        q = self.tracer.world_queries(self.world)
+        seq = self.init_seq + self.frame_no * (index.shape[1] * index.shape[2]) * self.samples
+        gathered = q.hemisphere_radiance(frame, self.samples, self.init_state, None, 1, self.max_depth, self.russian_roulette_limit,
+                                         self.background_color, 1, "none", init_seq=seq)
+        self.last_gather = gathered
+        e = np.asarray(gathered.radiance)[0]
+        taken = np.where(index[0] >= 0, self.samples, 0).astype(np.int32)
+        if self.accumulator is None:
+            self.accumulator = GradientAccumulator(q, static=self.static, **self.history_params)
+        probe = dict(samples=self.samples, init_state=self.init_state, init_seq=seq, max_depth=self.max_depth,
+                     russian_roulette_limit=self.russian_roulette_limit, background=self.background_color, depth=1)
+        old_scene = None
+        if self._before is not None and self.accumulator.frames > 0:  # (the tracer has closed that scene: one of the shader's own)
+            old_scene = DeviceScene(flatten.flatten_world(self._before), q.scene.device)
+            probe["queries"] = WorldQueries(old_scene)
+        try:
+            e, variance = self.accumulator.update(e, frame, self.tracer.camera, samples=taken, world=self.world, queries=q, probe=probe)
+        finally:
+            if old_scene is not None:
+                old_scene.close()
+            self.accumulator._prev_queries = None  # (its scene is the tracer's to close)
+        self._before = copy.copy(self.world)
+        self._before.shapes = [copy.copy(s) for s in self.world.shapes]
+        self.last_variance = variance
+        self.frame_no += 1
+        if self.filtered:
+            e, _ = q.variance_filtered(e, frame, variance=variance, **self.params)
+        mat = q.materials(frame)
+        lit = np.asarray(mat.emitted) + np.asarray(mat.brdf_color) * e[None]
+        return np.where(np.asarray(mat.hit)[..., None], lit, self._background(frame))
+
+
 def scatter_ray(brdf, pcg, in_dir, point, normal):
     """``brdf.scatter_ray`` (materials.py:132-152, 175-196; the orthonormal basis of geometry.py:247-262) in Python floats with
     ``x * x`` for ``x**2``, for a BRDF that may be a parameter holder (by class name) -> (origin, direction, tmin)."""
